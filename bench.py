@@ -18,8 +18,10 @@ step are in flight together, a GPU holds 1/N of their path slots) -- total work 
 `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run on 127.0.0.1) and refuses to run when
 fewer than N devices are visible.
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
-  north_star    the Sponza-class value again with the per-GPU rate the 8-GPU target needs;
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and reports the headline (with the Sponza-class workload
+also `north_star`: the value again with the per-GPU rate the 8-GPU target needs); --dump-outputs DIR writes the accumulator of the last
+timed step (and with --denoise its denoised image) as DIR/<name>.npy.  With --full the line also carries
+  north_star    as in a plain run;
   roofline      the dominant kernel against the roof that bounds it, and under "kernels" the same for every kernel of the step.
                 "hbm" kernels: frac = bytes that CROSS THE MEMORY INTERFACE per launch (rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this
                 command, calibrated, committed as profiles/pmc_latest_<workload>.json) / the launch time measured in THIS run / 8 TB/s --
@@ -504,6 +506,25 @@ def secondary_line(name, args, device, width=0, height=0, steps=5, parity=True, 
     return line
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: bytes of all arrays together
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array (H, W, C) float32 over the same pixels -> outdir/<name>.npy.  When together they pass DUMP_LIMIT_BYTES,
+    each is written as (n, C): the same n pixels of every array, drawn with a fixed seed and kept in pixel order, so that two runs with the
+    same arguments write the same pixels."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = None
+    if total > DUMP_LIMIT_BYTES:
+        h, w = next(iter(arrays.values())).shape[:2]
+        n = int(h * w * ((DUMP_LIMIT_BYTES - 4096) / total))  # (4 KB left for the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a if keep is None else a.reshape(-1, a.shape[-1])[keep])
+
+
 ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "hbm_frac", "algorithmic_frac", "issue_frac", "active_lanes", "l2_hit_rate",
                  "avg_launch_ms", "launches", "traffic")
 FINAL_LINE_LIMIT = 6144  # bytes: the driver keeps the tail of stdout; round 4's single 33 KB line could not be parsed from it
@@ -590,9 +611,11 @@ def emit(result):
 
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this command under torch.distributed.run (one process per GPU,
-    rendezvous on 127.0.0.1) and become that launcher.  Refuses when fewer than N devices are visible -- unless BENCH_SHARE_GPU=1
-    (all ranks on device 0 over gloo: a functional check of the N > 1 code on a single-GPU box, not a measurement)."""
+    rendezvous on 127.0.0.1) as a child process and exit with its status.  Refuses when fewer than N devices are visible -- unless BENCH_SHARE_GPU=1
+    (all ranks on device 0 over gloo: a functional check of the N > 1 code on a single-GPU box, not a measurement).  Counting the devices
+    opens the GPU in this process, so the launcher is started as a child rather than exec'd in its place."""
     import socket
+    import subprocess
     import torch
     share = os.environ.get("BENCH_SHARE_GPU") == "1"
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -607,7 +630,7 @@ def spawn_ranks(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -628,7 +651,7 @@ def main():
     ap.add_argument("--parity-spp", type=int, default=0,
                     help="frames (1 spp each) of the parity leg; 0 = the configuration's own sample count (atrium 256, helmet 64, street 64, glass 512)")
     ap.add_argument("--also", default=None,
-                    help="comma-separated lines measured after the headline on a single GPU and reported under \"also\" (" + ", ".join(sorted(ALSO_LINES)) + "): by default `"
+                    help="with --full: comma-separated lines measured after the headline on a single GPU and reported under \"also\" (" + ", ".join(sorted(ALSO_LINES)) + "): by default `"
                          + ALSO_DEFAULT + "` next to the atrium -- every other configuration of BASELINE.json, the ones with their own scene with a CPU baseline and parity leg; "
                          "`--also none` switches it off")
     ap.add_argument("--denoise", action="store_true",
@@ -647,7 +670,7 @@ def main():
                          "parity leg; resolution / depth / spp default to those of --workload (override: --width --height --depth --parity-spp); the scene's first camera")
     ap.add_argument("--hdrfile", default=None, help="Radiance .hdr environment for --scenefile (default: std_env.hdr if --workload uses one, else the physical sky)")
     ap.add_argument("--depth", type=int, default=0, help="maxDepth override (default: the workload's)")
-    ap.add_argument("--no-uncut", action="store_true", help="skip the second timed run on the geometry AS LOADED (no alpha cut) that the default single-GPU run reports as `value_uncut_geometry`")
+    ap.add_argument("--no-uncut", action="store_true", help="skip the second timed run on the geometry AS LOADED (no alpha cut) that a single-GPU --full run reports as `value_uncut_geometry`")
     ap.add_argument("--frame-queue", type=int, default=0,
                     help="issue the frames through mi_pt_render_frame ONE CALL PER FRAME -- the reference's onRender cadence, INTEGRATION.md's stub -- with mi_pt_set_frame_queue(N): the library "
                          "holds the calls back and issues N frames at a time (N replaces --in-flight; same image).  N = 1: one frame per set of launches, no batching at all")
@@ -659,9 +682,16 @@ def main():
                          "groups of in_flight * n_gpus (capped at 1024).  Default 128 (helmet 3809 / 3927 Msamples/s at 64 / 128; 256 on the glass workload, whose "
                          "volume random walks leave a long tail of ~100 nearly empty bounce iterations per batch: 238 / 469 / 559 / 605 Msamples/s at 32 / 128 / 128 "
                          "(round 3) / 256 frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: counter passes and the per-kernel roofline table, the uncut-geometry value, "
+                         "the CPU baseline + parity leg and the `also` configurations (--no-cpu-baseline, --no-uncut, --also, --cpu-seconds and --parity-spp shape "
+                         "this part).  Without it a run sets up, warms up, times --steps steps and reports the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32): the accumulator, and with --denoise the denoised "
+                         f"image; above {DUMP_LIMIT_BYTES // 10**6} MB in all, the same fixed, seeded sample of pixels from each")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        spawn_ranks(args.gpus)  # does not return: this process becomes the launcher of N ranks of the same command
+        spawn_ranks(args.gpus)  # does not return: this process waits for the launcher of N ranks of the same command and exits with its status
 
     import torch
     from vk_gltf_renderer_amd import _capi as capi
@@ -804,33 +834,16 @@ def main():
     if rank == 0:
         img = (reduced if dist is not None else accum).cpu().numpy()
         assert np.isfinite(img).all()
-        if os.environ.get("BENCH_DUMP"):  # test hook: the final frame (and its denoised version) of this run
+        if os.environ.get("BENCH_DUMP") or args.dump_outputs:  # the final frame (and its denoised version) of the timed steps
             dump = {"accum": img}
             if args.denoise:
                 bind(total if dist is not None else local)
                 dump["denoised"] = tracer.denoise_svgf(iterations=5, read=True)
                 bind(local)
-            np.savez(os.environ["BENCH_DUMP"], **dump)
-        static = ("bvhNodeCount", "bvhTriangleCount", "bvhNodeBytes", "bvhTriangleBytes")
-
-        def counter_pass(depth):
-            # deterministic: same frames -> same counts; rank 0's tiles; 4 sequential frames
-            ctr = make_tracer(True)
-            p = ptmod.default_params()
-            p.maxDepth, p.numSamples, p.pixelAngle, p.focalDistance = depth, 1, pixel_angle, focal
-            n = min(frames_timed, 4)
-            ptmod.HeadlessRenderer(ctr, p).render(n)
-            st = ctr.stats()
-            ctr.close()
-            return {k: (v if k in static else v / n) for k, v in st.items()}
-
-        per_frame = counter_pass(w["depth"])
-        first = counter_pass(1) if w["depth"] >= 1 else dict(per_frame)  # bounce 0 alone: paths end after their first shade
-        # the timed frames belong to this rank's tiles: timing and counters are both rank 0's
-        pmc = load_pmc(args.workload, F, W, H) if world == 1 else None  # (the committed counter passes are single-GPU runs)
-        kernels = kernel_table(per_frame, first, timing, frames_timed, F, pmc, guides=args.denoise)
-        roof = roofline_of(kernels, pmc)
-        keys = ("cameraPaths", "segments", "surfaceHits", "shadowRays", "nodesPrimary", "trisPrimary", "nodesClosest", "trisClosest", "nodesShadow", "trisShadow", "textureTaps")
+            if os.environ.get("BENCH_DUMP"):  # (test hook)
+                np.savez(os.environ["BENCH_DUMP"], **dump)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, dump)
         assert world == args.gpus
         result = {
             "metric": "Msamples/s (and ms/frame @ fixed spp) 1080p & 4K, 1/2/4/8 MI355X", "value": round(value, 3), "unit": "Msamples/s",
@@ -847,52 +860,77 @@ def main():
                        "library": capi.pt_lib().mi_pt_version().decode()},
             "ms_per_frame": round(elapsed / frames_timed * 1e3, 5),
             "timed_region_s": round(elapsed, 3), "scene_build_s": round(create_s, 3),
-            "roofline": roof,
-            "kernels": kernels,
-            "streams": overlap_note(kernels, elapsed / frames_timed * 1e3),
-            "per_frame": {k: round(per_frame[k], 1) for k in keys},
-            "per_frame_bounce0": {k: round(first[k], 1) for k in keys},
             "frame_ms_device": round(timing["totalMs"] / frames_timed, 4),
             "device_memory_GB": {"scene": round(mem["sceneBytes"] / 1e9, 3), "path_state_queues_images": round(mem["rendererBytes"] / 1e9, 3)},
             "bytes_per_path_slot": round(mem["pathStateBytes"] / max(1, mem["pathSlots"]), 1),
-            "node_visits_per_secondary_ray": round(per_frame["nodesClosest"] / max(1.0, per_frame["segments"] - per_frame["cameraPaths"]), 2),
-            "triangle_tests_per_secondary_ray": round(per_frame["trisClosest"] / max(1.0, per_frame["segments"] - per_frame["cameraPaths"]), 2),
         }
         if args.workload == NORTH_STAR["workload"] and not (args.width or args.height):
             result["north_star"] = dict(NORTH_STAR, workload=result["config"]["workload"], value=result["value"], unit="Msamples/s", n_gpus=world,
                                         value_per_gpu=round(value / world, 3), frac_of_needed_per_gpu=round(value / world / NORTH_STAR["needs_per_gpu_Msamples_s"], 3))
-        if world == 1 and args.alpha_cut > 0 and alpha_cut_dropped > 0 and not args.no_uncut:
-            # The same timed region on the geometry AS LOADED (no load-time alpha cut: a preprocessing step the reference does not perform on an asset without
-            # opacity micro-maps) -- reported next to `value`, which is measured on the cut geometry
-            tracer.close()
-            try:
-                result["value_uncut_geometry"] = uncut_value(args, w, W, H, F, frames_step, local_rank, hdr, frame_info, params, min(args.steps, 5))
-            except Exception as e:  # noqa: BLE001
-                result["value_uncut_geometry"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1:
-            tracer.close()  # (its path state is not needed any more; the parity leg's tracer may want as much again)
-            try:
-                result["cpu_baseline"], result["parity"] = cpu_baseline_and_parity(scene, w, W, H, F, args.cpu_seconds, lambda: make_tracer(False, partition=False), params,
-                                                                                   args.parity_spp)
-            except Exception as e:  # noqa: BLE001  (the measured line stands even if the checker's leg cannot run)
-                result["cpu_baseline"] = result["parity"] = {"error": f"{type(e).__name__}: {e}"}
-        # Next to the default line (the Sponza-class atrium, configs[2]), on the same GPU: every other configuration of BASELINE.json --
-        # helmet (configs[1]) and the same at 3840x2160, street (configs[3], 4K), glass + denoise (configs[4]) -- each scene with its own CPU
-        # baseline + full-size parity leg.
-        default_run = args.workload == NORTH_STAR["workload"] and not (args.width or args.height or args.denoise)
-        also = args.also if args.also is not None else (ALSO_DEFAULT if default_run else "none")
-        if also != "none" and world == 1:
-            tracer.close()  # (its ~80 GB of path state are not needed any more)
-            result["also"] = {}
-            for name in also.split(","):
-                wl, aw, ah, den, par = ALSO_LINES[name]
-                try:  # (a secondary line that fails -- e.g. out of device memory next to another tenant -- must not take the headline with it)
-                    result["also"][name] = secondary_line(wl, args, local_rank, width=aw, height=ah, steps=5, parity=par and not args.no_cpu_baseline, denoise=den)
+        # --full: what takes runs of its own -- the counter passes behind the per-kernel roofline table, the uncut-geometry value, the CPU baseline +
+        # parity leg and the other configurations
+        if args.full:
+            static = ("bvhNodeCount", "bvhTriangleCount", "bvhNodeBytes", "bvhTriangleBytes")
+
+            def counter_pass(depth):
+                # deterministic: same frames -> same counts; rank 0's tiles; 4 sequential frames
+                ctr = make_tracer(True)
+                p = ptmod.default_params()
+                p.maxDepth, p.numSamples, p.pixelAngle, p.focalDistance = depth, 1, pixel_angle, focal
+                n = min(frames_timed, 4)
+                ptmod.HeadlessRenderer(ctr, p).render(n)
+                st = ctr.stats()
+                ctr.close()
+                return {k: (v if k in static else v / n) for k, v in st.items()}
+
+            per_frame = counter_pass(w["depth"])
+            first = counter_pass(1) if w["depth"] >= 1 else dict(per_frame)  # bounce 0 alone: paths end after their first shade
+            # the timed frames belong to this rank's tiles: timing and counters are both rank 0's
+            pmc = load_pmc(args.workload, F, W, H) if world == 1 else None  # (the committed counter passes are single-GPU runs)
+            kernels = kernel_table(per_frame, first, timing, frames_timed, F, pmc, guides=args.denoise)
+            roof = roofline_of(kernels, pmc)
+            keys = ("cameraPaths", "segments", "surfaceHits", "shadowRays", "nodesPrimary", "trisPrimary", "nodesClosest", "trisClosest", "nodesShadow", "trisShadow", "textureTaps")
+            result.update({
+                "roofline": roof,
+                "kernels": kernels,
+                "streams": overlap_note(kernels, elapsed / frames_timed * 1e3),
+                "per_frame": {k: round(per_frame[k], 1) for k in keys},
+                "per_frame_bounce0": {k: round(first[k], 1) for k in keys},
+                "node_visits_per_secondary_ray": round(per_frame["nodesClosest"] / max(1.0, per_frame["segments"] - per_frame["cameraPaths"]), 2),
+                "triangle_tests_per_secondary_ray": round(per_frame["trisClosest"] / max(1.0, per_frame["segments"] - per_frame["cameraPaths"]), 2),
+            })
+            if world == 1 and args.alpha_cut > 0 and alpha_cut_dropped > 0 and not args.no_uncut:
+                # The same timed region on the geometry AS LOADED (no load-time alpha cut: a preprocessing step the reference does not perform on an asset without
+                # opacity micro-maps) -- reported next to `value`, which is measured on the cut geometry
+                tracer.close()
+                try:
+                    result["value_uncut_geometry"] = uncut_value(args, w, W, H, F, frames_step, local_rank, hdr, frame_info, params, min(args.steps, 5))
                 except Exception as e:  # noqa: BLE001
-                    result["also"][name] = {"error": f"{type(e).__name__}: {e}"}
-                    import gc
-                    gc.collect()
-                    torch.cuda.empty_cache()
+                    result["value_uncut_geometry"] = {"error": f"{type(e).__name__}: {e}"}
+            if not args.no_cpu_baseline and world == 1:
+                tracer.close()  # (its path state is not needed any more; the parity leg's tracer may want as much again)
+                try:
+                    result["cpu_baseline"], result["parity"] = cpu_baseline_and_parity(scene, w, W, H, F, args.cpu_seconds, lambda: make_tracer(False, partition=False), params,
+                                                                                       args.parity_spp)
+                except Exception as e:  # noqa: BLE001  (the measured line stands even if the checker's leg cannot run)
+                    result["cpu_baseline"] = result["parity"] = {"error": f"{type(e).__name__}: {e}"}
+            # Next to the default line (the Sponza-class atrium, configs[2]), on the same GPU: every other configuration of BASELINE.json --
+            # helmet (configs[1]) and the same at 3840x2160, street (configs[3], 4K), glass + denoise (configs[4]) -- each scene with its own CPU
+            # baseline + full-size parity leg.
+            default_run = args.workload == NORTH_STAR["workload"] and not (args.width or args.height or args.denoise)
+            also = args.also if args.also is not None else (ALSO_DEFAULT if default_run else "none")
+            if also != "none" and world == 1:
+                tracer.close()  # (its ~80 GB of path state are not needed any more)
+                result["also"] = {}
+                for name in also.split(","):
+                    wl, aw, ah, den, par = ALSO_LINES[name]
+                    try:  # (a secondary line that fails -- e.g. out of device memory next to another tenant -- must not take the headline with it)
+                        result["also"][name] = secondary_line(wl, args, local_rank, width=aw, height=ah, steps=5, parity=par and not args.no_cpu_baseline, denoise=den)
+                    except Exception as e:  # noqa: BLE001
+                        result["also"][name] = {"error": f"{type(e).__name__}: {e}"}
+                        import gc
+                        gc.collect()
+                        torch.cuda.empty_cache()
         emit(result)
     tracer.close()
     if dist is not None:

@@ -1,4 +1,4 @@
-"""bench.py's reporting contract, checked without a GPU: the roofline table cannot print a fraction above 1 (round-3 review: the algorithmic
+"""bench.py's reporting contract, checked without a GPU (one test, marked gpu, runs a plain and a --full run of the box workload): the roofline table cannot print a fraction above 1 (round-3 review: the algorithmic
 byte model printed 1.05 / 1.10 / 1.27), every configuration of the default run finds its committed counter passes, the rank launcher
 refuses what it cannot run, and the committed round-4 line obeys all of it."""
 import json
@@ -191,3 +191,53 @@ def test_step_shape_of_strong_and_weak_scaling():
         for mode in ("strong", "weak"):
             F, _ = bench.step_shape(mode, n, 128, 256, 3840, 2160)
             assert F * 3840 * 2160 / n <= bench.SLOT_BUDGET * 1.02 and (F % 64 == 0 or F < 64)
+
+
+def test_dump_outputs_whole_or_one_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays within DUMP_LIMIT_BYTES are written whole; above it every array is cut to the SAME seeded sample of pixels (in pixel
+    order), the files stay within the limit, and a second call writes the same arrays."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    a = rng.random((64, 96, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"accum": a})
+    assert os.listdir(tmp_path / "whole") == ["accum.npy"]
+    got = np.load(tmp_path / "whole" / "accum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40000)  # (two 98-KB images)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"accum": a, "denoised": 2 * a})
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["accum.npy", "denoised.npy"] and sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 40000
+    s, t = np.load(tmp_path / "s1" / "accum.npy"), np.load(tmp_path / "s1" / "denoised.npy")
+    assert s.dtype == np.float32 and s.ndim == 2 and s.shape[1] == 4 and 0 < s.shape[0] < 64 * 96
+    assert np.array_equal(t, 2 * s)  # the same pixels of both arrays
+    flat = a.reshape(-1, 4)
+    rows = [int(np.nonzero((flat == r).all(1))[0][0]) for r in s]
+    assert rows == sorted(rows)  # pixel order
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain run sets up, warms up, times --steps steps and prints the headline: no counter passes, kernel table, CPU baseline or parity leg in its record;
+    --dump-outputs writes the accumulator of the last timed step (the array the BENCH_DUMP test hook saves).  --full adds the rest, as the default run did."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "box", "--frames-per-step", "8", "--in-flight", "4"]
+    env = dict(os.environ, BENCH_DUMP=str(tmp_path / "hook.npz"), BENCH_FULL=str(tmp_path / "plain.json"))
+    r = subprocess.run(base + ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    full = json.load(open(tmp_path / "plain.json"))
+    assert not {"kernels", "roofline", "per_frame", "cpu_baseline", "parity", "also", "value_uncut_geometry"} & set(full)
+    assert os.listdir(tmp_path / "out") == ["accum.npy"]
+    acc = np.load(tmp_path / "out" / "accum.npy")
+    assert acc.dtype == np.float32 and acc.shape == (256, 256, 4) and np.isfinite(acc).all() and acc[..., :3].max() > 0
+    assert np.array_equal(acc, np.load(tmp_path / "hook.npz")["accum"])
+    env = dict(os.environ, BENCH_FULL=str(tmp_path / "full.json"))
+    r = subprocess.run(base + ["--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    full = json.load(open(tmp_path / "full.json"))
+    assert {"kernels", "roofline", "per_frame", "per_frame_bounce0"} <= set(full) and full["roofline"]["kernel"] in full["kernels"]

@@ -57,7 +57,7 @@ pick = {"shade_first": lambda n: n.startswith("k_shade<false") and n.endswith("t
 out = {"round": int(sys.argv[4]) if len(sys.argv) > 4 else 2, "workload": workload, "frames_in_flight": frames, "resolution": res,
        "fetch_size_calibration": (os.path.join("profiles", os.path.basename(calib_path)) + " (tools/calib_fetch.hip: counter / true bytes measured for 16-B streams and 16 / 48 / 80-B gathers)") if calib else "the guide (wide streaming reads): FETCH_SIZE x 2",
        "fetch_size_factor": "per kernel, see kernels[*].fetch_counter_over_true" if calib else 2.0,
-       "command": f"rocprofv3 --pmc <one counter group per pass: FETCH_SIZE | WRITE_SIZE | SQ_* | TCC_*> -- python bench.py --workload {workload}" + (f" --width {res[0]} --height {res[1]}" if (workload == "helmet" and res[0] == 3840) else "") + (" --denoise" if os.environ.get("PMC_DENOISE") else "") + " --steps 3 --warmup 1 --no-cpu-baseline --also none",
+       "command": f"rocprofv3 --pmc <one counter group per pass: FETCH_SIZE | WRITE_SIZE | SQ_* | TCC_*> -- python bench.py --workload {workload}" + (f" --width {res[0]} --height {res[1]}" if (workload == "helmet" and res[0] == 3840) else "") + (" --denoise" if os.environ.get("PMC_DENOISE") else "") + " --steps 3 --warmup 1 --full --no-cpu-baseline --also none",
        "note": "hbm_bytes_per_launch = FETCH_SIZE / (counter-over-true ratio of the kernel's access class) + WRITE_SIZE / (ratio of its writes); the raw counters and the bounds [raw, 2 x raw] are kept next to it", "kernels": {}}
 for key, match in pick.items():
     cands = sorted((n for n, k in summary.items() if match(n) and "FETCH_SIZE" in k and "WRITE_SIZE" in k),

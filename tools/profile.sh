@@ -11,7 +11,7 @@ run() { # name, rocprof args...
   local name=$1; shift
   ( cd /tmp && timeout ${PROFILE_TIMEOUT:-200} rocprofv3 "$@" --output-format csv -d "$out/$name" -- python "$OLDPWD/bench.py" "${BENCH_ARGS[@]}" > "$out/$name.log" 2>&1 )
 }
-BENCH_ARGS=("$@" --no-cpu-baseline --also none)
+BENCH_ARGS=("$@" --full --no-cpu-baseline --also none)
 for p in ${PASSES:-stats sq sq2 tcc fetch write}; do
   case $p in
     stats) run stats --kernel-trace --stats ;;

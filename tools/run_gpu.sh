@@ -9,7 +9,7 @@
 #   mbvalu                     tools/microbench_valu.hip (build it first: hipcc --offload-arch=gfx950 -O3 tools/microbench_valu.hip -o tools/_scratch/mb_valu)
 cd "$(dirname "$0")/.."; ulimit -c 0
 O=$PWD/gpurun_out; mkdir -p $O
-N="--no-cpu-baseline --also none"
+N="--full --no-cpu-baseline --also none"
 val() { python3 -c "
 import json,sys
 j=json.loads([l for l in open('$1'.replace('.json','.err')) if l.startswith('{')][-1]); k=j['kernels']  # (the full record goes to stderr; stdout ends with the compact line)
@@ -35,7 +35,7 @@ envab() { # envab <tag> <VAR> "<values...>" <workloads...>: the product build wi
 case "$1" in
   envab) shift; envab "$@" ;;
   line)  # the full default line (headline + every other configuration with CPU legs), as the driver runs it
-    timeout 1500 python bench.py --steps 20 --warmup 5 > $O/r06_bench_default_a.json 2> $O/r06_bench_default_a.err; echo "bench rc $?"; tail -c 600 $O/r06_bench_default_a.err
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_default_a.json 2> $O/r06_bench_default_a.err; echo "bench rc $?"; tail -c 600 $O/r06_bench_default_a.err
     python3 - <<'PY'
 import json
 j=json.loads(open('gpurun_out/r06_bench_default_a.json').read().strip().splitlines()[-1])
