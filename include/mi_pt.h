@@ -195,7 +195,11 @@ MI_PT_API int mi_pt_set_environment(MiPt* pt, const MiPtEnvironment* env);
  * depth and the path-state queues; resets accumulation. */
 MI_PT_API int mi_pt_resize(MiPt* pt, int width, int height);
 
-/* replaces the vkCmdUpdateBuffer of bFrameInfo / bSkyParams (reference: src/renderer.cpp:675-708) */
+/* replaces the vkCmdUpdateBuffer of bFrameInfo / bSkyParams (reference: src/renderer.cpp:675-708).
+ * info->visualization: a debug view MI_VIZ_* (mi_pt_shaderio.h; the reference's SceneFrameInfo::visualization).  A colour view replaces the
+ * sample of a first ray at its surface hit (misses, selection, depth and guides are the image's); MI_VIZ_CLAY shades with a clay material at
+ * every hit; MI_VIZ_OPACITY_MICROMAP colours the closest hit with alpha-tested geometry taken as opaque by whether its alpha is still tested at
+ * run time.  0 and any value outside 1..MI_VIZ_COUNT-1 render the image.  The shade counters of mi_pt_get_stats stay zero under a view. */
 MI_PT_API int mi_pt_set_frame_info(MiPt* pt, const MiSceneFrameInfo* info);
 MI_PT_API int mi_pt_set_sky(MiPt* pt, const MiSkyPhysicalParameters* sky);
 

@@ -156,6 +156,43 @@ enum MiSceneFrameInfoFlags
   MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 1 << 4
 };
 
+/* MiSceneFrameInfo::visualization: the debug views (reference: shaders/shaderio.h:100-133, applyVisualization in
+ * shaders/common.h.slang:32-164).  MI_VIZ_RENDERED is the path-traced image; any value outside 1..29 renders as it. */
+enum MiVisualization
+{
+  MI_VIZ_RENDERED                      = 0,
+  MI_VIZ_BASE_COLOR                    = 1,
+  MI_VIZ_METALLIC                      = 2,
+  MI_VIZ_ROUGHNESS                     = 3,
+  MI_VIZ_NORMAL_SHADING                = 4,
+  MI_VIZ_NORMAL_GEOMETRIC              = 5,
+  MI_VIZ_TANGENT                       = 6,
+  MI_VIZ_BITANGENT                     = 7,
+  MI_VIZ_EMISSIVE                      = 8,
+  MI_VIZ_OPACITY                       = 9,
+  MI_VIZ_TEXCOORD0                     = 10,
+  MI_VIZ_TEXCOORD1                     = 11,
+  MI_VIZ_CLAY                          = 12,
+  MI_VIZ_TRIANGLE_ID                   = 13,
+  MI_VIZ_FACE_ORIENTATION              = 14,
+  MI_VIZ_OCCLUSION                     = 15,
+  MI_VIZ_CLEARCOAT_FACTOR              = 16,
+  MI_VIZ_CLEARCOAT_ROUGHNESS           = 17,
+  MI_VIZ_CLEARCOAT_NORMAL              = 18,
+  MI_VIZ_SHEEN_COLOR                   = 19,
+  MI_VIZ_SHEEN_ROUGHNESS               = 20,
+  MI_VIZ_SPECULAR_FACTOR               = 21,
+  MI_VIZ_SPECULAR_COLOR                = 22,
+  MI_VIZ_TRANSMISSION_FACTOR           = 23,
+  MI_VIZ_IRIDESCENCE_FACTOR            = 24,
+  MI_VIZ_IRIDESCENCE_THICKNESS         = 25,
+  MI_VIZ_ANISOTROPY_STRENGTH           = 26,
+  MI_VIZ_DIFFUSE_TRANSMISSION_FACTOR   = 27,
+  MI_VIZ_DIFFUSE_TRANSMISSION_COLOR    = 28,
+  MI_VIZ_OPACITY_MICROMAP              = 29,
+  MI_VIZ_COUNT                         = 30
+};
+
 /* reference: shaders/shaderio.h:148-168 (396 B) */
 typedef struct MiSceneFrameInfo
 {

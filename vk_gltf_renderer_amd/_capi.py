@@ -5,6 +5,7 @@ function prototype is declared once here.  No arithmetic of the hot path lives i
 """
 import ctypes as C
 import os
+from enum import IntEnum
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -147,6 +148,43 @@ MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
 MI_LIGHT_NONE, MI_LIGHT_DIRECTIONAL, MI_LIGHT_SPOT, MI_LIGHT_POINT = 0, 1, 2, 3  # shaders/gltf_scene_io.h.slang:72-78
+
+
+class Visualization(IntEnum):
+    """MiSceneFrameInfo.visualization, the debug views (include/mi_pt_shaderio.h: MiVisualization).  Any other value renders the image."""
+    RENDERED = 0
+    BASE_COLOR = 1
+    METALLIC = 2
+    ROUGHNESS = 3
+    NORMAL_SHADING = 4
+    NORMAL_GEOMETRIC = 5
+    TANGENT = 6
+    BITANGENT = 7
+    EMISSIVE = 8
+    OPACITY = 9
+    TEXCOORD0 = 10
+    TEXCOORD1 = 11
+    CLAY = 12
+    TRIANGLE_ID = 13
+    FACE_ORIENTATION = 14
+    OCCLUSION = 15
+    CLEARCOAT_FACTOR = 16
+    CLEARCOAT_ROUGHNESS = 17
+    CLEARCOAT_NORMAL = 18
+    SHEEN_COLOR = 19
+    SHEEN_ROUGHNESS = 20
+    SPECULAR_FACTOR = 21
+    SPECULAR_COLOR = 22
+    TRANSMISSION_FACTOR = 23
+    IRIDESCENCE_FACTOR = 24
+    IRIDESCENCE_THICKNESS = 25
+    ANISOTROPY_STRENGTH = 26
+    DIFFUSE_TRANSMISSION_FACTOR = 27
+    DIFFUSE_TRANSMISSION_COLOR = 28
+    OPACITY_MICROMAP = 29
+
+
+MI_VIZ_COUNT = 30
 
 P = C.POINTER
 VP = C.c_void_p

@@ -37,6 +37,7 @@ void GltfRenderer::registerParameters(ParameterRegistry* r)
   r->add("useInfinitePlane", "Ground plane", &s.useInfinitePlane);
   r->add("isShadowCatcher", "Ground plane only catches shadows", &s.isShadowCatcher);
   r->add("infinitePlaneDistance", "Ground plane height", &s.infinitePlaneDistance);
+  r->add("visualization", "Visualization Mode", &s.visualization);  // reference: src/renderer.cpp:162 (MiVisualization)
   r->add("device", "HIP device ordinal", &m_resources.device);
   r->add("recomputeTangents", "Recreate all tangents after loading: [off:0, UV gradient:1, MikkTSpace:2]", &m_recomputeTangents);
   // the reference consumes baked opacity micro-maps (EXT_mesh_opacity_micromap) when --useOpacityMicromap is on (src/main.cpp:114-115);
@@ -352,6 +353,7 @@ void GltfRenderer::onRender(StreamHandle cmd, bool headless, uint32_t headlessFr
     f.infinitePlaneMetallic     = s.infinitePlaneMetallic;
     f.infinitePlaneRoughness    = s.infinitePlaneRoughness;
     f.shadowCatcherDarkenAmount = std::max(s.shadowCatcherDarkness, 0.0f);
+    f.visualization             = s.visualization;
     m_resources.skyParams.yIsUp = m_resources.camera.up[1] > 0.5f;  // reference: src/renderer.cpp:707
     m_pathTracer.onRender(cmd, m_resources);
     done = m_pathTracer.framesLastCall();
@@ -682,7 +684,12 @@ void GltfRenderer::saveHeadlessOutputImage()
     const int source = (m_pathTracer.isDenoiserEnabled() && m_pathTracer.hasValidDenoisedOutput()) ? 1 : 0;
     if(source)
       printf("DENOISER passes=%d final_image=denoised\n", m_pathTracer.denoiseCount());
-    if(mi_pt_tonemap(m_pathTracer.handle(), &m_resources.tonemapperData, source, -1.0f, ldr.data(), nullptr) != MI_PT_OK)
+    // a debug view is shown as it is, without the tonemapper; clay is shaded and keeps it (reference: src/renderer.cpp:1040-1046)
+    MiTonemapperData tm  = m_resources.tonemapperData;
+    const int        viz = m_resources.settings.visualization;
+    if(viz > MI_VIZ_RENDERED && viz < MI_VIZ_COUNT && viz != MI_VIZ_CLAY)
+      tm.isActive = 0;
+    if(mi_pt_tonemap(m_pathTracer.handle(), &tm, source, -1.0f, ldr.data(), nullptr) != MI_PT_OK)
     {
       fprintf(stderr, "tonemap: %s\n", mi_pt_last_error());
       return;

@@ -27,6 +27,7 @@ struct Settings  // reference defaults: src/resources.hpp:82-131
   float         infinitePlaneMetallic  = 0.0f;
   float         infinitePlaneRoughness = 0.5f;
   float         shadowCatcherDarkness  = 0.0f;
+  int           visualization          = MI_VIZ_RENDERED;  // MiVisualization (reference: Settings::visualization, shaderio::Visualization)
 };
 
 // reference: AnimationControl (src/ui_animation.hpp:51-85).  Interactive playback there advances by the UI's frame time; a

@@ -1232,6 +1232,11 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   // the closest-hit walks run their alpha machinery only where some alpha test has an open outcome: a scene whose non-opaque instances all have
   // alphaMode OPAQUE (transmissive glass) takes the plain kernels -- every candidate commits (INST_ALPHA_PASSES)
   c.hasAlphaClosest  = c.hasAlpha && pt->hasAlphaTest;
+  // debug views (MiSceneFrameInfo::visualization, pt_visualize.h): their own shade kernel; a value the reference does not know renders the image
+  c.visualization    = pt->frameInfo.visualization > MI_VIZ_RENDERED && pt->frameInfo.visualization < MI_VIZ_COUNT;
+  // the opacity-micromap view colours the closest hit with alpha-tested geometry taken as opaque: the closest-hit walks run without their alpha rounds
+  if(pt->frameInfo.visualization == MI_VIZ_OPACITY_MICROMAP)
+    c.hasAlphaClosest = false;
   c.hasTransmissive  = pt->hasTransmissive;
   c.simpleMaterials  = pt->simpleMaterials;
   c.wide             = pt->wide;

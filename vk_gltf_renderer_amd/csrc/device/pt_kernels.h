@@ -25,6 +25,7 @@ struct LaunchCtx
   bool            wide;  // traverse the 8-wide compressed BVH (scene.bvh8Nodes) instead of the BVH2
   bool            collectCounters;
   int             sortMode;  // per-bounce sort of the generic shade kernel: 0 off, 1 surface hits / others / dead, 2 hits grouped by material too
+  bool            visualization;  // fc.frameInfo.visualization is a debug view (1 .. MI_VIZ_COUNT - 1): launchShade runs k_shade_viz
 };
 
 void launchBuildShadeRecords(const DevScene& scene, uint32_t numTris, DevShadeTri* out, hipStream_t s);

@@ -100,13 +100,18 @@ PT_DEV float sqrtExact(float x) { return __ocml_sqrt_f32(x); }
 PT_DEV float logExact(float x) { return __ocml_log_f32(x); }
 PT_DEV float sinExact(float x) { return __ocml_sin_f32(x); }
 PT_DEV float cosExact(float x) { return __ocml_cos_f32(x); }
+PT_DEV float powExact(float x, float y) { return __ocml_pow_f32(x, y); }
 #else  // hipcc's host pass (never runs) and the device headers compiled for the host (tests/host_shim): IEEE by the language
 PT_DEV float divExact(float a, float b) { return a / b; }
 PT_DEV float sqrtExact(float x) { return sqrtf(x); }
 PT_DEV float logExact(float x) { return logf(x); }
 PT_DEV float sinExact(float x) { return sinf(x); }
 PT_DEV float cosExact(float x) { return cosf(x); }
+PT_DEV float powExact(float x, float y) { return powf(x, y); }
 #endif
+
+// IEC 61966-2-1 sRGB OETF: the tonemapper's last step and the debug views' encoding (pt_visualize.h); libm-grade pow in every translation unit
+PT_DEV float srgbOetf(float x) { return x > 0.0031308f ? fmaf(powExact(x, 1.0f / 2.4f), 1.055f, -0.055f) : x * 12.92f; }
 
 PT_DEV float dot(f2 a, f2 b) { return a.x * b.x + a.y * b.y; }
 PT_DEV float dot(f3 a, f3 b);

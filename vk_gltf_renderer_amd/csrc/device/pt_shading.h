@@ -71,9 +71,10 @@ PT_DEV f3 pointOffset(f3 p, f3 p0, f3 p1, f3 p2, f3 n0, f3 n1, f3 n2, f3 bary)  
   return p + tmpu * bary.x + tmpv * bary.y + tmpw * bary.z;
 }
 // V0..V2: the triangle's interleaved vertices (DevPrim::verts); attrs: SHADE_HAS_*; rp / ti are only read when the primitive has
-// uv1 or vertex colours (rp may be null otherwise).
+// uv1 or vertex colours (rp may be null otherwise).  frontFaceOut (optional): whether the ray met the front side, i.e. the geometric normal before
+// it is turned towards the ray (the debug views' face orientation).
 PT_DEV HitState getHitState(const float4* V0, const float4* V1, const float4* V2, uint32_t attrs, const DevPrim* rp, u3 ti, f3 bary, const float* w2o,
-                            const float* o2w, f3 worldRayDir)
+                            const float* o2w, f3 worldRayDir, bool* frontFaceOut = nullptr)
 {
   HitState hit;
   // 9 x 16 B in flight at once
@@ -93,6 +94,8 @@ PT_DEV HitState getHitState(const float4* V0, const float4* V1, const float4* V2
   }
   hit.nrm         = normalize(mulTransposed(w2o, normal));
   bool  frontFace = dot(hit.geonrm, worldRayDir) < 0.0f;
+  if(frontFaceOut)
+    *frontFaceOut = frontFace;
   float sideFlip  = frontFace ? 1.0f : -1.0f;
   f3    shadowPos = pointOffset(position, pos0, pos1, pos2, nrm0 * sideFlip, nrm1 * sideFlip, nrm2 * sideFlip, bary);
   hit.shadowPos   = mulPoint(o2w, shadowPos);

@@ -17,12 +17,7 @@ namespace {
 
 constexpr int HIST_BINS = 256;
 
-__device__ __forceinline__ float srgbOetf(float x)
-{
-  return x > 0.0031308f ? fmaf(powf(x, 1.0f / 2.4f), 1.055f, -0.055f) : x * 12.92f;
-}
-
-__device__ __forceinline__ float3 toSrgb(float3 c)
+__device__ __forceinline__ float3 toSrgb(float3 c)  // (srgbOetf: pt_math.h)
 {
   return make_float3(srgbOetf(c.x), srgbOetf(c.y), srgbOetf(c.z));
 }

@@ -142,10 +142,12 @@ def default_params():
     return p
 
 
-def camera_frame_info(cam, width, height):
-    """Returns (MiSceneFrameInfo, pixelAngle, focalDistance) — reference: src/renderer.cpp:675-705."""
+def camera_frame_info(cam, width, height, visualization=0):
+    """Returns (MiSceneFrameInfo, pixelAngle, focalDistance) — reference: src/renderer.cpp:675-705.  visualization: a debug view
+    (capi.Visualization); 0 is the path-traced image."""
     fi, pa, fd = capi.MiSceneFrameInfo(), C.c_float(), C.c_float()
     capi.host_lib().mi_camera_frame_info(C.byref(cam), width, height, C.byref(fi), C.byref(pa), C.byref(fd))
+    fi.visualization = int(visualization)
     return fi, pa.value, fd.value
 
 
