@@ -55,19 +55,35 @@ MI_PT_API int                  mi_mikktspace(const float* positions, const float
  * image is unchanged up to float rounding of the interpolated vertices (and up to sub-ulp T-junction cracks where a merged coarse piece
  * meets refined ones: ~1e-7 of a card's area, csrc/host/alpha_cut.cpp); the selection image (TraceLow treats every triangle as
  * opaque) reports what is seen through a removed part instead of the alpha-tested instance itself.  Returns the number of (sub-)triangles dropped (>= 0)
- * or a negative MiPtStatus; the MiPtSceneDesc changes (fetch mi_scene_desc again, create the renderer afterwards). */
+ * or a negative MiPtStatus; the MiPtSceneDesc changes (fetch mi_scene_desc again, create the renderer afterwards).
+ * Skinned and morphed primitives (mi_scene_deformation) are never cut: skinning does not commute with the cut's barycentric
+ * re-interpolation of the vertices. */
 MI_PT_API int64_t              mi_scene_cut_alpha(MiScene* scene, int subdivisions);
 
 /* Keyframe animation of node transforms (reference: nvvkgltf::AnimationSystem, src/gltf_scene_animation.hpp:93-122; AnimationInfo
  * src/gltf_scene.hpp:159-189; driven per frame by GltfRenderer::updateAnimation, src/renderer.cpp:2065-2170).  Translation /
- * rotation / scale channels with LINEAR, STEP and CUBICSPLINE samplers; morph weights, skins and KHR_animation_pointer are not
- * evaluated.  mi_scene_update_animation poses the scene at `time` (seconds on the clip's own axis, [start, end] as reported by
+ * rotation / scale channels and morph-target `weights` channels with LINEAR, STEP and CUBICSPLINE samplers; KHR_animation_pointer is
+ * not evaluated.  mi_scene_update_animation poses the scene at `time` (seconds on the clip's own axis, [start, end] as reported by
  * mi_scene_animation_info) and rewrites the matrices of the render-node table and the light placements of mi_scene_desc() in
- * place -- same pointers, same counts -- ready for mi_pt_update_render_nodes() + mi_pt_update_lights().  Returns 1 when
- * something moved, 0 when no channel covered `time`, or a negative MiPtStatus. */
+ * place -- same pointers, same counts -- ready for mi_pt_update_render_nodes() + mi_pt_update_lights(), and the per-frame tables of
+ * mi_scene_deformation() (joint matrices, morph weights), ready for mi_pt_update_deformation().  Returns 1 when something moved
+ * (a node or a weights channel covered `time`), 0 when no channel covered `time`, or a negative MiPtStatus. */
 MI_PT_API int                  mi_scene_num_animations(const MiScene* scene);
 MI_PT_API int                  mi_scene_animation_info(const MiScene* scene, int index, float* start, float* end, char* name, int nameCapacity);
 MI_PT_API int                  mi_scene_update_animation(MiScene* scene, int index, float time);
+
+/* Skins and morph targets (reference: AnimationSystem::parseSkinTasks / parseMorphPrimitives, src/gltf_scene_animation.cpp:196-320).
+ * mi_scene_deformation: the tables mi_pt_set_deformation takes, NULL when the scene deforms nothing.  One entry per unique deforming render
+ * primitive: skinned when a render node with a skin uses it and it has JOINTS_0 / WEIGHTS_0 (the first such node supplies the skin and the
+ * reference node: instances share one deformation), morphed when it has targets AND its mesh has a non-empty `weights` array (the
+ * reference's rule, kept).  Its frame arrays (joint matrices inverse(world[refNode]) * world[joint] * IBM, morph weights of mesh.weights
+ * padded with zeros) are rewritten in place by every mi_scene_update_animation; the pointers stay valid until mi_scene_recompute_tangents,
+ * which rebuilds the tables (re-fetch them).  Nothing is deformed at load.
+ * mi_scene_deform_on_host: the CPU restatement of the device kernel (the reference's computeSkinning / computeMorphTargets, with the
+ * device shaders' rules where the two differ): writes the posed vertices into the scene's own render-primitive streams, so that a renderer
+ * created afterwards -- or the CPU oracle -- sees the pose.  Returns the number of primitives deformed. */
+MI_PT_API const MiPtDeformDesc* mi_scene_deformation(const MiScene* scene);
+MI_PT_API int                   mi_scene_deform_on_host(MiScene* scene);
 
 MI_PT_API int                    mi_hdr_load(const char* path, MiHdr** out);
 MI_PT_API int                    mi_hdr_from_pixels(int width, int height, const float* rgb, MiHdr** out);

@@ -185,6 +185,57 @@ MI_PT_API int mi_pt_update_render_nodes(MiPt* pt, const MiGltfRenderNode* render
  * work in flight; the caller restarts accumulation. */
 MI_PT_API int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights);
 
+/* Vertex deformation of animated scenes: glTF skins (JOINTS_0 / WEIGHTS_0, four influences) and morph targets, evaluated on the device
+ * into the resident geometry (reference: shaders/skinning.comp.slang, shaders/morph.comp.slang dispatched by AnimationVk::dispatchAnimation,
+ * src/gltf_scene_animation_vk.cpp:413-592, from GltfRenderer::updateAnimation, src/renderer.cpp:2065-2170).  Per deforming render primitive:
+ *   morph:  p = base + sum_t w_t dp_t (targets with w_t == 0 skipped), n / t.xyz likewise and then normalised (tangent w kept);
+ *   skin:   p = sum_i w_i (J_i [p, 1]).xyz, n = normalize(sum_i w_i N_i n), t.xyz = normalize(sum_i w_i mat3(J_i) t.xyz) over the influences
+ *           with w_i > 0 and 0 <= j_i < numJoints (an out-of-range joint is skipped; weights are not renormalised), N_i = transpose(inverse(mat3(J_i)));
+ *   both:   morph, then skin, in one pass (the reference's two-pass composition, intermediate normalisation included).
+ * All pointers are host memory, copied by the call. */
+typedef struct MiPtDeformPrimitive
+{
+  int32_t         renderPrimID;    /* the render primitive whose streams are rewritten */
+  uint32_t        vertexCount;     /* must equal the render primitive's */
+  const float*    basePositions;   /* 3 floats / vertex: the rest pose (required) */
+  const float*    baseNormals;     /* 3 floats / vertex, NULL = the normal stream is not deformed */
+  const float*    baseTangents;    /* 4 floats / vertex, NULL = the tangent stream is not deformed */
+  const uint16_t* joints;          /* 4 per vertex; NULL = not skinned */
+  const float*    weights;         /* 4 per vertex; NULL = not skinned */
+  uint32_t        numJoints;       /* joints of the skin: matrices [jointMatrixOffset, + numJoints) of the frame's packed table */
+  uint32_t        jointMatrixOffset;
+  uint32_t        numTargets;      /* 0 = not morphed; weights [morphWeightOffset, + numTargets) of the frame's packed table */
+  uint32_t        morphWeightOffset;
+  const float*    positionDeltas;  /* 3 floats per vertex and target, target-major ([t][v]); required when numTargets > 0 */
+  const float*    normalDeltas;    /* ... or NULL (then requires baseNormals for non-NULL) */
+  const float*    tangentDeltas;   /* ... or NULL (xyz deltas; requires baseTangents for non-NULL) */
+} MiPtDeformPrimitive;
+
+typedef struct MiPtDeformDesc
+{
+  const MiPtDeformPrimitive* prims;
+  int                        numPrims;
+  int                        numJointMatrices;
+  int                        numMorphWeights;
+  const float*               jointMatrices; /* this frame's values: 16 floats per matrix, column-major like objectToWorld */
+  const float*               morphWeights;  /* this frame's values */
+} MiPtDeformDesc;
+
+enum { MI_PT_DEFORM_DEFER_BUILD = 1 }; /* mi_pt_update_deformation: leave the rebuild to the mi_pt_update_render_nodes call that follows */
+
+/* Static upload of the deformation tables, once after mi_pt_create (a copy of base poses, influences and deltas; NULL releases them).
+ * Every primitive is validated (render-primitive range, vertexCount equal to the resident primitive's, no duplicates, offsets within
+ * the totals): MI_PT_ERR_ARGUMENT otherwise.  Nothing is deformed yet: the geometry stays the one of mi_pt_create. */
+MI_PT_API int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc);
+/* One animated frame: takes the packed joint matrices (numJointMatrices x 16 floats) and morph weights (numMorphWeights floats) of
+ * mi_pt_set_deformation's layout, deforms every primitive in ONE launch, then rebuilds the acceleration structure -- unless flags holds
+ * MI_PT_DEFORM_DEFER_BUILD, for a caller that calls mi_pt_update_render_nodes next (one rebuild per animated frame).  Non-finite
+ * values: MI_PT_ERR_ARGUMENT, nothing changes.  Synchronises with the work in flight (queued frames render the old pose). */
+MI_PT_API int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* morphWeights, int flags);
+/* Reads back the resident streams of a render primitive (vertexCount x 3 / 3 / 4 floats); any pointer may be NULL, and a stream the
+ * primitive does not have is left untouched. */
+MI_PT_API int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* normals, float* tangents);
+
 /* replaces PathTracer::onDetach (reference: src/renderer_base.hpp:40) */
 MI_PT_API int mi_pt_destroy(MiPt* pt);
 
@@ -307,8 +358,9 @@ MI_PT_API const char* mi_pt_version(void);
 /* Layout version of the public structs of this header.  It is bumped whenever a struct a caller allocates (MiPtMemory, MiPtStats, MiPtFrameTiming,
  * MiPathtraceParams, ...) grows or changes: the library writes every field of the struct it was compiled with, so a caller built against an older
  * header must refuse to run -- `if(mi_pt_abi_version() != MI_PT_ABI_VERSION) fail` right after loading the library.
- * 6: MiPtMemory grew pathStateBytes / pathSlots (round 5); mi_pt_render_frames refuses maxDepth 0; mi_pt_set_frame_queue. */
-#define MI_PT_ABI_VERSION 6
+ * 6: MiPtMemory grew pathStateBytes / pathSlots (round 5); mi_pt_render_frames refuses maxDepth 0; mi_pt_set_frame_queue.
+ * 7: MiPtDeformPrimitive / MiPtDeformDesc and the deformation entry points (skins and morph targets on the device). */
+#define MI_PT_ABI_VERSION 7
 MI_PT_API int mi_pt_abi_version(void);
 
 #ifdef __cplusplus

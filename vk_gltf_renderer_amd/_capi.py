@@ -132,6 +132,18 @@ class MiPtFrameTiming(C.Structure):
                 ("tracePrimaryLaunches", i32), ("shadeFirstLaunches", i32)]
 
 
+class MiPtDeformPrimitive(C.Structure):
+    _fields_ = [("renderPrimID", i32), ("vertexCount", u32), ("basePositions", C.POINTER(f32)), ("baseNormals", C.POINTER(f32)),
+                ("baseTangents", C.POINTER(f32)), ("joints", C.POINTER(C.c_uint16)), ("weights", C.POINTER(f32)), ("numJoints", u32),
+                ("jointMatrixOffset", u32), ("numTargets", u32), ("morphWeightOffset", u32), ("positionDeltas", C.POINTER(f32)),
+                ("normalDeltas", C.POINTER(f32)), ("tangentDeltas", C.POINTER(f32))]
+
+
+class MiPtDeformDesc(C.Structure):
+    _fields_ = [("prims", C.POINTER(MiPtDeformPrimitive)), ("numPrims", i32), ("numJointMatrices", i32), ("numMorphWeights", i32),
+                ("jointMatrices", C.POINTER(f32)), ("morphWeights", C.POINTER(f32))]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -143,7 +155,8 @@ assert C.sizeof(MiGltfTextureInfo) == 32
 assert C.sizeof(MiGltfShadeMaterial) == 288
 assert C.sizeof(MiSceneFrameInfo) == 396
 
-MI_PT_ABI_VERSION = 6  # include/mi_pt.h
+MI_PT_ABI_VERSION = 7  # include/mi_pt.h
+MI_PT_DEFORM_DEFER_BUILD = 1
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
@@ -204,6 +217,8 @@ HOST_SYMBOLS = {
     "mi_scene_num_animations": (i32, [VP]),
     "mi_scene_animation_info": (i32, [VP, i32, P(f32), P(f32), C.c_char_p, i32]),
     "mi_scene_update_animation": (i32, [VP, i32, f32]),
+    "mi_scene_deformation": (P(MiPtDeformDesc), [VP]),
+    "mi_scene_deform_on_host": (i32, [VP]),
     "mi_hdr_from_pixels": (i32, [i32, i32, P(f32), P(VP)]),
     "mi_hdr_destroy": (None, [VP]),
     "mi_hdr_env": (P(MiPtEnvironment), [VP]),
@@ -249,6 +264,9 @@ PT_SYMBOLS = {
     "mi_pt_abi_version": (i32, []),
     "mi_pt_update_render_nodes": (i32, [VP, P(MiGltfRenderNode), i32, P(C.c_uint8)]),
     "mi_pt_update_lights": (i32, [VP, P(MiGltfLight), i32]),
+    "mi_pt_set_deformation": (i32, [VP, P(MiPtDeformDesc)]),
+    "mi_pt_update_deformation": (i32, [VP, P(f32), P(f32), i32]),
+    "mi_pt_read_vertices": (i32, [VP, i32, P(f32), P(f32), P(f32)]),
 }
 
 

@@ -310,6 +310,23 @@ bool GltfRenderer::updateAnimation()
     ac.play = false;
   if(mi_scene_update_animation(sc, ac.currentAnimation, m_animTime) <= 0)
     return false;
+  // skins and morph targets (reference: AnimationVk::dispatchAnimation from updateAnimation): the static tables once per path-tracer
+  // instance, then per frame the deformation with the rebuild left to mi_pt_update_render_nodes -- one rebuild per animated frame
+  const MiPtDeformDesc* deform = mi_scene_deformation(sc);
+  if(deform && m_deformSetFor != m_pathTracer.handle())
+  {
+    if(mi_pt_set_deformation(m_pathTracer.handle(), deform) != MI_PT_OK)
+    {
+      fprintf(stderr, "updateAnimation: %s\n", mi_pt_last_error());
+      return false;
+    }
+    m_deformSetFor = m_pathTracer.handle();
+  }
+  if(deform && mi_pt_update_deformation(m_pathTracer.handle(), deform->jointMatrices, deform->morphWeights, MI_PT_DEFORM_DEFER_BUILD) != MI_PT_OK)
+  {
+    fprintf(stderr, "updateAnimation: %s\n", mi_pt_last_error());
+    return false;
+  }
   const MiPtSceneDesc* d = mi_scene_desc(sc);
   if(mi_pt_update_render_nodes(m_pathTracer.handle(), d->renderNodes, d->numRenderNodes, d->renderNodeVisible) != MI_PT_OK
      || mi_pt_update_lights(m_pathTracer.handle(), d->lights, d->numLights) != MI_PT_OK)

@@ -55,6 +55,7 @@ private:
   int                 m_alphaCut{4};
   int                 m_animClip{-1};
   float               m_animTime{0.0f};
+  MiPt*               m_deformSetFor{nullptr};  // the path-tracer instance the scene's skin / morph tables were uploaded to
   // sequencer state (set through the registry by the script)
   int                 m_seqFrames{256}, m_seqAverages{64}, m_seqResetFrames{0}, m_seqRenderSystem{0}, m_gltfCamera{0};
   bool                m_seqFlag{false};

@@ -16,6 +16,7 @@
 #include "mi_pt.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
+#include "pt_deform.h"
 #include "pt_kernels.h"
 
 namespace {
@@ -208,6 +209,17 @@ struct MiPt
   std::vector<uint8_t>          matInstFlags;   // per material: INST_FORCE_OPAQUE | INST_CULL_DISABLE | INST_TRANSMISSIVE | INST_ALPHA_PASSES
   std::vector<uint8_t>          matFeatures;    // per material: bit0 volume scatter, bit1 needs the generic shade kernel
   std::vector<uint32_t>         primTriangles;  // per render primitive: triangle count, 0 when it has no usable geometry
+  std::vector<pt::DevPrim>      hostPrims;      // the device addresses of every primitive's streams (mi_pt_read_vertices, deformation)
+  std::vector<uint32_t>         primVertices;   // per render primitive: vertex count
+  // skins and morph targets (mi_pt_set_deformation): static tables, allocated only for a scene that deforms something
+  DevBuf<uint8_t>               deformPool;     // base poses, influences, deltas (16-byte aligned sub-allocations)
+  DevBuf<pt::DeformTask>        deformTasks;
+  DevBuf<uint32_t>              deformBlockTask;
+  DevBuf<float4>                deformJoints;   // 6 float4 per joint matrix (pt_deform.h)
+  DevBuf<float>                 deformWeights;
+  int                           deformJointCount = 0, deformWeightCount = 0;
+  uint32_t                      deformBlocks = 0;
+  bool                          deformSet = false;
   int                           bvhBuilder = 0;
   // frame state
   int                     width = 0, height = 0;
@@ -471,7 +483,14 @@ int buildAccelerationUnguarded(MiPt* pt);
 // EMPTY structure (frames render the environment only) and the error is returned to the caller.
 int buildAcceleration(MiPt* pt)
 {
-  const int rc = buildAccelerationUnguarded(pt);
+  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  const auto        t0          = std::chrono::steady_clock::now();
+  const int         rc          = buildAccelerationUnguarded(pt);
+  if(buildTiming && pt->accelBuilds > 1)  // (the first build's phases are printed by mi_pt_create)
+  {
+    (void)hipDeviceSynchronize();
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "rebuild", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
   if(rc != MI_PT_OK)
   {
     const std::string why = g_lastError;  // (the frees below must not disturb the message)
@@ -782,6 +801,9 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
     HIP_TRY(hipMemcpy(pt->geometry.ptr, staging.data(), staging.size(), hipMemcpyHostToDevice));
   }
   HIP_TRY(pt->prims.upload(devPrims.data(), devPrims.size()));
+  pt->hostPrims = devPrims;
+  for(int i = 0; i < sd->numRenderPrimitives; ++i)
+    pt->primVertices.push_back(sd->renderPrimitives[i].vertexCount);
   phase("tables + geometry upload");
 
   // ---- what the acceleration structure is built from (see buildAcceleration) ------------------------------------------------
@@ -972,6 +994,219 @@ int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights)
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still sample the old table
   HIP_TRY(hipMemcpy(pt->lights.ptr, lights, sizeof(MiGltfLight) * size_t(numLights), hipMemcpyHostToDevice));
+  return MI_PT_OK;
+}
+
+static void releaseDeformation(MiPt* pt)
+{
+  pt->deformPool.release();
+  pt->deformTasks.release();
+  pt->deformBlockTask.release();
+  pt->deformJoints.release();
+  pt->deformWeights.release();
+  pt->deformJointCount = pt->deformWeightCount = 0;
+  pt->deformBlocks = 0;
+  pt->deformSet    = false;
+}
+
+int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_deformation: null instance");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(!desc)
+  {
+    releaseDeformation(pt);
+    return MI_PT_OK;
+  }
+  const int numPrims = int(pt->primVertices.size());
+  if(desc->numPrims < 0 || desc->numJointMatrices < 0 || desc->numMorphWeights < 0 || (desc->numPrims > 0 && !desc->prims))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_deformation: negative count or null primitive table");
+  // ---- validation: the kernel indexes everything below without further checks
+  std::vector<uint8_t> seen(size_t(numPrims), 0);
+  size_t               poolBytes = 0;
+  uint64_t             blocks    = 0;
+  for(int k = 0; k < desc->numPrims; ++k)
+  {
+    const MiPtDeformPrimitive& d   = desc->prims[k];
+    const std::string          who = "mi_pt_set_deformation: primitive " + std::to_string(k) + ": ";
+    if(d.renderPrimID < 0 || d.renderPrimID >= numPrims)
+      return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " out of range");
+    if(seen[size_t(d.renderPrimID)]++)
+      return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " listed twice");
+    const pt::DevPrim& rp = pt->hostPrims[size_t(d.renderPrimID)];
+    if(d.vertexCount != pt->primVertices[size_t(d.renderPrimID)])
+      return fail(MI_PT_ERR_ARGUMENT, who + "vertexCount differs from the resident primitive's");
+    if(!d.basePositions || !rp.positions)
+      return fail(MI_PT_ERR_ARGUMENT, who + "no base positions");
+    if((d.baseNormals && !rp.normals) || (d.baseTangents && !rp.tangents))
+      return fail(MI_PT_ERR_ARGUMENT, who + "a base stream the resident primitive does not have");
+    if(!d.joints != !d.weights)
+      return fail(MI_PT_ERR_ARGUMENT, who + "joints and weights go together");
+    if(d.joints && uint64_t(d.jointMatrixOffset) + d.numJoints > uint64_t(desc->numJointMatrices))
+      return fail(MI_PT_ERR_ARGUMENT, who + "joint matrices beyond the table");
+    if(d.numTargets > 0 && (!d.positionDeltas || uint64_t(d.morphWeightOffset) + d.numTargets > uint64_t(desc->numMorphWeights)))
+      return fail(MI_PT_ERR_ARGUMENT, who + "morph targets without position deltas, or weights beyond the table");
+    if((d.normalDeltas && !d.baseNormals) || (d.tangentDeltas && !d.baseTangents))
+      return fail(MI_PT_ERR_ARGUMENT, who + "normal / tangent deltas need the base stream");
+    if(!d.joints && d.numTargets == 0)
+      return fail(MI_PT_ERR_ARGUMENT, who + "neither skinned nor morphed");
+    const size_t nv = d.vertexCount;
+    poolBytes += align16(nv * 48);
+    if(d.joints)
+      poolBytes += align16(nv * 8) + align16(nv * 16);
+    const size_t deltaBytes = nv * 12 * d.numTargets;
+    poolBytes += d.numTargets ? align16(deltaBytes) * (1 + (d.normalDeltas ? 1 : 0) + (d.tangentDeltas ? 1 : 0)) : 0;
+    blocks += (nv + pt::DEFORM_BLOCK - 1) / pt::DEFORM_BLOCK;
+  }
+  if(blocks > 0x7fffffffull)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_deformation: too many vertices");
+  releaseDeformation(pt);
+  if(desc->numPrims == 0)
+    return MI_PT_OK;
+  // ---- static upload: base poses (in the layout of DevPrim::verts, from the resident record: uv0 and the stream values that are not
+  // deformed keep theirs), influences, deltas
+  HIP_TRY(pt->deformPool.alloc(std::max<size_t>(poolBytes, 16)));
+  std::vector<uint8_t>        staging(std::max<size_t>(poolBytes, 16), 0);
+  std::vector<pt::DeformTask> tasks(size_t(desc->numPrims));
+  std::vector<uint32_t>       blockTask;
+  size_t                      off = 0;
+  auto                        put = [&](const void* src, size_t bytes) -> const uint8_t* {
+    memcpy(staging.data() + off, src, bytes);
+    const uint8_t* d = pt->deformPool.ptr + off;
+    off += align16(bytes);
+    return d;
+  };
+  HIP_TRY(pt->deformJoints.alloc(size_t(std::max(desc->numJointMatrices, 1)) * 6));
+  HIP_TRY(pt->deformWeights.alloc(size_t(std::max(desc->numMorphWeights, 1))));
+  for(int k = 0; k < desc->numPrims; ++k)
+  {
+    const MiPtDeformPrimitive& d  = desc->prims[k];
+    const pt::DevPrim&         rp = pt->hostPrims[size_t(d.renderPrimID)];
+    const size_t               nv = d.vertexCount;
+    std::vector<float>         base(nv * 12);
+    HIP_TRY(hipMemcpy(base.data(), rp.verts, nv * 48, hipMemcpyDeviceToHost));
+    for(size_t v = 0; v < nv; ++v)
+    {
+      float* o = &base[v * 12];
+      memcpy(o, d.basePositions + v * 3, 12);
+      if(d.baseNormals) { o[3] = d.baseNormals[v * 3]; o[4] = d.baseNormals[v * 3 + 1]; o[5] = d.baseNormals[v * 3 + 2]; }
+      if(d.baseTangents) memcpy(o + 8, d.baseTangents + v * 4, 16);
+    }
+    pt::DeformTask& t = tasks[size_t(k)];
+    memset(&t, 0, sizeof(t));
+    t.base = reinterpret_cast<const float4*>(put(base.data(), nv * 48));
+    if(d.joints)
+    {
+      t.joints  = reinterpret_cast<const uint2*>(put(d.joints, nv * 8));
+      t.weights = reinterpret_cast<const float4*>(put(d.weights, nv * 16));
+      t.flags |= pt::DF_SKIN;
+      t.numJoints  = d.numJoints;
+      t.jointTable = pt->deformJoints.ptr + size_t(d.jointMatrixOffset) * 6;
+    }
+    if(d.numTargets)
+    {
+      t.numTargets   = d.numTargets;
+      t.morphWeights = pt->deformWeights.ptr + d.morphWeightOffset;
+      t.posDeltas    = reinterpret_cast<const float*>(put(d.positionDeltas, nv * 12 * d.numTargets));
+      if(d.normalDeltas)
+      {
+        t.nrmDeltas = reinterpret_cast<const float*>(put(d.normalDeltas, nv * 12 * d.numTargets));
+        t.flags |= pt::DF_MORPH_N;
+      }
+      if(d.tangentDeltas)
+      {
+        t.tanDeltas = reinterpret_cast<const float*>(put(d.tangentDeltas, nv * 12 * d.numTargets));
+        t.flags |= pt::DF_MORPH_T;
+      }
+    }
+    if(d.baseNormals)
+      t.flags |= pt::DF_NORMALS;
+    if(d.baseTangents)
+      t.flags |= pt::DF_TANGENTS;
+    t.outPositions = const_cast<float*>(rp.positions);
+    t.outNormals   = const_cast<float*>(rp.normals);
+    t.outTangents  = const_cast<float*>(rp.tangents);
+    t.outVerts     = const_cast<float4*>(rp.verts);
+    t.vertexCount  = uint32_t(nv);
+    t.firstBlock   = uint32_t(blockTask.size());
+    for(size_t b = 0; b < (nv + pt::DEFORM_BLOCK - 1) / pt::DEFORM_BLOCK; ++b)
+      blockTask.push_back(uint32_t(k));
+  }
+  HIP_TRY(hipMemcpy(pt->deformPool.ptr, staging.data(), staging.size(), hipMemcpyHostToDevice));
+  HIP_TRY(pt->deformTasks.upload(tasks.data(), tasks.size()));
+  HIP_TRY(pt->deformBlockTask.upload(blockTask.data(), blockTask.size()));
+  pt->deformJointCount  = desc->numJointMatrices;
+  pt->deformWeightCount = desc->numMorphWeights;
+  pt->deformBlocks      = uint32_t(blockTask.size());
+  pt->deformSet         = true;
+  return MI_PT_OK;
+}
+
+int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* morphWeights, int flags)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: null instance");
+  if(!pt->deformSet)
+    return fail(MI_PT_ERR_STATE, "mi_pt_update_deformation: no deformation set (mi_pt_set_deformation)");
+  if((pt->deformJointCount > 0 && !jointMatrices) || (pt->deformWeightCount > 0 && !morphWeights))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: null table");
+  for(size_t i = 0, n = size_t(pt->deformJointCount) * 16; i < n; ++i)
+    if(!std::isfinite(jointMatrices[i]))
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: non-finite joint matrix");
+  for(int i = 0; i < pt->deformWeightCount; ++i)
+    if(!std::isfinite(morphWeights[i]))
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: non-finite morph weight");
+  // joint table: rows 0-2 of J (the last row of J [p, 1] is never read) and of N = transpose(inverse(mat3(J))), the cofactor matrix / det
+  std::vector<float4> table(size_t(std::max(pt->deformJointCount, 1)) * 6, make_float4(0, 0, 0, 0));
+  for(int j = 0; j < pt->deformJointCount; ++j)
+  {
+    const float* M = jointMatrices + size_t(j) * 16;  // column-major: M[c * 4 + r]
+    float4*      o = &table[size_t(j) * 6];
+    for(int r = 0; r < 3; ++r)
+      o[r] = make_float4(M[r], M[4 + r], M[8 + r], M[12 + r]);
+    const float a = M[0], b = M[4], c = M[8], e = M[1], f = M[5], g = M[9], h = M[2], i = M[6], k = M[10];
+    const float det = a * (f * k - g * i) - b * (e * k - g * h) + c * (e * i - f * h);
+    const float id  = 1.0f / det;
+    o[3] = make_float4((f * k - g * i) * id, -(e * k - g * h) * id, (e * i - f * h) * id, 0.0f);
+    o[4] = make_float4(-(b * k - c * i) * id, (a * k - c * h) * id, -(a * i - b * h) * id, 0.0f);
+    o[5] = make_float4((b * g - c * f) * id, -(a * g - c * e) * id, (a * f - b * e) * id, 0.0f);
+  }
+  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old pose
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipMemcpy(pt->deformJoints.ptr, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
+  if(pt->deformWeightCount > 0)
+    HIP_TRY(hipMemcpy(pt->deformWeights.ptr, morphWeights, sizeof(float) * size_t(pt->deformWeightCount), hipMemcpyHostToDevice));
+  pt::launchDeform(pt->deformTasks.ptr, pt->deformBlockTask.ptr, pt->deformBlocks, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  if(buildTiming)
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "deform", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  if(flags & MI_PT_DEFORM_DEFER_BUILD)
+    return MI_PT_OK;
+  return buildAcceleration(pt);
+}
+
+int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* normals, float* tangents)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || renderPrimID < 0 || renderPrimID >= int(pt->hostPrims.size()))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_vertices: no such render primitive");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const pt::DevPrim& p  = pt->hostPrims[size_t(renderPrimID)];
+  const size_t       nv = pt->primVertices[size_t(renderPrimID)];
+  if(positions && p.positions && nv)
+    HIP_TRY(hipMemcpy(positions, p.positions, nv * 12, hipMemcpyDeviceToHost));
+  if(normals && p.normals && nv)
+    HIP_TRY(hipMemcpy(normals, p.normals, nv * 12, hipMemcpyDeviceToHost));
+  if(tangents && p.tangents && nv)
+    HIP_TRY(hipMemcpy(tangents, p.tangents, nv * 16, hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
 
@@ -1649,7 +1884,8 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   const pt::DevScene& sc = pt->scene;
   uint64_t scene = bytes(pt->materials) + bytes(pt->texInfos) + bytes(pt->nodes) + bytes(pt->prims) + bytes(pt->lights) + bytes(pt->textures) + bytes(pt->texels) + bytes(pt->texQuads)
                    + bytes(pt->geometry) + bytes(pt->instFlags) + bytes(pt->srgbLut) + bytes(pt->envPixels) + bytes(pt->envAccel) + bytes(pt->alphaTris)
-                   + bytes(pt->shadeTris) + bytes(pt->texRefs) + bytes(pt->coreTex) + bytes(pt->bvh8Planes);
+                   + bytes(pt->shadeTris) + bytes(pt->texRefs) + bytes(pt->coreTex) + bytes(pt->bvh8Planes) + bytes(pt->deformPool) + bytes(pt->deformTasks)
+                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights);
   // the acceleration structure is raw allocations: 64-B BVH2 nodes or 80-B BVH8 nodes + 48-B triangle records
   scene += uint64_t(pt->staticStats.bvhNodeCount) * pt->staticStats.bvhNodeBytes + uint64_t(sc.numTris) * sizeof(pt::DevTri);
   const uint64_t pathState = bytes(pt->pathArrays) + bytes(pt->optThroughput) + bytes(pt->optMisc) + bytes(pt->optMedium) + bytes(pt->optPixelSum) + bytes(pt->optGuides)

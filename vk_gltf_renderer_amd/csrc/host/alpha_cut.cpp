@@ -98,6 +98,10 @@ uint64_t GltfScene::cutAlphaMasked(int subdivisions)
     const int m = std::max(0, rn.materialID);
     pm = (pm == -1 || pm == m) ? m : -2;
   }
+  // skinned and morphed primitives stay whole: skinning does not commute with the barycentric re-interpolation of the cut's new
+  // vertices, and their influences / deltas are per original vertex
+  for(const DeformPrim& dp : m_deform)
+    primMaterial[size_t(dp.renderPrimID)] = -2;
   std::map<std::pair<int, int>, PassTable> tables, failTables;  // (texture, threshold byte)
   uint64_t removed = 0;
   for(size_t p = 0; p < m_primData.size(); ++p)

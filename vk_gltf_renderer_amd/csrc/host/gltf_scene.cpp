@@ -366,8 +366,8 @@ void createSimpleTangents(RenderPrimitiveData& d)
 // to the vertex normal (|t . n| < 0.9) with the handedness flipped for this renderer's bitangent convention, else the fast tangent
 // of the normal (:169-187); corners of a vertex whose tangents are compatible (within ~11 degrees, same handedness, or one of them
 // degenerate: :194-218) share the vertex, the others get copies of it (:353-399), in corner order.  Returns the number of
-// vertices added.
-uint32_t recomputeTangentsMikk(RenderPrimitiveData& d)
+// vertices added; `copyOf` receives the source vertex of every added one.
+uint32_t recomputeTangentsMikk(RenderPrimitiveData& d, std::vector<uint32_t>& copyOf)
 {
   if(d.positions.empty() || d.normals.empty() || d.texCoords0.empty() || d.indices.size() < 3)
     return 0;
@@ -412,7 +412,7 @@ uint32_t recomputeTangentsMikk(RenderPrimitiveData& d)
   // vertex v keeps the tangent of its first corner; every later corner joins the first group (the vertex itself, then its copies in
   // creation order) whose tangent it is compatible with, or founds a new copy
   d.tangents.assign(nv * 4, 0.0f);
-  std::vector<uint32_t> copyOf;  // original vertex of every added vertex
+  copyOf.clear();  // original vertex of every added vertex
   std::vector<float>    copyTangent;
   for(size_t v = 0; v < nv; ++v)
   {
@@ -475,17 +475,57 @@ uint32_t GltfScene::recomputeTangents(bool forceCreation, bool mikktspace)
   // reference: recomputeTangents / collectPrimitivesForTangents (src/gltf_create_tangent.cpp:619-677): primitives with positions,
   // normals and TEXCOORD_0; those without a TANGENT stream only when creation is forced
   uint32_t added = 0;
-  for(RenderPrimitiveData& d : m_primData)
+  // deforming primitives: tangents of the rest pose, and every added vertex inherits its source's influences and deltas
+  std::vector<int> deformOf(m_primData.size(), -1);
+  for(size_t k = 0; k < m_deform.size(); ++k)
   {
+    const DeformPrim&    dp = m_deform[k];
+    RenderPrimitiveData& d  = m_primData[size_t(dp.renderPrimID)];
+    deformOf[size_t(dp.renderPrimID)] = int(k);
+    d.positions = dp.basePos;
+    if(!dp.baseNrm.empty())
+      d.normals = dp.baseNrm;
+    if(!dp.baseTan.empty())
+      d.tangents = dp.baseTan;
+  }
+  std::vector<uint32_t> copyOf;
+  for(size_t p = 0; p < m_primData.size(); ++p)
+  {
+    RenderPrimitiveData& d = m_primData[p];
     if(d.positions.empty() || d.normals.empty() || d.texCoords0.empty())
       continue;
     if(d.tangents.empty() && !forceCreation)
       continue;
     if(mikktspace)
-      added += recomputeTangentsMikk(d);
+    {
+      const uint32_t nv = d.vertexCount;
+      added += recomputeTangentsMikk(d, copyOf);
+      if(deformOf[p] >= 0 && d.vertexCount != nv)
+      {
+        DeformPrim& dp   = m_deform[size_t(deformOf[p])];
+        auto        grow = [&](auto& v, size_t width, size_t blocks) {  // blocks: per-target arrays [t][v]
+          if(v.empty())
+            return;
+          std::remove_reference_t<decltype(v)> out(size_t(d.vertexCount) * width * blocks);
+          for(size_t b = 0; b < blocks; ++b)
+          {
+            std::copy(v.begin() + long(b * nv * width), v.begin() + long((b + 1) * nv * width), out.begin() + long(b * d.vertexCount * width));
+            for(size_t c = 0; c < copyOf.size(); ++c)
+              std::copy_n(v.begin() + long((b * nv + copyOf[c]) * width), width, out.begin() + long((b * d.vertexCount + nv + c) * width));
+          }
+          v.swap(out);
+        };
+        grow(dp.joints, 4, 1);
+        grow(dp.weights, 4, 1);
+        grow(dp.posDeltas, 3, dp.numTargets);
+        grow(dp.nrmDeltas, 3, dp.numTargets);
+        grow(dp.tanDeltas, 3, dp.numTargets);
+      }
+    }
     else
       createSimpleTangents(d);
   }
+  finalizeDeformation();  // new base copies (the tangents changed, the vertex counts may have)
   finalizeDesc();  // the streams may have been reallocated
   return added;
 }
@@ -1133,6 +1173,7 @@ void GltfScene::buildPrimitives(std::map<std::string, int>& primMap)  // referen
       primMap[key] = int(m_primData.size());
       RenderPrimitiveData d;
       d.meshID            = int(i);
+      d.meshPrimitive     = int(j);
       const Value& attrs  = prim["attributes"];
       int          posAcc = getInt(attrs, "POSITION", -1);
       if(posAcc >= 0)
@@ -1475,6 +1516,7 @@ bool GltfScene::parse(const std::string& baseDir)  // reference: src/gltf_scene.
     traverse(r, mx::identity(), true, primMap);
   m_roots = roots;
   parseAnimations();
+  parseDeformation();
 
   // scene bounds over visible render nodes (reference: src/gltf_scene.cpp:2303-2336)
   bool  any     = false;

@@ -4,8 +4,8 @@
 // :2269-2300 lights, :2338-2429 render nodes + EXT_mesh_gpu_instancing, :1561-1594 default camera;
 // src/gltf_material_cache.cpp:103-260; src/gltf_scene_vk.cpp:493-501, :741-870, :909-947, :1102-1154, :1354-1392).
 // Keyframe animation of node transforms (gltf_scene_animation.cpp here; reference: src/gltf_scene_animation.cpp:355-700) feeds
-// mi_pt_update_render_nodes / mi_pt_update_lights.  Editing, saving, merging, skinning, morph targets, KHR_animation_pointer
-// and the variants UI are out of scope.
+// mi_pt_update_render_nodes / mi_pt_update_lights; skins and morph targets (same file; reference: src/gltf_scene_animation.cpp:196-320)
+// feed mi_pt_update_deformation.  Editing, saving, merging, KHR_animation_pointer and the variants UI are out of scope.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -33,7 +33,7 @@ struct RenderPrimitiveData
   std::vector<uint32_t> indices;
   std::vector<float>    positions, normals, tangents, texCoords0, texCoords1;
   std::vector<uint32_t> colors;
-  int                   meshID = -1;
+  int                   meshID = -1, meshPrimitive = -1;  // the glTF mesh and the index of the primitive in it
   uint32_t              vertexCount = 0;
   uint32_t              opaqueTriangles = 0;  // triangles [0, n) cannot fail their material's alpha test (cutAlphaMasked)
 };
@@ -84,6 +84,10 @@ public:
   int            numAnimations() const { return int(m_animations.size()); }
   AnimationInfo& animationInfo(int index) { return m_animations[size_t(index)].info; }
   bool           updateAnimation(int index);
+  // Skins and morph targets (see mi_host.h: mi_scene_deformation).  deformation() is NULL when nothing deforms; deformOnHost writes the
+  // posed vertices of the current frame tables into renderPrimitives() and returns the number of primitives deformed.
+  const MiPtDeformDesc* deformation() const { return m_deform.empty() ? nullptr : &m_deformDesc; }
+  int                   deformOnHost();
   const std::vector<uint8_t>& renderNodeVisible() const { return m_renderNodeVisible; }
   // Load-time bake for alpha-MASK geometry (alpha_cut.cpp; the counterpart of the reference's opacity micro-map bake,
   // src/gltf_scene_omm.cpp): triangles are cut into subdivisions x subdivisions sub-triangles and those on which the alpha test
@@ -111,6 +115,10 @@ private:
   uint16_t addTextureInfo(const mijson::Value& texInfo);
   mx::mat4 localMatrix(int nodeID) const;
   void     parseAnimations();
+  void     parseDeformation();
+  void     finalizeDeformation();  // (re)takes the base copies from the streams and rebuilds m_deformDesc
+  void     updateDeformTables();
+  std::vector<mx::mat4> nodeWorldMatrices() const;
   void     placeLight(MiGltfLight& info, const mx::mat4& world) const;
 
   struct AnimationSampler
@@ -121,8 +129,9 @@ private:
   };
   struct AnimationChannel
   {
-    enum Path { eTranslation, eRotation, eScale } path = eTranslation;
+    enum Path { eTranslation, eRotation, eScale, eWeights } path = eTranslation;
     int node = -1, sampler = 0;
+    int numWeights = 0;  // eWeights: values per keyframe (the morph targets the channel drives)
   };
   struct Animation
   {
@@ -150,6 +159,31 @@ private:
   AlphaCutStats                 m_alphaCutStats;
   bool                          m_alphaCutDone = false;
   std::vector<uint8_t>          m_onPath;  // nodes on the current traversal path (cycle guard)
+
+  // skins and morph targets: one entry per unique deforming render primitive (reference: SkinTask + MorphResult)
+  struct DeformPrim
+  {
+    int                   renderPrimID = -1, meshID = -1;
+    int                   skin = -1, refNode = -1;     // skinned: the skin and the node of the first render node that uses the primitive
+    std::vector<uint16_t> joints;                      // 4 per vertex (JOINTS_0)
+    std::vector<float>    weights;                     // 4 per vertex (WEIGHTS_0)
+    uint32_t              numTargets = 0;              // morphed: targets (the mesh has a non-empty `weights` array)
+    std::vector<float>    posDeltas, nrmDeltas, tanDeltas;  // 3 floats per vertex and target, target-major
+    bool                  morphNormals = false, morphTangents = false;  // some target carries NORMAL / TANGENT deltas
+    std::vector<float>    basePos, baseNrm, baseTan;   // the rest pose the frames are evaluated from
+    uint32_t              jointOffset = 0, weightOffset = 0;
+  };
+  struct Skin
+  {
+    std::vector<int>      joints;
+    std::vector<mx::mat4> inverseBind;
+  };
+  std::vector<Skin>                m_skins;
+  std::vector<DeformPrim>          m_deform;
+  std::vector<MiPtDeformPrimitive> m_deformPrims;
+  MiPtDeformDesc                   m_deformDesc{};
+  std::vector<float>               m_jointMatrices, m_morphWeights;  // the frame tables (stable pointers)
+  std::vector<std::vector<float>>  m_meshWeights;                    // current mesh.weights, per mesh
 
   mijson::Value                      m_doc;
   bool decompressMeshopt();  // EXT / KHR_meshopt_compression buffer views -> their fallback regions (meshopt_decoder.hpp)

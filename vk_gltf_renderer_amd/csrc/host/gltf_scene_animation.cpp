@@ -1,16 +1,21 @@
-// Keyframe animation of node transforms: glTF 2.0 `animations` with translation / rotation / scale channels and LINEAR, STEP
-// and CUBICSPLINE samplers (glTF 2.0 specification, section 3.11 and appendix C), evaluated into per-node poses, from which
-// the world matrices, the render-node table and the light placements are recomputed in place.  Behaviour follows the
-// reference's AnimationSystem (src/gltf_scene_animation.cpp:84-175 parse, :355-478 update / segment search, :484-700
+// Keyframe animation: glTF 2.0 `animations` with translation / rotation / scale / weights channels and LINEAR, STEP and CUBICSPLINE
+// samplers (glTF 2.0 specification, section 3.11 and appendix C), evaluated into per-node poses and per-mesh morph weights, from which
+// the world matrices, the render-node table, the light placements and the deformation tables are recomputed in place.  Behaviour
+// follows the reference's AnimationSystem (src/gltf_scene_animation.cpp:84-175 parse, :355-478 update / segment search, :484-700
 // interpolation): a sampler needs two keyframes, a channel is applied only while the time lies inside its keyframe range, the
-// clip's [start, end] is the hull of all sampler inputs, rotations are slerped (LINEAR) or spline-evaluated and normalised.
-// Morph-target weights, skins and KHR_animation_pointer channels are skipped: they change vertex data or material tables, which
-// is outside the instance-update boundary (mi_pt_update_render_nodes).
+// clip's [start, end] is the hull of all sampler inputs, rotations are slerped (LINEAR) or spline-evaluated and normalised.  Weights
+// channels are evaluated with all three samplers as the specification defines them (a CUBICSPLINE key holds in-tangents, values and
+// out-tangents of every target); the reference interpolates LINEAR ones only.
+// Skins and morph targets (parseDeformation, reference: src/gltf_scene_animation.cpp:196-320): the vertex data they change is deformed
+// on the device (mi_pt_update_deformation, csrc/device/deform.hip) from the per-frame tables built here -- joint matrices
+// inverse(world[refNode]) * world[joint] * IBM (reference: src/gltf_scene_animation_vk.cpp:454-478) and the mesh weights -- or on the
+// host by deformOnHost, the CPU restatement of that kernel.  KHR_animation_pointer channels are skipped.
 #include <algorithm>
 #include <cmath>
 #include <map>
 #include <cstring>
 #include <limits>
+#include <set>
 
 #include "gltf_scene.hpp"
 
@@ -89,12 +94,28 @@ void GltfScene::parseAnimations()
         ch.path = AnimationChannel::eRotation;
       else if(path == "scale")
         ch.path = AnimationChannel::eScale;
+      else if(path == "weights")
+        ch.path = AnimationChannel::eWeights;
       else
-        continue;  // weights / pointer
+        continue;  // pointer
       ch.node    = gc["target"]["node"].integer(-1);
       ch.sampler = gc["sampler"].integer(-1);
       if(ch.node < 0 || size_t(ch.node) >= m_nodePose.size() || ch.sampler < 0 || size_t(ch.sampler) >= anim.samplers.size())
         continue;
+      if(ch.path == AnimationChannel::eWeights)
+      {
+        // the node's mesh takes the weights (node.weights is not evaluated, as in the reference); a key holds one value per target
+        // (x3 for CUBICSPLINE), so the target count is what the output accessor holds per key
+        const int               mesh = m_doc["nodes"][size_t(ch.node)]["mesh"].integer(-1);
+        const AnimationSampler& sm   = anim.samplers[size_t(ch.sampler)];
+        const size_t            keys = sm.inputs.size() * (sm.interpolation == AnimationSampler::eCubicSpline ? 3 : 1);
+        if(mesh < 0 || size_t(mesh) >= m_doc["meshes"].size() || sm.components != 1 || keys == 0 || sm.outputs.size() % keys != 0
+           || sm.outputs.empty())
+          continue;
+        ch.numWeights = int(sm.outputs.size() / keys);
+        anim.channels.push_back(ch);
+        continue;
+      }
       const int need = ch.path == AnimationChannel::eRotation ? 4 : 3;
       if(anim.samplers[size_t(ch.sampler)].components != need)
         continue;
@@ -146,7 +167,7 @@ bool GltfScene::updateAnimation(int index)
     return false;
   const Animation& anim = m_animations[size_t(index)];
   const float      time = anim.info.currentTime;
-  bool             any  = false;
+  bool             any  = false, anyWeights = false;
 
   for(const AnimationChannel& ch : anim.channels)
   {
@@ -166,9 +187,12 @@ bool GltfScene::updateAnimation(int index)
       continue;
     const float keyDelta = t1 - t0;
     const float t        = std::fabs(keyDelta) < std::numeric_limits<float>::epsilon() ? 0.0f : std::min(std::max((time - t0) / keyDelta, 0.0f), 1.0f);
-    const int   nc       = sm.components;
+    const bool  weights  = ch.path == AnimationChannel::eWeights;
+    const int   nc       = weights ? ch.numWeights : sm.components;
     const size_t numOut  = sm.outputs.size() / size_t(nc);
-    float       v[4]     = {0, 0, 0, 1};
+    std::vector<float> vbuf(size_t(std::max(nc, 4)), 0.0f);
+    float*      v        = vbuf.data();
+    v[3]                 = weights ? v[3] : 1.0f;
     bool        have     = false;
     switch(sm.interpolation)
     {
@@ -206,8 +230,8 @@ bool GltfScene::updateAnimation(int index)
           {
             const float len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
             if(len > 0.0f)
-              for(float& c : v)
-                c /= len;
+              for(int c = 0; c < 4; ++c)
+                v[c] /= len;
           }
           have = true;
         }
@@ -215,6 +239,13 @@ bool GltfScene::updateAnimation(int index)
     }
     if(!have)
       continue;
+    if(weights)
+    {
+      std::vector<float>& mw = m_meshWeights[size_t(m_doc["nodes"][size_t(ch.node)]["mesh"].integer(-1))];
+      mw.assign(v, v + nc);  // (the reference resizes mesh.weights to the channel's count as well)
+      anyWeights = true;
+      continue;
+    }
     NodePose& pose = m_nodePose[size_t(ch.node)];
     if(!pose.animated)
     {
@@ -236,7 +267,11 @@ bool GltfScene::updateAnimation(int index)
     any = true;
   }
   if(!any)
-    return false;
+  {
+    if(anyWeights)
+      updateDeformTables();
+    return anyWeights;
+  }
 
   // World matrices (reference: Scene::updateNodeWorldMatrices), per PATH from a scene root: glTF hierarchies are strict trees, but
   // load-time traversal instantiates a node of a non-conforming file under every parent it is listed by -- each such render node
@@ -265,7 +300,348 @@ bool GltfScene::updateAnimation(int index)
   }
   for(size_t l = 0; l < m_lights.size(); ++l)
     placeLight(m_lights[l], worldOf(m_lightPath[l]));
+  updateDeformTables();
   return true;
+}
+
+//----------------------------------------------------------------------------------------------------------------------
+// Skins and morph targets
+//----------------------------------------------------------------------------------------------------------------------
+
+// World matrix of every node from the current poses, along the first path from a scene root that reaches it (a node outside the
+// scene hierarchy keeps its local matrix).
+std::vector<mx::mat4> GltfScene::nodeWorldMatrices() const
+{
+  const size_t          n = m_doc["nodes"].size();
+  std::vector<mx::mat4> world(n);
+  std::vector<uint8_t>  done(n, 0);
+  for(size_t i = 0; i < n; ++i)
+    world[i] = localMatrix(int(i));
+  std::vector<std::pair<int, mx::mat4>> stack;
+  for(int r : m_roots)
+    if(r >= 0 && size_t(r) < n && !done[size_t(r)])
+      stack.push_back({r, mx::identity()});
+  while(!stack.empty())
+  {
+    auto [node, parent] = stack.back();
+    stack.pop_back();
+    if(done[size_t(node)])
+      continue;
+    done[size_t(node)]  = 1;
+    world[size_t(node)] = mx::mul(parent, localMatrix(node));
+    const Value& children = m_doc["nodes"][size_t(node)]["children"];
+    for(size_t c = children.size(); c-- > 0;)
+    {
+      const int child = children[c].integer(-1);
+      if(child >= 0 && size_t(child) < n && !done[size_t(child)])
+        stack.push_back({child, world[size_t(node)]});
+    }
+  }
+  return world;
+}
+
+// reference: AnimationSystem::parseSkinTasks / parseMorphPrimitives (src/gltf_scene_animation.cpp:196-320)
+void GltfScene::parseDeformation()
+{
+  m_skins.clear();
+  m_deform.clear();
+  m_meshWeights.clear();
+  const Value& meshes = m_doc["meshes"];
+  for(size_t m = 0; m < meshes.size(); ++m)
+  {
+    std::vector<float> w;
+    const Value&       mw = meshes[m]["weights"];
+    for(size_t t = 0; t < mw.size(); ++t)
+      w.push_back(float(mw[t].number()));
+    m_meshWeights.push_back(std::move(w));
+  }
+  const Value& skins = m_doc["skins"];
+  for(size_t k = 0; k < skins.size(); ++k)
+  {
+    Skin         sk;
+    const Value& joints = skins[k]["joints"];
+    for(size_t j = 0; j < joints.size(); ++j)
+      sk.joints.push_back(joints[j].integer(-1));
+    // a missing, unreadable or short inverseBindMatrices list leaves the remaining joints at identity (as the reference does)
+    std::vector<float> ibm;
+    if(skins[k]["inverseBindMatrices"].isNumber() && readAccessorFloats(skins[k]["inverseBindMatrices"].integer(-1), 16, ibm))
+      for(size_t j = 0; j + 1 <= ibm.size() / 16 && j < sk.joints.size(); ++j)
+      {
+        mx::mat4 M;
+        memcpy(M.m, &ibm[j * 16], sizeof(M.m));
+        sk.inverseBind.push_back(M);
+      }
+    m_skins.push_back(std::move(sk));
+  }
+
+  std::vector<int> deformOf(m_primData.size(), -1);
+  auto             entry = [&](int rp) -> DeformPrim& {
+    if(deformOf[size_t(rp)] < 0)
+    {
+      deformOf[size_t(rp)] = int(m_deform.size());
+      DeformPrim dp;
+      dp.renderPrimID = rp;
+      dp.meshID       = m_primData[size_t(rp)].meshID;
+      m_deform.push_back(std::move(dp));
+    }
+    return m_deform[size_t(deformOf[size_t(rp)])];
+  };
+  auto primJson = [&](int rp) -> const Value& {
+    const RenderPrimitiveData& d = m_primData[size_t(rp)];
+    return meshes[size_t(std::max(d.meshID, 0))]["primitives"][size_t(std::max(d.meshPrimitive, 0))];
+  };
+  // morph targets: the primitive has targets AND its mesh a non-empty `weights` array (reference :211 -- a file that animates the weights
+  // of a mesh without default weights is not morphed, a quirk kept for parity)
+  for(size_t rp = 0; rp < m_primData.size(); ++rp)
+  {
+    const RenderPrimitiveData& d = m_primData[rp];
+    if(d.meshID < 0 || d.vertexCount == 0 || d.positions.empty())
+      continue;
+    const Value& targets = primJson(int(rp))["targets"];
+    if(targets.size() == 0 || m_meshWeights[size_t(d.meshID)].empty())
+      continue;
+    DeformPrim&    dp = entry(int(rp));
+    const uint32_t nt = uint32_t(targets.size()), nv = d.vertexCount;
+    dp.numTargets     = nt;
+    for(size_t t = 0; t < nt; ++t)
+    {
+      dp.morphNormals  = dp.morphNormals || targets[t].has("NORMAL");
+      dp.morphTangents = dp.morphTangents || targets[t].has("TANGENT");
+    }
+    dp.morphNormals  = dp.morphNormals && !d.normals.empty();  // deltas of a stream the primitive does not have are ignored
+    dp.morphTangents = dp.morphTangents && !d.tangents.empty();
+    auto readDeltas  = [&](const char* attr, std::vector<float>& out) {
+      out.assign(size_t(nv) * 3 * nt, 0.0f);
+      for(size_t t = 0; t < nt; ++t)
+      {
+        std::vector<float> a;
+        // a missing, unreadable or short accessor contributes nothing (sparse accessors decode in readAccessorFloats)
+        if(targets[t][attr].isNumber() && readAccessorFloats(targets[t][attr].integer(-1), 3, a) && a.size() == size_t(nv) * 3)
+          for(size_t i = 0; i < a.size(); ++i)
+            out[t * size_t(nv) * 3 + i] = std::isfinite(a[i]) ? a[i] : 0.0f;
+      }
+    };
+    readDeltas("POSITION", dp.posDeltas);
+    if(dp.morphNormals)
+      readDeltas("NORMAL", dp.nrmDeltas);
+    if(dp.morphTangents)
+      readDeltas("TANGENT", dp.tanDeltas);
+  }
+  // skins: one task per unique skinned render primitive; the first render node that uses it supplies the skin and the reference node
+  // (reference :270-320).  Instances of the primitive share that one deformation.
+  std::set<int> seen;
+  for(size_t n = 0; n < m_renderNodes.size(); ++n)
+  {
+    const int rp   = m_renderNodes[n].renderPrimID;
+    const int node = m_renderNodeSource[n].node;
+    const int skin = m_doc["nodes"][size_t(node)]["skin"].integer(-1);
+    if(skin < 0 || size_t(skin) >= m_skins.size() || rp < 0 || size_t(rp) >= m_primData.size() || !seen.insert(rp).second)
+      continue;
+    const RenderPrimitiveData& d     = m_primData[size_t(rp)];
+    const Value&               attrs = primJson(rp)["attributes"];
+    std::vector<float>         j, w;
+    if(d.vertexCount == 0 || d.positions.empty() || !attrs["JOINTS_0"].isNumber() || !attrs["WEIGHTS_0"].isNumber()
+       || !readAccessorFloats(attrs["JOINTS_0"].integer(-1), 4, j) || !readAccessorFloats(attrs["WEIGHTS_0"].integer(-1), 4, w)
+       || j.size() != size_t(d.vertexCount) * 4 || w.size() != size_t(d.vertexCount) * 4)
+      continue;  // no usable influences: the primitive keeps its bind pose
+    DeformPrim& dp = entry(rp);
+    dp.skin        = skin;
+    dp.refNode     = node;
+    dp.joints.resize(j.size());
+    dp.weights.resize(w.size());
+    for(size_t i = 0; i < j.size(); ++i)
+    {
+      dp.joints[i]  = std::isfinite(j[i]) && j[i] >= 0.0f && j[i] <= 65535.0f ? uint16_t(j[i]) : uint16_t(65535);  // (out of range: skipped)
+      dp.weights[i] = std::isfinite(w[i]) ? w[i] : 0.0f;
+    }
+  }
+  finalizeDeformation();
+}
+
+void GltfScene::finalizeDeformation()
+{
+  uint32_t joints = 0, weights = 0;
+  m_deformPrims.clear();
+  for(DeformPrim& dp : m_deform)
+  {
+    const RenderPrimitiveData& d       = m_primData[size_t(dp.renderPrimID)];
+    const bool                 skinned = dp.skin >= 0;
+    dp.basePos                         = d.positions;
+    dp.baseNrm.clear();
+    dp.baseTan.clear();
+    if(!d.normals.empty() && (skinned || dp.morphNormals))
+      dp.baseNrm = d.normals;
+    if(!d.tangents.empty() && (skinned || dp.morphTangents))
+      dp.baseTan = d.tangents;
+    if(dp.morphTangents && d.tangents.empty())  // (a tangent stream only ever appears, by recomputeTangents; deltas never lose theirs)
+      dp.morphTangents = false;
+    dp.jointOffset  = joints;
+    dp.weightOffset = weights;
+    if(skinned)
+      joints += uint32_t(m_skins[size_t(dp.skin)].joints.size());
+    weights += dp.numTargets;
+    MiPtDeformPrimitive p{};
+    p.renderPrimID      = dp.renderPrimID;
+    p.vertexCount       = d.vertexCount;
+    p.basePositions     = dp.basePos.data();
+    p.baseNormals       = dp.baseNrm.empty() ? nullptr : dp.baseNrm.data();
+    p.baseTangents      = dp.baseTan.empty() ? nullptr : dp.baseTan.data();
+    p.joints            = skinned ? dp.joints.data() : nullptr;
+    p.weights           = skinned ? dp.weights.data() : nullptr;
+    p.numJoints         = skinned ? uint32_t(m_skins[size_t(dp.skin)].joints.size()) : 0;
+    p.jointMatrixOffset = dp.jointOffset;
+    p.numTargets        = dp.numTargets;
+    p.morphWeightOffset = dp.weightOffset;
+    p.positionDeltas    = dp.numTargets ? dp.posDeltas.data() : nullptr;
+    p.normalDeltas      = dp.numTargets && dp.morphNormals ? dp.nrmDeltas.data() : nullptr;
+    p.tangentDeltas     = dp.numTargets && dp.morphTangents && !dp.tanDeltas.empty() ? dp.tanDeltas.data() : nullptr;
+    m_deformPrims.push_back(p);
+  }
+  m_jointMatrices.assign(size_t(joints) * 16, 0.0f);
+  m_morphWeights.assign(weights, 0.0f);
+  m_deformDesc                  = MiPtDeformDesc{};
+  m_deformDesc.prims            = m_deformPrims.data();
+  m_deformDesc.numPrims         = int(m_deformPrims.size());
+  m_deformDesc.numJointMatrices = int(joints);
+  m_deformDesc.numMorphWeights  = int(weights);
+  m_deformDesc.jointMatrices    = m_jointMatrices.data();
+  m_deformDesc.morphWeights     = m_morphWeights.data();
+  updateDeformTables();
+}
+
+// The frame tables, in place: joint matrices inverse(world[refNode]) * world[joint] * IBM (reference: src/gltf_scene_animation_vk.cpp:454-478;
+// a joint that names no node keeps identity) and the morph weights (mesh.weights, zero beyond its length).
+void GltfScene::updateDeformTables()
+{
+  if(m_deform.empty())
+    return;
+  std::vector<mx::mat4> world;
+  for(const DeformPrim& dp : m_deform)
+  {
+    if(dp.skin >= 0)
+    {
+      if(world.empty())
+        world = nodeWorldMatrices();
+      const Skin&    sk     = m_skins[size_t(dp.skin)];
+      const mx::mat4 invRef = mx::inverse(world[size_t(dp.refNode)]);
+      for(size_t j = 0; j < sk.joints.size(); ++j)
+      {
+        mx::mat4 J = mx::identity();
+        if(sk.joints[j] >= 0 && size_t(sk.joints[j]) < world.size())
+          J = mx::mul(mx::mul(invRef, world[size_t(sk.joints[j])]), j < sk.inverseBind.size() ? sk.inverseBind[j] : mx::identity());
+        for(float& c : J.m)
+          c = std::isfinite(c) ? c : 0.0f;  // (a singular reference node: no NaN reaches the device, which would refuse the frame)
+        memcpy(&m_jointMatrices[(size_t(dp.jointOffset) + j) * 16], J.m, sizeof(J.m));
+      }
+    }
+    if(dp.numTargets)
+    {
+      const std::vector<float>& mw = m_meshWeights[size_t(dp.meshID)];
+      for(uint32_t t = 0; t < dp.numTargets; ++t)
+        m_morphWeights[size_t(dp.weightOffset) + t] = t < mw.size() && std::isfinite(mw[t]) ? mw[t] : 0.0f;
+    }
+  }
+}
+
+namespace {
+inline void normalize3(float* v)
+{
+  const float l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  v[0] /= l;
+  v[1] /= l;
+  v[2] /= l;
+}
+}  // namespace
+
+// The CPU restatement of k_deform (csrc/device/deform.hip), with the same rules: morph (zero weights skipped, normal / tangent normalised
+// when deltas moved them), then skin (influences with w > 0 and a joint inside the skin; the rest skipped; no renormalisation).
+int GltfScene::deformOnHost()
+{
+  int count = 0;
+  for(const DeformPrim& dp : m_deform)
+  {
+    RenderPrimitiveData& d   = m_primData[size_t(dp.renderPrimID)];
+    const size_t         nv  = d.vertexCount;
+    const bool           hasN = !dp.baseNrm.empty(), hasT = !dp.baseTan.empty();
+    const float*         J    = m_jointMatrices.data() + size_t(dp.jointOffset) * 16;
+    const uint32_t       nj   = dp.skin >= 0 ? uint32_t(m_skins[size_t(dp.skin)].joints.size()) : 0;
+    // normal matrices transpose(inverse(mat3(J))) (the device computes them the same way, mi_pt_update_deformation)
+    std::vector<float> N(size_t(nj) * 9);
+    for(uint32_t j = 0; j < nj; ++j)
+    {
+      const float* M = J + size_t(j) * 16;  // column-major: M[c * 4 + r]
+      const float  a = M[0], b = M[4], c = M[8], e = M[1], f = M[5], g = M[9], h = M[2], i = M[6], k = M[10];  // rows (a b c) (e f g) (h i k)
+      const float  det = a * (f * k - g * i) - b * (e * k - g * h) + c * (e * i - f * h);
+      const float  id  = 1.0f / det;
+      // cofactor matrix / det == transpose(inverse); stored row-major: N[r * 3 + c]
+      float* o = &N[size_t(j) * 9];
+      o[0] = (f * k - g * i) * id; o[1] = -(e * k - g * h) * id; o[2] = (e * i - f * h) * id;
+      o[3] = -(b * k - c * i) * id; o[4] = (a * k - c * h) * id; o[5] = -(a * i - b * h) * id;
+      o[6] = (b * g - c * f) * id; o[7] = -(a * g - c * e) * id; o[8] = (a * f - b * e) * id;
+    }
+    for(size_t v = 0; v < nv; ++v)
+    {
+      float p[3] = {dp.basePos[v * 3], dp.basePos[v * 3 + 1], dp.basePos[v * 3 + 2]};
+      float n[3] = {0, 0, 0}, t[4] = {0, 0, 0, 0};
+      if(hasN)
+        memcpy(n, &dp.baseNrm[v * 3], sizeof(n));
+      if(hasT)
+        memcpy(t, &dp.baseTan[v * 4], sizeof(t));
+      if(dp.numTargets)
+      {
+        for(uint32_t k = 0; k < dp.numTargets; ++k)
+        {
+          const float w = m_morphWeights[size_t(dp.weightOffset) + k];
+          if(w == 0.0f)
+            continue;
+          const size_t o = (size_t(k) * nv + v) * 3;
+          for(int c = 0; c < 3; ++c)
+            p[c] += w * dp.posDeltas[o + size_t(c)];
+          if(hasN && dp.morphNormals)
+            for(int c = 0; c < 3; ++c)
+              n[c] += w * dp.nrmDeltas[o + size_t(c)];
+          if(hasT && dp.morphTangents)
+            for(int c = 0; c < 3; ++c)
+              t[c] += w * dp.tanDeltas[o + size_t(c)];
+        }
+        if(hasN && dp.morphNormals)
+          normalize3(n);
+        if(hasT && dp.morphTangents)
+          normalize3(t);
+      }
+      if(dp.skin >= 0)
+      {
+        float sp[3] = {0, 0, 0}, sn[3] = {0, 0, 0}, st[3] = {0, 0, 0};
+        for(int i = 0; i < 4; ++i)
+        {
+          const float    w = dp.weights[v * 4 + size_t(i)];
+          const uint32_t j = dp.joints[v * 4 + size_t(i)];
+          if(!(w > 0.0f) || j >= nj)
+            continue;
+          const float* M  = J + size_t(j) * 16;
+          const float* Nm = &N[size_t(j) * 9];
+          for(int r = 0; r < 3; ++r)
+          {
+            sp[r] += w * (M[r] * p[0] + M[4 + r] * p[1] + M[8 + r] * p[2] + M[12 + r]);
+            sn[r] += w * (Nm[r * 3] * n[0] + Nm[r * 3 + 1] * n[1] + Nm[r * 3 + 2] * n[2]);
+            st[r] += w * (M[r] * t[0] + M[4 + r] * t[1] + M[8 + r] * t[2]);
+          }
+        }
+        memcpy(p, sp, sizeof(sp));
+        memcpy(n, sn, sizeof(sn));
+        memcpy(t, st, sizeof(st));
+        normalize3(n);
+        normalize3(t);
+      }
+      memcpy(&d.positions[v * 3], p, sizeof(p));
+      if(hasN)
+        memcpy(&d.normals[v * 3], n, sizeof(n));
+      if(hasT)
+        memcpy(&d.tangents[v * 4], t, 3 * sizeof(float));  // (w kept)
+    }
+    ++count;
+  }
+  return count;
 }
 
 }  // namespace mihost

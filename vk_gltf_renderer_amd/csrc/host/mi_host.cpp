@@ -133,6 +133,19 @@ int mi_scene_update_animation(MiScene* scene, int index, float time)
     return MI_PT_ERR_IO;
   }
 }
+const MiPtDeformDesc* mi_scene_deformation(const MiScene* scene)
+{
+  return scene ? scene->scene.deformation() : nullptr;
+}
+int mi_scene_deform_on_host(MiScene* scene)
+{
+  if(!scene)
+  {
+    g_hostError = "mi_scene_deform_on_host: null scene";
+    return MI_PT_ERR_ARGUMENT;
+  }
+  return scene->scene.deformOnHost();
+}
 int mi_mikktspace(const float* positions, const float* normals, const float* texCoords, uint32_t numVertices, const uint32_t* indices,
                   uint32_t numTriangles, float* cornerTangents)
 {

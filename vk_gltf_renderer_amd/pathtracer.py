@@ -86,6 +86,21 @@ class Scene:
             _check_host(r)
         return bool(r)
 
+    @property
+    def deformation(self):
+        """The skin / morph tables (capi.MiPtDeformDesc, mi_scene_deformation) or None when the scene deforms nothing.  Its frame arrays
+        (joint matrices, morph weights) follow every update_animation in place."""
+        d = self._h.mi_scene_deformation(self._p)
+        return d.contents if d else None
+
+    def deform_on_host(self):
+        """Writes the posed vertices of the current frame into the scene's own render-primitive streams (the CPU restatement of the
+        device kernel), so that a PathTracer created afterwards, or the oracle, sees the pose.  Returns the primitives deformed."""
+        n = self._h.mi_scene_deform_on_host(self._p)
+        if n < 0:
+            _check_host(n)
+        return n
+
     def bounds(self):
         lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
         self._h.mi_scene_bounds(self._p, lo, hi)
@@ -173,9 +188,41 @@ class PathTracer:
         """New placement / colour / cone of the lights (same count as at creation)."""
         _check_pt(self._l.mi_pt_update_lights(self._p, lights, count))
 
+    def set_deformation(self, scene):
+        """Static upload of the scene's skin / morph tables (mi_pt_set_deformation); None, or a scene without deformers, releases them."""
+        d = scene.deformation if scene is not None else None
+        _check_pt(self._l.mi_pt_set_deformation(self._p, C.byref(d) if d is not None else None))
+        self._deforming = d is not None
+
+    def update_deformation(self, joint_matrices, morph_weights, defer_build=False):
+        """Deforms every skinned / morphed primitive on the device from this frame's packed tables (ctypes float pointers or float32 arrays),
+        then rebuilds the acceleration structure unless defer_build (the caller calls update_render_nodes next)."""
+        def keep(a):  # a float32 array that lives across the call, or the ctypes pointer as given
+            return a if a is None or isinstance(a, C._Pointer) else np.ascontiguousarray(a, dtype=np.float32)
+
+        def ptr(a):
+            return a if a is None or isinstance(a, C._Pointer) else a.ctypes.data_as(C.POINTER(C.c_float))
+        jm, mw = keep(joint_matrices), keep(morph_weights)
+        _check_pt(self._l.mi_pt_update_deformation(self._p, ptr(jm), ptr(mw), capi.MI_PT_DEFORM_DEFER_BUILD if defer_build else 0))
+
+    def read_vertices(self, prim):
+        """The resident streams of render primitive `prim`: (positions (V, 3), normals (V, 3) or None, tangents (V, 4) or None)."""
+        p = self._scene.desc.contents.renderPrimitives[prim]
+        n = int(p.vertexCount)
+        pos = np.zeros((n, 3), np.float32)
+        nrm = np.zeros((n, 3), np.float32) if p.normals else None
+        tan = np.zeros((n, 4), np.float32) if p.tangents else None
+        f = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
+        _check_pt(self._l.mi_pt_read_vertices(self._p, int(prim), f(pos), f(nrm), f(tan)))
+        return pos, nrm, tan
+
     def update_from_scene(self, scene):
-        """After Scene.update_animation: hands the scene's render-node and light tables to the device again."""
+        """After Scene.update_animation: hands the scene's render-node and light tables to the device again -- and, after set_deformation,
+        deforms the skinned / morphed geometry first (with the rebuild left to update_render_nodes: one per frame)."""
         d = scene.desc.contents
+        deform = scene.deformation if getattr(self, "_deforming", False) else None
+        if deform is not None:
+            self.update_deformation(deform.jointMatrices, deform.morphWeights, defer_build=True)
         self.update_render_nodes(d.renderNodes, d.numRenderNodes, d.renderNodeVisible)
         self.update_lights(d.lights, d.numLights)
 

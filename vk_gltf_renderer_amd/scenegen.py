@@ -93,7 +93,44 @@ class GlbBuilder:
         self.doc["materials"].append(mat)
         return len(self.doc["materials"]) - 1
 
-    def primitive(self, positions, indices=None, normals=None, uv0=None, uv1=None, colors=None, tangents=None, material=None):
+    def sparse_accessor(self, count, indices, values, base=None):
+        """An accessor of `count` elements whose listed elements come from a sparse block (indices u16 / u32, values (n, c) float32);
+        the others are zero, or `base` ((count, c) float32, stored dense)."""
+        values = np.ascontiguousarray(values, np.float32)
+        indices = np.asarray(indices)
+        indices = indices.astype(np.uint16) if indices.max(initial=0) < 65535 else indices.astype(np.uint32)
+        acc = {"componentType": 5126, "count": int(count), "type": _TYPE[values.shape[1]],
+               "sparse": {"count": int(len(indices)), "indices": {"bufferView": self._view(indices.tobytes()), "componentType": _COMPONENT[indices.dtype]},
+                          "values": {"bufferView": self._view(values.tobytes())}}}
+        if base is not None:
+            acc["bufferView"] = self._view(np.ascontiguousarray(base, np.float32).tobytes())
+        self.doc["accessors"].append(acc)
+        return len(self.doc["accessors"]) - 1
+
+    def skin(self, joints, inverse_bind=None):
+        """A skin over `joints` (node indices); inverse_bind: (n, 4, 4) row-major matrices (stored column-major) or None."""
+        sk = {"joints": [int(j) for j in joints]}
+        if inverse_bind is not None:
+            m = np.asarray(inverse_bind, np.float32).transpose(0, 2, 1).reshape(-1, 16)
+            sk["inverseBindMatrices"] = self.accessor(m)
+        self.doc.setdefault("skins", []).append(sk)
+        return len(self.doc["skins"]) - 1
+
+    def primitive(self, positions, indices=None, normals=None, uv0=None, uv1=None, colors=None, tangents=None, material=None, joints=None,
+                  weights=None, targets=None):
+        """joints: (V, 4) uint8 / uint16 (JOINTS_0); weights: (V, 4) float32, or uint8 / uint16 stored normalized (WEIGHTS_0);
+        targets: [{"POSITION" | "NORMAL" | "TANGENT": (V, 3) float32 array or accessor index}] morph targets."""
+        prim = self._primitive(positions, indices, normals, uv0, uv1, colors, tangents, material)
+        if joints is not None:
+            prim["attributes"]["JOINTS_0"] = self.accessor(np.asarray(joints), 34962)
+        if weights is not None:
+            weights = np.asarray(weights)
+            prim["attributes"]["WEIGHTS_0"] = self.accessor(weights, 34962, normalized=weights.dtype != np.float32)
+        if targets is not None:
+            prim["targets"] = [{k: (v if isinstance(v, int) else self.accessor(np.asarray(v, np.float32), 34962)) for k, v in t.items()} for t in targets]
+        return prim
+
+    def _primitive(self, positions, indices=None, normals=None, uv0=None, uv1=None, colors=None, tangents=None, material=None):
         attrs = {"POSITION": self.accessor(np.asarray(positions, np.float32), 34962, minmax=True)}
         if normals is not None:
             attrs["NORMAL"] = self.accessor(np.asarray(normals, np.float32), 34962)
@@ -115,8 +152,11 @@ class GlbBuilder:
             prim["material"] = material
         return prim
 
-    def mesh(self, primitives):
-        self.doc["meshes"].append({"primitives": primitives})
+    def mesh(self, primitives, weights=None):
+        m = {"primitives": primitives}
+        if weights is not None:
+            m["weights"] = [float(w) for w in weights]
+        self.doc["meshes"].append(m)
         return len(self.doc["meshes"]) - 1
 
     def node(self, root=True, **kw):
@@ -156,13 +196,14 @@ class GlbBuilder:
         return len(ext["lights"]) - 1
 
     def animation(self, channels, name=None):
-        """channels: [(node, path, times, values, interpolation)]; CUBICSPLINE values are (keys, 3, n): in-tangent, value, out-tangent."""
+        """channels: [(node, path, times, values, interpolation)]; CUBICSPLINE values are (keys, 3, n): in-tangent, value, out-tangent.
+        A "weights" channel's values are (keys, targets), or (keys, 3, targets) for CUBICSPLINE."""
         anim = {"samplers": [], "channels": []}
         if name:
             anim["name"] = name
         for node, path, times, values, interp in channels:
             values = np.asarray(values, np.float32)
-            out = values.reshape(-1, values.shape[-1])
+            out = values.reshape(-1) if path == "weights" else values.reshape(-1, values.shape[-1])  # (weights: SCALAR, all targets per key)
             anim["samplers"].append({"input": self.accessor(np.asarray(times, np.float32), minmax=True), "output": self.accessor(out),
                                      "interpolation": interp})
             anim["channels"].append({"sampler": len(anim["samplers"]) - 1, "target": {"node": node, "path": path}})
@@ -1045,3 +1086,136 @@ def scene_animated(path, seed=5, tess=12):
     b.animation([(still, "translation", [1.0, 3.0], [[-2.0, -0.6, -1.0], [-2.0, 0.8, -1.0]], "LINEAR")], name="lift")
     b.ext_used.add("EXT_mesh_gpu_instancing")
     return b.save(path)
+
+
+def _rot_matrix(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def scene_skinned(path, seed=11, tess=12):
+    """Skins and morph targets: a tessellated limb (normal-mapped, no TANGENT: tangents are generated) skinned to a 3-joint chain under a
+    rotated and scaled rig node, drawn by two nodes that share the skinned mesh, plus a second skinned primitive in the same mesh; a morph
+    blob with 3 targets (dense POSITION + NORMAL, sparse POSITION, POSITION + NORMAL on a non-zero base) driven by a LINEAR, a STEP and a
+    CUBICSPLINE weights channel on successive time ranges; a primitive that is both morphed and skinned.  JOINTS_0 come as u8 and u16,
+    WEIGHTS_0 as float, normalized u8 and normalized u16.  Clip "pose": [0, 3] s.  tess scales every tessellation (tess=240: ~1.6 M deformed
+    vertices, the timing variant)."""
+    rng = np.random.default_rng(seed)
+    b = GlbBuilder()
+    nmap = np.zeros((8, 8, 4), np.uint8)
+    nmap[..., 0] = 128 + rng.integers(-40, 40, (8, 8))
+    nmap[..., 1] = 128 + rng.integers(-40, 40, (8, 8))
+    nmap[..., 2] = 230
+    nmap[..., 3] = 255
+    bumpy = b.material({"pbrMetallicRoughness": {"baseColorFactor": [0.85, 0.55, 0.35, 1], "metallicFactor": 0.0, "roughnessFactor": 0.6},
+                        "normalTexture": {"index": b.texture(b.image(nmap), b.sampler())}})
+    green = b.material(lambert_material((0.3, 0.7, 0.35)))
+    blue = b.material({"pbrMetallicRoughness": {"baseColorFactor": [0.25, 0.35, 0.85, 1], "metallicFactor": 0.3, "roughnessFactor": 0.4}})
+    grey = b.material(lambert_material((0.6, 0.6, 0.6)))
+
+    # ---- skeleton: rig (rotated, scaled) -> j0 -> j1 -> j2, 0.7 apart along y
+    j2 = b.node(root=False, translation=[0.0, 0.7, 0.0])
+    j1 = b.node(root=False, translation=[0.0, 0.7, 0.0], children=[j2])
+    j0 = b.node(root=False, translation=[0.0, 0.0, 0.0], children=[j1])
+    bind = [np.eye(4) for _ in range(3)]
+    for k in range(3):
+        bind[k][1, 3] = 0.7 * k
+    ibm = np.stack([np.linalg.inv(m) for m in bind])
+    ibm_short = ibm[:2]  # the second skin lists fewer inverse bind matrices than joints: the last joint takes identity
+    skin = b.skin([j0, j1, j2], ibm)
+    skin2 = b.skin([j0, j1, j2], ibm_short)
+
+    # limb: a cylinder from y = -0.1 to 1.5, weights blended between the two nearest joints
+    rings, seg = 4 * tess, 2 * tess
+    yy, aa = np.meshgrid(np.linspace(-0.1, 1.5, rings + 1), np.linspace(0, 2 * np.pi, seg + 1), indexing="ij")
+    yy, aa = yy.reshape(-1), aa.reshape(-1)
+    rad = 0.18 + 0.03 * np.sin(3 * yy)
+    lp = np.stack([rad * np.cos(aa), yy, rad * np.sin(aa)], 1).astype(np.float32)
+    ln = np.stack([np.cos(aa), np.zeros_like(aa), np.sin(aa)], 1).astype(np.float32)
+    luv = np.stack([aa / (2 * np.pi), yy], 1).astype(np.float32)
+    i = (np.arange(rings)[:, None] * (seg + 1) + np.arange(seg)[None, :]).reshape(-1)
+    lidx = np.stack([i, i + seg + 2, i + seg + 1, i, i + 1, i + seg + 2], 1).reshape(-1, 3).astype(np.uint32)
+
+    def influences(y):
+        f = np.clip(y / 0.7, 0, 1.999)
+        lo = np.floor(f).astype(np.int64)
+        fr = f - lo
+        j = np.stack([lo, lo + 1, np.zeros_like(lo), np.zeros_like(lo)], 1)
+        w = np.stack([1 - fr, fr, np.zeros_like(fr), np.zeros_like(fr)], 1)
+        return j, w
+    lj, lw = influences(lp[:, 1])
+    limb = b.primitive(lp, lidx, normals=ln, uv0=luv, material=bumpy, joints=lj.astype(np.uint8), weights=lw.astype(np.float32))
+    # a fin along the limb: u16 joints, normalized u16 weights
+    fp, fn, fuv, fi = grid(2 * tess, 4 * tess, (0.3, 1.5), axis="z")
+    fp = (fp + np.array([0.35, 0.75, 0.0], np.float32)).astype(np.float32)
+    fj, fw = influences(fp[:, 1])
+    fin = b.primitive(fp, fi, normals=fn, uv0=fuv, material=green, joints=fj.astype(np.uint16), weights=np.round(fw * 65535).astype(np.uint16))
+    limb_mesh = b.mesh([limb, fin])
+    arm_a = b.node(root=False, mesh=limb_mesh, skin=skin)
+    arm_b = b.node(root=False, mesh=limb_mesh, skin=skin, translation=[0.9, 0.0, 0.3])  # shares the deformation of arm_a
+
+    # morph + skin: a plate bent by two targets, skinned by u16 joints with normalized u8 weights (the skin with the short IBM list)
+    cp, cn, cuv, ci = grid(3 * tess, 3 * tess, (0.5, 1.2), axis="x")
+    cp = (cp + np.array([-0.4, 0.7, 0.0], np.float32)).astype(np.float32)
+    cj, cw = influences(cp[:, 1])
+    cw8 = np.round(cw * 255).astype(np.uint8)
+    bend = np.zeros_like(cp)
+    bend[:, 0] = 0.25 * np.sin(np.pi * (cp[:, 1] - 0.1) / 1.2)
+    bend_n = np.zeros_like(cn)
+    bend_n[:, 1] = 0.4 * np.cos(np.pi * (cp[:, 1] - 0.1) / 1.2)
+    twist = np.zeros_like(cp)
+    twist[:, 2] = 0.2 * (cp[:, 1] - 0.7) * np.sign(cp[:, 2])
+    combo = b.primitive(cp, ci, normals=cn, uv0=cuv, material=blue, joints=cj.astype(np.uint16), weights=cw8,
+                        targets=[{"POSITION": bend, "NORMAL": bend_n}, {"POSITION": twist}])
+    combo_mesh = b.mesh([combo], weights=[0.5, 0.0])
+    plate = b.node(root=False, mesh=combo_mesh, skin=skin2)
+    rig = b.node(translation=[-0.6, -0.8, 0.0], rotation=_quat((0, 0, 1), -0.35), scale=[1.3, 1.1, 1.2], children=[j0, arm_a, arm_b, plate])
+
+    # morph blob: 3 targets; the second one sparse (a patch of vertices), the third on a non-zero base accessor with normal deltas
+    sp, sn, suv, si = uv_sphere(2 * tess, tess, 0.45)
+    suv[:, 0] = np.abs(2 * suv[:, 0] - 1)  # mirrored: a MikkTSpace recomputation splits vertices along the mirror line
+    nv = sp.shape[0]
+    t0 = (sn * 0.15 * (sp[:, 1:2] > 0)).astype(np.float32)
+    t0n = np.zeros_like(sn)
+    t0n[:, 1] = 0.3 * (sp[:, 1] > 0)
+    patch = np.nonzero((sp[:, 0] > 0.2) & (np.abs(sp[:, 1]) < 0.2))[0]
+    vals = np.tile(np.array([[0.25, 0.0, 0.0]], np.float32), (len(patch), 1))
+    t2 = np.zeros_like(sp)
+    t2[:, 2] = 0.1 * np.sin(6 * np.arctan2(sp[:, 0], sp[:, 2]))
+    t2n = (rng.uniform(-0.2, 0.2, sn.shape)).astype(np.float32)
+    sparse_base = np.zeros_like(sp)
+    sparse_base[:, 1] = -0.05 * (sp[:, 1] < -0.3)
+    tgt = [{"POSITION": t0, "NORMAL": t0n},
+           {"POSITION": b.sparse_accessor(nv, patch, vals)},
+           {"POSITION": b.sparse_accessor(nv, patch[:3], vals[:3] * 0.5, base=t2), "NORMAL": t2n}]
+    blob_mesh = b.mesh([b.primitive(sp, si, normals=sn, uv0=suv, material=grey, targets=tgt)], weights=[0.0, 0.0, 0.0])
+    blob = b.node(mesh=blob_mesh, translation=[1.2, 0.2, -0.3])
+
+    fp2, fn2, _, fi2 = grid(4, 4, (8, 8))
+    b.node(mesh=b.mesh([b.primitive(fp2, fi2, normals=fn2, material=grey)]), translation=[0, -1.0, 0])
+    b.camera_node((0.3, 0.8, 4.2), (0.2, 0.0, 0.0), yfov=0.75)
+    b.light({"type": "directional", "intensity": 2.5})
+    b.node(rotation=_quat((1, 0.3, 0), -0.9), extensions={"KHR_lights_punctual": {"light": 0}})
+
+    t4 = [0.0, 1.0, 2.0, 3.0]
+    rot1 = [_quat((0, 0, 1), a) for a in (0.0, 0.6, -0.4, 0.9)]
+    rot2 = [_quat((1, 0, 1), a) for a in (0.0, -0.8, 0.7, 0.2)]
+    cub = np.zeros((3, 3, 3), np.float32)
+    cub[:, 1] = [[0.2, 0.0, 0.9], [0.9, 0.5, 0.0], [0.1, 1.0, 0.4]]
+    cub[:, 0] = rng.uniform(-0.5, 0.5, (3, 3))
+    cub[:, 2] = rng.uniform(-0.5, 0.5, (3, 3))
+    b.animation([(j1, "rotation", t4, rot1, "LINEAR"),
+                 (j2, "rotation", t4, rot2, "STEP"),
+                 (j0, "translation", [0.0, 3.0], [[0, 0, 0], [0.1, 0.2, 0.0]], "LINEAR"),
+                 (blob, "weights", [0.0, 1.0], [[0.0, 0.0, 0.0], [1.0, 0.6, 0.3]], "LINEAR"),
+                 (blob, "weights", [1.0, 1.5, 2.0], [[0.3, 0.2, 0.8], [0.9, 0.0, 0.5], [0.4, 0.7, 0.1]], "STEP"),
+                 (blob, "weights", [2.0, 2.5, 3.0], cub, "CUBICSPLINE"),
+                 (plate, "weights", [0.0, 3.0], [[0.0, 0.0], [1.0, 1.0]], "LINEAR")], name="pose")
+    return b.save(path)
+
+
+def scene_skinned_large(path, seed=11):
+    """scene_skinned with ~1.6 M deformed vertices (the timing variant)."""
+    return scene_skinned(path, seed=seed, tess=240)
