@@ -232,6 +232,40 @@ MI_PT_API int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc);
  * MI_PT_DEFORM_DEFER_BUILD, for a caller that calls mi_pt_update_render_nodes next (one rebuild per animated frame).  Non-finite
  * values: MI_PT_ERR_ARGUMENT, nothing changes.  Synchronises with the work in flight (queued frames render the old pose). */
 MI_PT_API int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* morphWeights, int flags);
+/* How the acceleration structure follows an animated frame (mi_pt_update_render_nodes, and mi_pt_update_deformation without
+ * MI_PT_DEFORM_DEFER_BUILD).  REBUILD (default): a full build, as always.  REFIT: the 8-wide tree keeps its topology and is refitted in
+ * place -- the triangle records and boxes of what moved or deformed, then every node's boxes, level by level.  AUTO: refit while the
+ * refitted tree's SAH cost stays within rebuildCostRatio x the cost right after the last full build, rebuild otherwise.  An update is
+ * refitted only when the 8-wide walk is active (not bvhBuilder bit 0, not MI_PT_HOST_COLLAPSE) and the node table differs from the
+ * resident one in objectToWorld / worldToObject alone (same primitives, materials and visibility); every other update rebuilds.  The
+ * image does not depend on the tree: a refitted frame renders bit for bit what a fresh instance of the same pose renders.  Instances back
+ * at the matrices of the last build get the boxes they were built with; a primitive deformed since that build keeps its refitted boxes
+ * (pre-split references: their whole triangles' boxes) until the next build. */
+enum
+{
+  MI_PT_ACCEL_REBUILD = 0,
+  MI_PT_ACCEL_REFIT   = 1,
+  MI_PT_ACCEL_AUTO    = 2
+};
+enum { MI_PT_ACCEL_LAST_BUILD = 0, MI_PT_ACCEL_LAST_REFIT = 1 }; /* MiPtAccelInfo::lastUpdate */
+/* Unknown mode, or a ratio that is not finite or below 1: MI_PT_ERR_ARGUMENT.  Switching to REFIT or AUTO while the structure holds no
+ * refit data rebuilds it once, here (a build), unless no build can keep any (BVH2 walk, MI_PT_HOST_COLLAPSE, an empty or one-reference
+ * scene); switching to REBUILD frees the refit data at once.  Synchronises like an update. */
+MI_PT_API int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio);
+typedef struct MiPtAccelInfo
+{
+  int32_t  mode;              /* MI_PT_ACCEL_* in force */
+  int32_t  lastUpdate;        /* MI_PT_ACCEL_LAST_*: what the last build or update did (an AUTO refit it replaced by a rebuild counts as a build) */
+  float    rebuildCostRatio;  /* AUTO's bound */
+  int32_t  reserved;
+  uint64_t builds;            /* full builds of this instance, the one of mi_pt_create included */
+  uint64_t refits;
+  double   sahCostAtBuild;    /* SAH cost of the tree right after the last full build, and now (0 without refit data); bit-reproducible: */
+  double   sahCost;           /* the same inputs give the same cost, and so the same AUTO decision */
+  uint64_t trianglesMoved;    /* triangles whose render node moved or whose primitive deformed, at the last refit */
+  uint64_t refitBytes;        /* device memory of the refit data (counted in MiPtMemory::sceneBytes) */
+} MiPtAccelInfo;
+MI_PT_API int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* info);
 /* Reads back the resident streams of a render primitive (vertexCount x 3 / 3 / 4 floats); any pointer may be NULL, and a stream the
  * primitive does not have is left untouched. */
 MI_PT_API int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* normals, float* tangents);
@@ -359,8 +393,9 @@ MI_PT_API const char* mi_pt_version(void);
  * MiPathtraceParams, ...) grows or changes: the library writes every field of the struct it was compiled with, so a caller built against an older
  * header must refuse to run -- `if(mi_pt_abi_version() != MI_PT_ABI_VERSION) fail` right after loading the library.
  * 6: MiPtMemory grew pathStateBytes / pathSlots (round 5); mi_pt_render_frames refuses maxDepth 0; mi_pt_set_frame_queue.
- * 7: MiPtDeformPrimitive / MiPtDeformDesc and the deformation entry points (skins and morph targets on the device). */
-#define MI_PT_ABI_VERSION 7
+ * 7: MiPtDeformPrimitive / MiPtDeformDesc and the deformation entry points (skins and morph targets on the device).
+ * 8: MiPtAccelInfo and the refit entry points (mi_pt_set_accel_update, mi_pt_get_accel_info). */
+#define MI_PT_ABI_VERSION 8
 MI_PT_API int mi_pt_abi_version(void);
 
 #ifdef __cplusplus

@@ -1,0 +1,346 @@
+"""Refit of the 8-wide BVH in place on animated frames (mi_pt_set_accel_update, csrc/device/bvh_refit.hip).  The image does not depend on the
+tree, so a refitted frame must render bit for bit what a fresh instance of the same pose renders: skinned clips, node-transform clips,
+pre-split references, mirrored matrices and non-opaque instances.  Also: no drift back to the build's pose, the fallbacks that rebuild, the
+AUTO policy, queued frames, memory and the build-timing lines."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import deform_util as du
+import parity_util as pu
+from vk_gltf_renderer_amd import _capi as capi
+from vk_gltf_renderer_amd import pathtracer as ptmod
+from vk_gltf_renderer_amd import scenegen
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H, FRAMES = 128, 96, 2
+
+
+@pytest.fixture(scope="module")
+def skinned(tmp_path_factory):
+    return scenegen.scene_skinned(str(tmp_path_factory.mktemp("gpu_refit") / "skinned.glb"))
+
+
+@pytest.fixture(scope="module")
+def animated(tmp_path_factory):
+    return scenegen.scene_animated(str(tmp_path_factory.mktemp("gpu_refit") / "animated.glb"))
+
+
+def _tracer(st, **kw):
+    tr = ptmod.PathTracer(st.scene, **kw)
+    tr.resize(st.width, st.height)
+    tr.set_frame_info(st.frame_info)
+    tr.set_sky(st.sky)
+    return tr
+
+
+def _render(tr, st, frames=FRAMES):
+    total = 0
+    for f in range(frames):
+        p = st.frame_params(f, total)
+        tr.render_frame(p)
+        total += p.numSamples
+    return tr.read_accum()
+
+
+def _images(tr, st):
+    return _render(tr, st), tr.read_selection(), tr.read_depth()
+
+
+def _same_as_fresh(tr, st, scene=None, what=""):
+    """The refitted instance renders what a fresh instance of the scene's current tables renders, bit for bit."""
+    got = _images(tr, st)
+    fresh = _tracer(st) if scene is None else ptmod.PathTracer(scene)
+    if scene is not None:
+        fresh.resize(st.width, st.height)
+        fresh.set_frame_info(st.frame_info)
+        fresh.set_sky(st.sky)
+    want = _images(fresh, st)
+    fresh.close()
+    for g, w, name in zip(got, want, ("accum", "selection", "depth")):
+        assert (g == w).all(), (what, name, int((g != w).sum()))
+    return got[0]
+
+
+def _nodes(scene):
+    d = scene.desc.contents
+    return d.renderNodes, int(d.numRenderNodes)
+
+
+def _set_matrix(node, M):
+    M = np.asarray(M, np.float64)
+    node.objectToWorld[:] = [float(v) for v in M.T.reshape(-1).astype(np.float32)]
+    node.worldToObject[:] = [float(v) for v in np.linalg.inv(M).T.reshape(-1).astype(np.float32)]
+
+
+def _matrix(node):
+    return np.array(node.objectToWorld[:], np.float64).reshape(4, 4).T
+
+
+def _rot(axis, angle, t=(0, 0, 0)):
+    c, s = np.cos(angle), np.sin(angle)
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    R = np.eye(4)
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    R[:3, 3] = t
+    return R
+
+
+def test_skinned_clip_refits_like_a_fresh_instance(skinned):
+    st = pu.Setup(skinned, W, H, max_depth=3)
+    tr = _tracer(st)
+    tr.set_deformation(st.scene)
+    tr.set_accel_update("refit")
+    info = tr.accel_info()
+    assert info["mode"] == capi.MI_PT_ACCEL_REFIT and info["builds"] == 2 and info["refits"] == 0 and info["refitBytes"] > 0, info
+    assert info["sahCostAtBuild"] > 0 and info["sahCost"] == info["sahCostAtBuild"], info
+    d = st.scene.deformation
+    rest = _render(tr, st)
+    for k, time in enumerate((0.6, 1.4, 2.7)):
+        assert st.scene.update_animation(0, time)
+        tr.update_from_scene(st.scene)
+        info = tr.accel_info()
+        assert info["builds"] == 2 and info["refits"] == k + 1 and info["lastUpdate"] == capi.MI_PT_ACCEL_LAST_REFIT, info
+        assert info["trianglesMoved"] > 0, info
+        streams = {p.renderPrimID: tr.read_vertices(p.renderPrimID) for p in du.prims(d)}
+        holder, keep = du.posed_desc(st.scene, streams)
+        img = _same_as_fresh(tr, st, holder, time)
+        assert not (img == rest).all()
+    tr.close()
+
+
+def test_node_transform_clip_refits_like_a_fresh_instance(animated):
+    st = pu.Setup(animated, W, H, max_depth=3)
+    tr = _tracer(st)
+    tr.set_accel_update(capi.MI_PT_ACCEL_REFIT)
+    for k, time in enumerate((0.3, 1.1, 1.9, 0.0)):
+        assert st.scene.update_animation(0, time)
+        tr.update_from_scene(st.scene)
+        _same_as_fresh(tr, st, what=time)
+    info = tr.accel_info()
+    assert info["builds"] == 2 and info["refits"] == 4, info
+    tr.close()
+
+
+def _move_and_compare(st, moves, what):
+    """Refit after each move of render nodes ({index: 4x4 world matrix}) in the scene's own table; compare with a fresh instance."""
+    nodes, n = _nodes(st.scene)
+    tr = _tracer(st)
+    tr.set_accel_update("refit")
+    for step in moves:
+        for i, M in step.items():
+            _set_matrix(nodes[i], M)
+        tr.update_render_nodes(nodes, n, st.scene.desc.contents.renderNodeVisible)
+        assert tr.accel_info()["lastUpdate"] == capi.MI_PT_ACCEL_LAST_REFIT, what
+        _same_as_fresh(tr, st, what=what)
+    tr.close()
+
+
+def test_moved_pre_split_instance(tmp_path):
+    path = scenegen.scene_atrium_class(str(tmp_path / "atrium_sliver.glb"), detail=0.25, tex_size=64, sliver=True)
+    st = pu.Setup(path, W, H, max_depth=2)
+    nodes, n = _nodes(st.scene)
+    counts = [int(st.scene.desc.contents.renderPrimitives[nodes[i].renderPrimID].triangleCount) if nodes[i].renderPrimID >= 0 else 0 for i in range(n)]
+    big = int(np.argmax(counts))
+    M0 = _matrix(nodes[big])
+    _move_and_compare(st, [{big: _rot(1, 0.2, (0.3, 0.1, -0.2)) @ M0}, {big: _rot(0, -0.1, (0.0, 0.4, 0.1)) @ M0}], "sliver atrium")
+
+
+def test_mirrored_matrix(animated):
+    st = pu.Setup(animated, W, H, max_depth=3)
+    nodes, n = _nodes(st.scene)
+    M0 = _matrix(nodes[n - 1])
+    _move_and_compare(st, [{n - 1: np.diag([-1.0, 1.0, 1.0, 1.0]) @ M0}, {n - 1: M0}], "mirrored")
+
+
+def test_every_node_of_mixed_alpha_glass_rotated(tmp_path):
+    st = pu.Setup(scenegen.scene_mixed_alpha_glass(str(tmp_path / "mixed.glb")), W, H, max_depth=4)
+    nodes, n = _nodes(st.scene)
+    M0 = [_matrix(nodes[i]) for i in range(n)]
+    _move_and_compare(st, [{i: _rot(1, 0.05 * (i + 1), (0.02 * i, 0.0, 0.0)) @ M0[i] for i in range(n)}], "mixed alpha glass")
+
+
+def test_no_drift_back_to_the_built_pose(animated):
+    """Refit to a pose and back to the build's: the SAH cost is the build's bit for bit, and node visits and triangle tests are those of the
+    tree as built, up to what two renders of one tree differ by (shadow counters: a few tenths of a per cent; a refit that drifted, or another
+    tree, is tens of per cent away)."""
+    st = pu.Setup(animated, W, H, max_depth=3)
+    nodes, n = _nodes(st.scene)
+    M0 = [_matrix(nodes[i]) for i in range(n)]
+    raw = [(list(nodes[i].objectToWorld), list(nodes[i].worldToObject)) for i in range(n)]
+    tr = _tracer(st, collect_counters=True)
+    tr.set_accel_update("refit")
+    want = []
+    for _ in range(2):  # (the tree as built, rendered twice: the walk counters of one tree differ by a few visits from render to render)
+        tr.reset_stats()
+        _render(tr, st)
+        want.append(tr.stats())
+    sah0 = tr.accel_info()["sahCost"]
+    for i in range(n):
+        _set_matrix(nodes[i], _rot(2, 0.4, (0.5, 0.2, 0.0)) @ M0[i])
+    tr.update_render_nodes(nodes, n, None)
+    assert tr.accel_info()["sahCost"] != sah0
+    for i in range(n):  # (the build's exact tables back)
+        nodes[i].objectToWorld[:], nodes[i].worldToObject[:] = raw[i]
+    tr.update_render_nodes(nodes, n, None)
+    assert tr.accel_info()["sahCost"] == sah0 and tr.accel_info()["refits"] == 2
+    for _ in range(2):
+        tr.reset_stats()
+        _render(tr, st)
+        got = tr.stats()
+        for k in ("nodesClosest", "trisClosest", "nodesShadow", "trisShadow", "nodesPrimary", "trisPrimary"):
+            spread = max(abs(want[1][k] - want[0][k]), 1e-2 * want[0][k])
+            assert abs(got[k] - want[0][k]) <= spread, (k, got[k], want[0][k], want[1][k])
+    tr.close()
+
+
+def test_fallbacks_rebuild(animated):
+    st = pu.Setup(animated, W, H, max_depth=3)
+    nodes, n = _nodes(st.scene)
+    tr = _tracer(st)
+    tr.set_accel_update("refit")
+    # a visibility change
+    vis = (C.c_uint8 * n)(*([1] * (n - 1) + [0]))
+    tr.update_render_nodes(nodes, n, vis)
+    info = tr.accel_info()
+    assert info["lastUpdate"] == capi.MI_PT_ACCEL_LAST_BUILD and info["builds"] == 3 and info["refits"] == 0, info
+    # a material change
+    nodes[0].materialID = (nodes[0].materialID + 1) % int(st.scene.desc.contents.numMaterials)
+    tr.update_render_nodes(nodes, n, None)
+    info = tr.accel_info()
+    assert info["lastUpdate"] == capi.MI_PT_ACCEL_LAST_BUILD and info["builds"] == 4, info
+    _same_as_fresh(tr, st, what="material")
+    tr.close()
+    # the BVH2 walk
+    tr = _tracer(st, bvh=1)
+    tr.set_accel_update("refit")
+    assert tr.accel_info()["builds"] == 1  # (the BVH2 walk can never refit: the switch builds nothing)
+    _set_matrix(nodes[n - 1], _rot(1, 0.3) @ _matrix(nodes[n - 1]))
+    tr.update_render_nodes(nodes, n, None)
+    info = tr.accel_info()
+    assert info["lastUpdate"] == capi.MI_PT_ACCEL_LAST_BUILD and info["refits"] == 0 and info["refitBytes"] == 0, info
+    got = _images(tr, st)
+    tr.close()
+    fresh = _tracer(st, bvh=1)
+    want = _images(fresh, st)
+    fresh.close()
+    assert all((g == w).all() for g, w in zip(got, want))
+
+
+def test_bad_arguments(animated):
+    st = pu.Setup(animated, 32, 32, max_depth=2)
+    tr = _tracer(st)
+    for mode, ratio in ((3, 1.5), (-1, 1.5), (1, 0.5), (2, float("nan")), (2, float("inf"))):
+        with pytest.raises(ptmod.MiError):
+            tr.set_accel_update(mode, ratio)
+    assert tr.accel_info()["mode"] == capi.MI_PT_ACCEL_REBUILD and tr.accel_info()["builds"] == 1
+    tr.close()
+
+
+def test_auto_policy(animated):
+    st = pu.Setup(animated, 64, 48, max_depth=2)
+    nodes, n = _nodes(st.scene)
+    M0 = [_matrix(nodes[i]) for i in range(n)]
+    poses = [{i: _rot(1, 0.3 * k, (0.2 * k * (i % 2), 0.0, 0.0)) @ M0[i] for i in range(n)} for k in (1, 2, 3, 1)]
+
+    def run(ratio):
+        tr = _tracer(st)
+        tr.set_accel_update("auto", ratio)
+        seq = []
+        for pose in poses:
+            for i, M in pose.items():
+                _set_matrix(nodes[i], M)
+            tr.update_render_nodes(nodes, n, None)
+            a = tr.accel_info()
+            seq.append((a["lastUpdate"], a["sahCost"], a["sahCostAtBuild"]))
+        tr.close()
+        for i in range(n):
+            _set_matrix(nodes[i], M0[i])
+        return seq
+    tight, loose = run(1.0), run(1e30)
+    assert all(s[0] == capi.MI_PT_ACCEL_LAST_REFIT for s in loose), loose
+    # ratio 1: any growth of the cost rebuilds (and a rebuild resets the reference cost)
+    assert any(s[0] == capi.MI_PT_ACCEL_LAST_BUILD for s in tight), tight
+    for kind, cost, at_build in tight:
+        assert kind == capi.MI_PT_ACCEL_LAST_BUILD or cost <= at_build, tight
+    assert run(1.0) == tight and run(1.2) == run(1.2)
+
+
+def test_memory_and_queued_frames(skinned):
+    st = pu.Setup(skinned, W, H, max_depth=3)
+    tr = _tracer(st)
+    tr.set_deformation(st.scene)
+    rebuild_bytes = tr.memory()["sceneBytes"]
+    tr.set_accel_update("refit")
+    info = tr.accel_info()
+    assert tr.memory()["sceneBytes"] == rebuild_bytes + info["refitBytes"]
+    seen = []
+    for k in range(8):
+        st.scene.update_animation(0, (0.4, 1.9)[k % 2])
+        tr.update_from_scene(st.scene)
+        seen.append(tr.memory()["sceneBytes"])
+        assert k < 2 or seen[k] == seen[k - 2], (k, seen)
+    with_refit = tr.memory()["sceneBytes"]
+    refit_bytes = tr.accel_info()["refitBytes"]
+    tr.set_accel_update("rebuild")
+    assert tr.accel_info()["refitBytes"] == 0 and tr.memory()["sceneBytes"] == with_refit - refit_bytes
+    # ... and after the next update, what an instance that never left REBUILD holds after the same update
+    other_st = pu.Setup(skinned, W, H, max_depth=3)
+    other = _tracer(other_st)
+    other.set_deformation(other_st.scene)
+    for t in (0.4, 0.0):
+        for s_, x in ((st, tr), (other_st, other)):
+            s_.scene.update_animation(0, t)
+            x.update_from_scene(s_.scene)
+    assert tr.memory()["sceneBytes"] == other.memory()["sceneBytes"]
+    other.close()
+    tr.close()
+
+    ref_st = pu.Setup(skinned, W, H, max_depth=3)
+    ref = _tracer(ref_st)
+    want = _render(ref, ref_st, 3)
+    ref.close()
+    q_st = pu.Setup(skinned, W, H, max_depth=3)
+    q = _tracer(q_st)
+    q.set_deformation(q_st.scene)
+    q.set_accel_update("refit")
+    q.set_frame_queue(8)
+    total = 0
+    for f in range(3):
+        p = q_st.frame_params(f, total)
+        q.render_frame(p)
+        total += p.numSamples
+    q_st.scene.update_animation(0, 1.1)
+    q.update_from_scene(q_st.scene)  # flushes the three queued frames first
+    assert (q.read_accum() == want).all()
+    assert q.accel_info()["lastUpdate"] == capi.MI_PT_ACCEL_LAST_REFIT
+    q.close()
+
+
+def test_one_refit_per_animated_frame(skinned):
+    script = (
+        "import sys; sys.path[:0] = [%r, %r]\n"
+        "import parity_util as pu\n"
+        "from vk_gltf_renderer_amd import pathtracer as ptmod\n"
+        "st = pu.Setup(%r, 64, 48, max_depth=2)\n"
+        "tr = ptmod.PathTracer(st.scene)\n"
+        "tr.set_deformation(st.scene)\n"
+        "tr.set_accel_update('refit')\n"
+        "print('[mark] animated', file=sys.stderr, flush=True)\n"
+        "for t in (0.5, 1.5, 2.5):\n"
+        "    st.scene.update_animation(0, t)\n"
+        "    tr.update_from_scene(st.scene)\n"
+        "tr.close()\n") % (ROOT, os.path.join(ROOT, "tests"), skinned)
+    env = dict(os.environ, MI_PT_BUILD_TIMING="1")
+    r = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    animated = r.stderr.split("[mark] animated")[1]
+
+    def count(what):
+        return sum(1 for line in animated.splitlines() if line.startswith("[mi_pt build]") and line.split()[2] == what)
+    assert count("deform") == 3 and count("refit") == 3 and count("rebuild") == 0, animated

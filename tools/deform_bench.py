@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--tess", type=int, default=240)
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--size", type=int, nargs=2, default=(1920, 1080))
+    ap.add_argument("--accel-update", choices=("rebuild", "refit", "auto"), default="rebuild",
+                    help="mi_pt_set_accel_update mode: with refit / auto, rebuild_ms is the time of the acceleration update (a refit)")
+    ap.add_argument("--ratio", type=float, default=1.5, help="AUTO's rebuild cost ratio")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         glb = scenegen.scene_skinned(os.path.join(tmp, "skinned_large.glb"), tess=a.tess)
@@ -54,7 +57,9 @@ def main():
         tr.set_frame_info(st.frame_info)
         tr.set_sky(st.sky)
         tr.set_deformation(st.scene)
+        tr.set_accel_update(a.accel_update, a.ratio)
         desc = st.scene.desc.contents
+        sah = []
         t_def, t_rebuild, t_anim, t_nodes, moved = [], [], [], [], []
         times = [0.1 + 2.8 * f / max(a.frames - 1, 1) for f in range(a.frames)]
         for f, t in enumerate([0.05] + times):  # (the first one warms up)
@@ -66,6 +71,9 @@ def main():
             tr.update_render_nodes(desc.renderNodes, desc.numRenderNodes, desc.renderNodeVisible)
             tr.update_lights(desc.lights, desc.numLights)
             t2 = time.perf_counter()
+            info = tr.accel_info()
+            if f and info["sahCostAtBuild"] > 0:
+                sah.append(round(info["sahCost"] / info["sahCostAtBuild"], 4))
             tr.render_frame(st.frame_params(0, 0))
             tr.synchronize()
             t3 = time.perf_counter()
@@ -87,7 +95,8 @@ def main():
         return round(1e3 * sorted(v)[len(v) // 2], 3)
     print(json.dumps({"deformed_vertices": verts, "triangles": st.scene.num_triangles, "size": list(a.size), "frames": a.frames,
                       "kernel_bytes_min": min(moved), "kernel_bytes_max": max(moved), "deform_call_ms": med(t_def), "rebuild_ms": med(t_rebuild),
-                      "animated_frame_ms": med(t_anim), "node_only_frame_ms": med(t_nodes)}))
+                      "animated_frame_ms": med(t_anim), "node_only_frame_ms": med(t_nodes), "accel_update": a.accel_update,
+                      "accel_info": info, "sah_ratio_per_pose": sah}))
 
 
 if __name__ == "__main__":

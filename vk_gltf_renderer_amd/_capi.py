@@ -144,6 +144,11 @@ class MiPtDeformDesc(C.Structure):
                 ("jointMatrices", C.POINTER(f32)), ("morphWeights", C.POINTER(f32))]
 
 
+class MiPtAccelInfo(C.Structure):
+    _fields_ = [("mode", i32), ("lastUpdate", i32), ("rebuildCostRatio", f32), ("reserved", i32), ("builds", C.c_uint64), ("refits", C.c_uint64),
+                ("sahCostAtBuild", C.c_double), ("sahCost", C.c_double), ("trianglesMoved", C.c_uint64), ("refitBytes", C.c_uint64)]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -154,9 +159,12 @@ assert C.sizeof(MiGltfLight) == 64
 assert C.sizeof(MiGltfTextureInfo) == 32
 assert C.sizeof(MiGltfShadeMaterial) == 288
 assert C.sizeof(MiSceneFrameInfo) == 396
+assert C.sizeof(MiPtAccelInfo) == 64
 
-MI_PT_ABI_VERSION = 7  # include/mi_pt.h
+MI_PT_ABI_VERSION = 8  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
+MI_PT_ACCEL_REBUILD, MI_PT_ACCEL_REFIT, MI_PT_ACCEL_AUTO = 0, 1, 2
+MI_PT_ACCEL_LAST_BUILD, MI_PT_ACCEL_LAST_REFIT = 0, 1
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
@@ -267,6 +275,8 @@ PT_SYMBOLS = {
     "mi_pt_set_deformation": (i32, [VP, P(MiPtDeformDesc)]),
     "mi_pt_update_deformation": (i32, [VP, P(f32), P(f32), i32]),
     "mi_pt_read_vertices": (i32, [VP, i32, P(f32), P(f32), P(f32)]),
+    "mi_pt_set_accel_update": (i32, [VP, i32, f32]),
+    "mi_pt_get_accel_info": (i32, [VP, P(MiPtAccelInfo)]),
 }
 
 

@@ -49,6 +49,9 @@ void PathTracer::registerParameters(ParameterRegistry* r)
   r->add("ptPerformanceTarget", "Performance target [Interactive:0, Balanced:1, Quality:2, MaxQuality:3]", &m_performanceTarget);
   // (our own) traversal / shading counters of the C-ABI: slower kernels, printed as HEADLESS_COUNTERS at the end of a headless run
   r->add("ptCounters", "Collect traversal counters (MiPtStats; slower) and print them at the end of a headless run", &m_collectCounters);
+  // (our own) how animated frames update the acceleration structure: mi_pt_set_accel_update, applied right after mi_pt_create
+  r->add("accelUpdate", "Acceleration structure on animated frames [rebuild:0, refit:1, auto:2]", &m_accelUpdate);
+  r->add("accelRebuildRatio", "auto: rebuild once the refitted tree's SAH cost exceeds this x the cost after the last build", &m_accelRebuildRatio);
 }
 
 void PathTracer::onAttach(Resources& res, void* profiler)
@@ -73,6 +76,14 @@ void PathTracer::onSceneInvalidated(Resources& res)
   {
     m_error = mi_pt_last_error();
     fprintf(stderr, "PathTracer: mi_pt_create failed: %s\n", m_error.c_str());
+    m_pt = nullptr;
+    return;
+  }
+  if(m_accelUpdate != MI_PT_ACCEL_REBUILD && mi_pt_set_accel_update(m_pt, m_accelUpdate, m_accelRebuildRatio) != MI_PT_OK)
+  {
+    m_error = mi_pt_last_error();
+    fprintf(stderr, "PathTracer: mi_pt_set_accel_update failed: %s\n", m_error.c_str());
+    mi_pt_destroy(m_pt);
     m_pt = nullptr;
     return;
   }

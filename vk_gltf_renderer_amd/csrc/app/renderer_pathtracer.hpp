@@ -73,6 +73,8 @@ private:
   bool        m_adaptiveSampling{true};    // reference default: on, until --ptSamples is given (src/renderer_pathtracer.hpp:161)
   int         m_performanceTarget{1};      // Balanced
   bool        m_collectCounters{false};    // --ptCounters (our own): MiPtCreateOptions::collectCounters
+  int         m_accelUpdate{0};            // --accelUpdate (our own): MI_PT_ACCEL_REBUILD / REFIT / AUTO
+  float       m_accelRebuildRatio{1.5f};   // --accelRebuildRatio: AUTO's bound (mi_pt_set_accel_update)
   double      m_lastFrameDeviceMs{0.0};
   int         m_totalSamplesAccumulated{0};
   int         m_framesThisCall{1}, m_framesLastCall{1};

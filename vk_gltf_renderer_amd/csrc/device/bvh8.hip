@@ -37,6 +37,7 @@
 #include <functional>
 #include <vector>
 
+#include "bvh_refit.h"
 #include "pt_build.h"
 #include "pt_ticket.h"
 #include "pt_bvh.h"
@@ -45,20 +46,7 @@ namespace pt {
 
 namespace {
 
-struct Node8  // 80 bytes, see header
-{
-  float    p[3];
-  uint8_t  e[3];
-  uint8_t  imask;
-  uint32_t childBase;
-  uint32_t triBase;
-  uint16_t valid;      // two bits per slot: triangles of its leaf child (see header)
-  uint16_t reserved16;
-  uint32_t reserved32;
-  uint8_t  qlo[3][8];
-  uint8_t  qhi[3][8];
-};
-static_assert(sizeof(Node8) == 80, "Node8 must be 80 bytes");
+// (Node8, the 80-byte record: bvh_refit.h, shared with the refit)
 
 // Largest leaf child: 2 triangles.  Two bits of the node's 16-bit valid mask belong to
 // a slot, so a leaf child holds one or two triangles -- which is also what measured best when the mask had room for three and four
@@ -118,9 +106,7 @@ __device__ __forceinline__ float d_area(const DCand& c)
 // split[n][i]: how many of the i roots go to the left BVH2 child (-1: the subtree stays one child); split[n][1]: 0 = leaf, 1 = inner
 // node; split[n][0]: the left share of the inner node's eight.  Filled bottom-up (second arrival at a node solves it, like k_fit),
 // read top-down by the level kernels instead of the greedy opening.
-#ifndef MI_PT_DP_C_TRI
-#define MI_PT_DP_C_TRI (56.0f / 235.0f)  // a triangle test against a node visit, in vector instructions (round 3's counts; see LABNOTES.md section 3 for the round-4 sweep)
-#endif
+// (MI_PT_DP_C_TRI: bvh_refit.h, whose SAH cost of a refitted tree weighs triangles the same way)
 constexpr float DP_C_TRI = MI_PT_DP_C_TRI;
 struct DpTables
 {
@@ -357,7 +343,7 @@ __global__ void k_collapse_count(int numItems, const int* items, const float4* n
 // pass 2: the node records, the next level's work list, the triangle permutation
 __global__ void k_collapse_emit(int numItems, const int* items, const float4* nodes2, DpTables dp, uint32_t maxLeaf, const unsigned long long* counts,
                                 const unsigned long long* offsets, uint32_t levelStart, uint32_t nextLevelStart, uint32_t triLevelBase, Node8* nodes8,
-                                int* nextItems, uint32_t* perm, unsigned long long* totals)
+                                int* nextItems, uint32_t* perm, unsigned long long* totals, RefitBox* slotBox)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= numItems)
@@ -408,48 +394,16 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
   }
   Node8 N;
   memset(&N, 0, sizeof(N));
-  int ex[3];
-  for(int a = 0; a < 3; ++a)
   {
-    N.p[a]          = lo[a];
-    const float ext = hi[a] - lo[a];
-    ex[a]           = ext > 0.0f ? int(ceil(log2(double(ext) / 255.0))) : -126;
-    ex[a]           = max(-126, min(ex[a], 126));
-  }
-  for(int sl = 0; sl < 8; ++sl)
-    for(int a = 0; a < 3; ++a)
+    float    clo[3][8], chi[3][8];
+    uint32_t used = 0;
+    for(int sl = 0; sl < 8; ++sl)
     {
-      N.qlo[a][sl] = 255;  // empty slot: inverted box (and no valid bit)
-      N.qhi[a][sl] = 0;
+      const int c = candOfSlot[sl] < 0 ? 0 : candOfSlot[sl];
+      for(int a = 0; a < 3; ++a) { clo[a][sl] = cands[c].lo[a]; chi[a][sl] = cands[c].hi[a]; }
+      used |= candOfSlot[sl] < 0 ? 0u : 1u << sl;
     }
-  for(int a = 0; a < 3; ++a)
-  {
-    for(;;)
-    {
-      const float scale = ldexpf(1.0f, ex[a]);
-      bool        fits  = true;
-      for(int sl = 0; sl < 8 && fits; ++sl)
-      {
-        if(candOfSlot[sl] < 0)
-          continue;
-        const DCand& c  = cands[candOfSlot[sl]];
-        const double ql = floor((double(c.lo[a]) - double(N.p[a])) / double(scale));
-        const double qh = ceil((double(c.hi[a]) - double(N.p[a])) / double(scale));
-        int          il = int(fmax(0.0, fmin(255.0, ql))), ih = int(fmax(0.0, fmin(255.0, qh)));
-        while(il > 0 && __fmaf_rn(float(il), scale, N.p[a]) > c.lo[a])
-          --il;
-        while(ih < 255 && __fmaf_rn(float(ih), scale, N.p[a]) < c.hi[a])
-          ++ih;
-        if(__fmaf_rn(float(il), scale, N.p[a]) > c.lo[a] || __fmaf_rn(float(ih), scale, N.p[a]) < c.hi[a])
-          fits = false;
-        N.qlo[a][sl] = uint8_t(il);
-        N.qhi[a][sl] = uint8_t(ih);
-      }
-      if(fits || ex[a] >= 126)
-        break;
-      ++ex[a];
-    }
-    N.e[a] = uint8_t(ex[a] + 127);
+    quantiseNode8(N, lo, hi, clo, chi, used);  // (bvh_refit.h: the refit requantises with the same text)
   }
   // children: inner ones get consecutive node indices in slot order (they are the next level's items), leaf ones consecutive triangles
   const unsigned long long off = offsets[i];
@@ -471,18 +425,30 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
     else
     {
       N.valid |= uint16_t((tc >= 2u ? 3u : 1u) << (2 * sl));  // (tc <= 2: d_isInner opens anything larger)
-      // the (at most 4) triangles below c.ref, left to right
-      int stack[8], sp = 0;
-      stack[sp++] = c.ref;
+      // the (at most 4) triangles below c.ref, left to right; `slotBox`: the box each was filed under (its box in its BVH2 parent)
+      int stack[8], from[8], sp = 0;
+      stack[sp] = c.ref; from[sp++] = -1;
       while(sp > 0)
       {
-        const int r = stack[--sp];
+        --sp;
+        const int r = stack[sp], f = from[sp];
         if(r < 0)
+        {
+          if(slotBox)
+          {
+            RefitBox b;
+            if(f < 0)
+              for(int a = 0; a < 3; ++a) { b.lo[a] = c.lo[a]; b.hi[a] = c.hi[a]; }
+            else
+              d_childBox(nodes2, f >> 1, f & 1, b.lo, b.hi);
+            slotBox[triAt] = b;
+          }
           perm[triAt++] = uint32_t(~r);
+        }
         else
         {
-          stack[sp++] = d_childRef(nodes2, r, 1);
-          stack[sp++] = d_childRef(nodes2, r, 0);
+          stack[sp] = d_childRef(nodes2, r, 1); from[sp++] = 2 * r + 1;
+          stack[sp] = d_childRef(nodes2, r, 0); from[sp++] = 2 * r;
         }
       }
     }
@@ -530,6 +496,8 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
       if(!(ok = check(hipMalloc(&itemsA, sizeof(int) * size_t(numInner)), "alloc level items"))) break;
       if(!(ok = check(hipMalloc(&itemsB, sizeof(int) * size_t(numInner)), "alloc level items"))) break;
       if(!(ok = check(hipMalloc(&dPerm, sizeof(uint32_t) * size_t(n)), "alloc perm"))) break;
+      if(opt.keepRefit)  // the refit data (bvh_refit.hip): the box each triangle slot was filed under
+        if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.slotBox), sizeof(RefitBox) * size_t(n)), "alloc refit slot boxes"))) break;
       if(!(ok = check(hipMalloc(&counts, sizeof(unsigned long long) * size_t(numInner)), "alloc counts"))) break;
       if(!(ok = check(hipMalloc(&offsets, sizeof(unsigned long long) * size_t(numInner)), "alloc offsets"))) break;
       if(!(ok = check(hipMalloc(&totals, sizeof(unsigned long long)), "alloc totals"))) break;
@@ -560,7 +528,8 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
         hipLaunchKernelGGL(k_collapse_count, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA, b2.nodes, dp, maxLeaf, counts);
         if(!(ok = check(hipcub::DeviceScan::ExclusiveSum(scanTemp, scanBytes, counts, offsets, int(levelCount), stream), "scan"))) break;
         hipLaunchKernelGGL(k_collapse_emit, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA, b2.nodes, dp, maxLeaf, counts, offsets, levelStart,
-                           levelStart + levelCount, trisPlaced, dNodes, itemsB, dPerm, totals);
+                           levelStart + levelCount, trisPlaced, dNodes, itemsB, dPerm, totals, out.slotBox);
+        out.levels.push_back(levelStart);
         unsigned long long t = 0;
         if(!(ok = check(hipGetLastError(), "collapse kernels"))) break;
         if(!(ok = check(hipMemcpyAsync(&t, totals, sizeof(t), hipMemcpyDeviceToHost, stream), "read level totals"))) break;
@@ -587,6 +556,9 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
       }
       if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.nodes), sizeof(Node8) * size_t(numNodes8)), "alloc BVH8 nodes"))) break;
       if(!(ok = check(hipMemcpyAsync(out.nodes, dNodes, sizeof(Node8) * size_t(numNodes8), hipMemcpyDeviceToDevice, stream), "copy BVH8 nodes"))) break;
+      out.levels.push_back(numNodes8);
+      if(opt.keepRefit)  // (filled by the first pass of k_refit_level, which the caller runs over the new tree)
+        if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.nodeBox), sizeof(RefitBox) * size_t(numNodes8)), "alloc refit node boxes"))) break;
       if(!(ok = check(hipMalloc(&out.tris, sizeof(DevTri) * size_t(n)), "alloc BVH8 triangles"))) break;
       hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm, b2.tris, out.tris);
       ok = check(hipGetLastError(), "k_reorder_tris") && check(hipStreamSynchronize(stream), "sync");
@@ -598,6 +570,8 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
     {
       if(out.nodes) (void)hipFree(out.nodes);
       if(out.tris) (void)hipFree(out.tris);
+      if(out.slotBox) (void)hipFree(out.slotBox);
+      if(out.nodeBox) (void)hipFree(out.nodeBox);
       out = Bvh8Output();
       return false;
     }

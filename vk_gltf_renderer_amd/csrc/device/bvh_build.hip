@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "bvh_refit.h"
 #include "bvh_reinsert.h"
 #include "bvh_split.h"
 #include "pt_build.h"
@@ -65,37 +66,9 @@ __global__ void k_tri_setup(BuildTables T, uint32_t numTris, DevTri* tris, float
     const int               rnode = T.entryNode[a];
     const uint32_t          t     = g - T.nodeTriOffset[a];
     const MiGltfRenderNode& rn    = T.nodes[rnode];
-    const DevPrim&          rp    = T.prims[rn.renderPrimID];
-    const uint32_t          i0 = rp.indices[3 * t], i1 = rp.indices[3 * t + 1], i2 = rp.indices[3 * t + 2];
-    f3 p0 = mulPoint(rn.objectToWorld, mk3(rp.positions + 3 * size_t(i0)));
-    f3 p1 = mulPoint(rn.objectToWorld, mk3(rp.positions + 3 * size_t(i1)));
-    f3 p2 = mulPoint(rn.objectToWorld, mk3(rp.positions + 3 * size_t(i2)));
-    // Vertex buffers and instance matrices are untrusted bytes.  A triangle with a NaN, an infinity or a coordinate whose square
-    // overflows would poison the scene bounds, the Morton keys and the surface areas the clustering compares; it becomes a point at
-    // the origin instead -- zero area, so no ray hits it -- and the rest of the scene builds and renders as if it were not there.
-    {
-      const float big = 1.0e18f;
-      const bool  ok  = fabsf(p0.x) < big && fabsf(p0.y) < big && fabsf(p0.z) < big && fabsf(p1.x) < big && fabsf(p1.y) < big && fabsf(p1.z) < big
-                      && fabsf(p2.x) < big && fabsf(p2.y) < big && fabsf(p2.z) < big;  // false for NaN as well
-      if(!ok)
-        p0 = p1 = p2 = mk3(0.0f);
-    }
-    f3 e1 = p1 - p0, e2 = p2 - p0;
-    DevTri tri;
-    tri.a   = make_float4(p0.x, p0.y, p0.z, __int_as_float(rnode));
-    tri.b   = make_float4(e1.x, e1.y, e1.z, __int_as_float(int(t)));
-    // (a triangle the load-time classification found opaque -- DevPrim::opaqueTriangles -- counts as FORCE_OPAQUE like an opaque instance)
-    tri.c   = make_float4(e2.x, e2.y, e2.z, __uint_as_float(uint32_t(T.instFlags[rnode]) | (t < rp.opaqueTriangles ? uint32_t(INST_FORCE_OPAQUE) : 0u)));
+    DevTri                  tri;
+    worldTriangle(rn, T.prims[rn.renderPrimID], rnode, t, uint32_t(T.instFlags[rnode]), tri, lo, hi);  // (bvh_refit.h: the refit rewrites it with the same text)
     tris[g] = tri;
-    // bounds from the same p0 + e arithmetic the intersector sees
-    f3 q1 = p0 + e1, q2 = p0 + e2;
-    lo[0] = fminf(p0.x, fminf(q1.x, q2.x)); hi[0] = fmaxf(p0.x, fmaxf(q1.x, q2.x));
-    lo[1] = fminf(p0.y, fminf(q1.y, q2.y)); hi[1] = fmaxf(p0.y, fmaxf(q1.y, q2.y));
-    lo[2] = fminf(p0.z, fminf(q1.z, q2.z)); hi[2] = fmaxf(p0.z, fmaxf(q1.z, q2.z));
-    // include the true vertices too (p0+e may round inward)
-    lo[0] = fminf(lo[0], fminf(p1.x, p2.x)); hi[0] = fmaxf(hi[0], fmaxf(p1.x, p2.x));
-    lo[1] = fminf(lo[1], fminf(p1.y, p2.y)); hi[1] = fmaxf(hi[1], fmaxf(p1.y, p2.y));
-    lo[2] = fminf(lo[2], fminf(p1.z, p2.z)); hi[2] = fmaxf(hi[2], fmaxf(p1.z, p2.z));
     boxLo[g] = make_float4(lo[0], lo[1], lo[2], 0.0f);
     boxHi[g] = make_float4(hi[0], hi[1], hi[2], 0.0f);
   }

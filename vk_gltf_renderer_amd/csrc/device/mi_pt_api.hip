@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mi_pt.h"
+#include "bvh_refit.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_deform.h"
@@ -220,7 +221,24 @@ struct MiPt
   int                           deformJointCount = 0, deformWeightCount = 0;
   uint32_t                      deformBlocks = 0;
   bool                          deformSet = false;
+  std::vector<int>              deformPrimIDs;  // the render primitives the deformation tables deform
   int                           bvhBuilder = 0;
+  // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
+  int                           accelMode = MI_PT_ACCEL_REBUILD;
+  float                         accelRatio = 1.5f;
+  int                           lastUpdate = MI_PT_ACCEL_LAST_BUILD;
+  bool                          switchBuild = false;  // the build of mi_pt_set_accel_update is running
+  bool                          refitCapable = false; // the last build went through the device collapse: a build in REFIT / AUTO mode keeps refit data
+  uint64_t                      accelRefits = 0, trianglesMoved = 0;
+  double                        sahAtBuild = 0.0, sahNow = 0.0;
+  DevBuf<pt::RefitBox>          refitSlotBox, refitBuiltBox, refitNodeBox;  // per slot: current box, box the build filed; per node: its box
+  DevBuf<float>                 refitSah;         // per node: its SAH term
+  DevBuf<double>                refitSahPartial;  // the cost reduction (pt::REFIT_SAH_PARTIALS + 1)
+  DevBuf<uint8_t>               refitDirty;       // per render node: pt::REFIT_CLEAN / MOVED / HOME
+  std::vector<uint32_t>         refitLevels;      // level starts of the node array + the node count; empty = no refit data
+  std::vector<MiGltfRenderNode> builtNodes;       // the node table of the last full build
+  std::vector<uint8_t>          primDirty;        // per render primitive: deformed since the last acceleration update ...
+  std::vector<uint8_t>          primDeformed;     // ... since the last full build
   // frame state
   int                     width = 0, height = 0;
   int                     tileRank = 0, tileWorld = 1, tileSize = 64;
@@ -478,6 +496,8 @@ hipEvent_t getEvent(MiPt* pt, size_t& cursor)
 // build (mi_pt_create; reference: SceneRtx BLAS + TLAS build, src/gltf_scene_rtx.cpp:173-385) and the transform / visibility
 // updates of animated scenes (mi_pt_update_render_nodes; reference: TLAS update, src/gltf_scene_transform_vk.cpp:534-639) alike.
 int buildAccelerationUnguarded(MiPt* pt);
+void dropAcceleration(MiPt* pt);
+void releaseRefitData(MiPt* pt);
 // A failed (re)build must not leave the scene descriptor pointing at freed or half-built arrays: mi_pt_update_render_nodes runs
 // this once per animated frame, and the next mi_pt_render_frame would walk them.  On any error the instance falls back to an
 // EMPTY structure (frames render the environment only) and the error is returned to the caller.
@@ -491,9 +511,17 @@ int buildAcceleration(MiPt* pt)
     (void)hipDeviceSynchronize();
     fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "rebuild", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   }
+  pt->lastUpdate = MI_PT_ACCEL_LAST_BUILD;
   if(rc != MI_PT_OK)
+    dropAcceleration(pt);
+  return rc;
+}
+// The state a failed build or refit leaves: an EMPTY structure, no refit data, the error message kept.
+void dropAcceleration(MiPt* pt)
+{
   {
     const std::string why = g_lastError;  // (the frees below must not disturb the message)
+    releaseRefitData(pt);
     if(pt->bvhNodes) (void)hipFree(pt->bvhNodes);
     if(pt->bvhTris) (void)hipFree(pt->bvhTris);
     if(pt->bvh8Nodes) (void)hipFree(pt->bvh8Nodes);
@@ -506,16 +534,13 @@ int buildAcceleration(MiPt* pt)
     pt->sceneDevDirty = true;
     g_lastError = why;
   }
-  return rc;
 }
-int buildAccelerationUnguarded(MiPt* pt)
+// Per render node: its material's instance flags, and INST_FLIP_FACING for a mirroring matrix (the triangle records carry them); sets the
+// scene-wide material summaries (hasAlpha, ...) on the way.  The build and the refit both take them from here.
+std::vector<uint8_t> instanceFlags(MiPt* pt)
 {
-  const int numNodes = int(pt->hostNodes.size()), numMaterials = int(pt->matInstFlags.size()), numPrims = int(pt->primTriangles.size());
-  std::vector<uint8_t>  flags(size_t(std::max(numNodes, 1)), 0);
-  std::vector<uint32_t> triOffset;
-  std::vector<int32_t>  entryNode;
-  uint64_t              totalTris = 0;
-  triOffset.push_back(0);
+  const int            numNodes = int(pt->hostNodes.size()), numMaterials = int(pt->matInstFlags.size());
+  std::vector<uint8_t> flags(size_t(std::max(numNodes, 1)), 0);
   pt->hasAlpha = pt->hasAlphaTest = pt->hasTransmissive = pt->hasVolumeScatter = false;
   pt->simpleMaterials = true;
   for(int n = 0; n < numNodes; ++n)
@@ -538,6 +563,39 @@ int buildAccelerationUnguarded(MiPt* pt)
     if(det < 0.0f)
       f |= pt::INST_FLIP_FACING;
     flags[size_t(n)] = uint8_t(f);
+  }
+  return flags;
+}
+
+void releaseRefitData(MiPt* pt)
+{
+  pt->refitSlotBox.release(); pt->refitBuiltBox.release(); pt->refitNodeBox.release(); pt->refitSah.release(); pt->refitSahPartial.release();
+  pt->refitDirty.release();
+  pt->refitLevels.clear();
+  pt->sahAtBuild = pt->sahNow = 0.0;
+}
+
+// The SAH cost of the resident tree from the refit data (the node boxes and terms k_refit_level wrote), read back: one small copy
+int readSahCost(MiPt* pt, double& cost)
+{
+  pt::launchSahCost(pt->refitSah.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->refitNodeBox.ptr, pt->refitSahPartial.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(&cost, pt->refitSahPartial.ptr + pt::REFIT_SAH_PARTIALS, sizeof(double), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+
+int buildAccelerationUnguarded(MiPt* pt)
+{
+  releaseRefitData(pt);
+  const int numNodes = int(pt->hostNodes.size()), numPrims = int(pt->primTriangles.size());
+  std::vector<uint8_t>  flags = instanceFlags(pt);
+  std::vector<uint32_t> triOffset;
+  std::vector<int32_t>  entryNode;
+  uint64_t              totalTris = 0;
+  triOffset.push_back(0);
+  for(int n = 0; n < numNodes; ++n)
+  {
+    const MiGltfRenderNode& rn = pt->hostNodes[size_t(n)];
     if(!pt->hostVisible.empty() && !pt->hostVisible[size_t(n)])
       continue;  // invisible nodes get no geometry (reference: src/gltf_scene_rtx.cpp:319-323)
     if(rn.renderPrimID < 0 || rn.renderPrimID >= numPrims || pt->primTriangles[size_t(rn.renderPrimID)] == 0)
@@ -557,6 +615,7 @@ int buildAccelerationUnguarded(MiPt* pt)
   if(pt->bvhTris) (void)hipFree(pt->bvhTris);
   if(pt->bvh8Nodes) (void)hipFree(pt->bvh8Nodes);
   pt->bvhNodes = nullptr; pt->bvhTris = nullptr; pt->bvh8Nodes = nullptr;
+  pt->refitCapable = false;
   if(pt->accelBuilds++ == pt->sw.failBuildAt && pt->sw.failBuildAt > 0)  // test hook (armed at mi_pt_create): this REbuild fails after the old structure is gone
     return fail(MI_PT_ERR_HIP, "BVH build failed: MI_PT_DIAG_FAIL_BUILD");
   {
@@ -566,7 +625,10 @@ int buildAccelerationUnguarded(MiPt* pt)
     HIP_TRY(dEntry.upload(entryNode.data(), entryNode.size()));
     pt::BvhBuildInput in{pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, dOffset.ptr, dEntry.ptr, int(entryNode.size()), uint32_t(totalTris)};
     in.karrasTopology = (pt->bvhBuilder & 2) != 0;
-    in.reinsertPasses = pt->accelBuilds == 1 ? pt->sw.reinsert : pt->sw.reinsertUpdate;  // (accelBuilds counts this build already)
+    // (accelBuilds counts this build already.)  The build of a switch to REFIT / AUTO makes the tree the updates then refit: it runs the scene
+    // build's passes, once, at a moment the caller chose.  The fallback and AUTO rebuilds of those modes happen during playback and run the
+    // update's passes like every other rebuild -- 16 passes would add ~160 ms to a 17-ms rebuild at 2.8 M triangles (RunSwitches::reinsertUpdate)
+    in.reinsertPasses = (pt->accelBuilds == 1 || pt->switchBuild) ? pt->sw.reinsert : pt->sw.reinsertUpdate;
     in.reinsertRounds = pt->sw.reinsertRounds;
     in.splitFactor    = pt->sw.splitFactor;
     in.splitMaxDepth  = pt->sw.splitMaxDepth;
@@ -593,7 +655,13 @@ int buildAccelerationUnguarded(MiPt* pt)
       pt::Bvh8Output b8;
       pt::Bvh8Options b8opt;
       b8opt.sahCollapse = !pt->sw.collapseGreedy; b8opt.hostCollapse = pt->sw.hostCollapse;
-      if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
+      b8opt.keepRefit   = pt->accelMode != MI_PT_ACCEL_REBUILD;
+      pt->refitCapable  = !pt->sw.hostCollapse && bo.numNodes > 0;  // (a one-reference scene takes the host collapse: bvh8.hip)
+      const bool built  = pt::buildBvh8(bo, b8, nullptr, err, b8opt);
+      // the refit data, owned from here on (the host collapse keeps none: its updates rebuild)
+      pt->refitSlotBox.ptr = b8.slotBox; pt->refitSlotBox.count = b8.slotBox ? b8.numTris : 0;
+      pt->refitNodeBox.ptr = b8.nodeBox; pt->refitNodeBox.count = b8.nodeBox ? b8.numNodes : 0;
+      if(!built)
       {
         if(b8.nodes)
           (void)hipFree(b8.nodes);
@@ -616,6 +684,33 @@ int buildAccelerationUnguarded(MiPt* pt)
         HIP_TRY(pt->bvh8Planes.alloc(size_t(b8.numNodes) * 48));
         pt::launchBvh8Planes(b8.nodes, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
         HIP_TRY(hipGetLastError());
+      }
+      if(b8.slotBox && b8.nodeBox)
+      {
+        // the refit data: the boxes the build filed the references under stay as they are (REFIT_HOME), the SAH cost of the tree as built.
+        // The nodes are requantised once from the unions of those boxes (a BVH2 box may be looser than the union below it): the tree an
+        // update refits back to the build's pose is then this one, byte for byte.
+        HIP_TRY(pt->refitBuiltBox.alloc(b8.numTris));
+        HIP_TRY(hipMemcpy(pt->refitBuiltBox.ptr, b8.slotBox, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
+        HIP_TRY(pt->refitSah.alloc(b8.numNodes));
+        HIP_TRY(pt->refitSahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
+        HIP_TRY(pt->refitDirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
+        pt::launchRefitLevels(b8.nodes, b8.levels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+        if(pt->bvh8Planes.ptr)
+          pt::launchBvh8Planes(b8.nodes, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
+        HIP_TRY(hipGetLastError());
+        if(int rc = readSahCost(pt, pt->sahAtBuild))
+          return rc;
+        pt->sahNow      = pt->sahAtBuild;
+        pt->refitLevels = b8.levels;
+        pt->builtNodes  = pt->hostNodes;
+        pt->primDirty.assign(pt->primTriangles.size(), 0);
+        pt->primDeformed.assign(pt->primTriangles.size(), 0);
+      }
+      else
+      {
+        pt->refitSlotBox.release();
+        pt->refitNodeBox.release();
       }
     }
   }
@@ -642,6 +737,77 @@ int buildAccelerationUnguarded(MiPt* pt)
   }
   pt->sceneDevDirty = true;
   return MI_PT_OK;
+}
+
+// The refit of an update: `moved` per render node = its matrices changed.  The triangle records and slot boxes of what moved or deformed
+// (k_refit_tris: REFIT_HOME for geometry back in the pose of the last build, whose boxes are then the ones it was built with -- except a
+// primitive deformed since that build: deformed vertices are not compared with the built ones, so its pre-split references keep their
+// whole triangles' boxes until the next build, conservative and the same image), every node
+// level by level, the packet walk's planes, the SAH cost.  AUTO rebuilds when that cost exceeds the ratio x the cost at the last build.
+int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved)
+{
+  static const bool    buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  const auto           t0          = std::chrono::steady_clock::now();
+  const size_t         numNodes = pt->hostNodes.size(), numPrims = pt->primTriangles.size();
+  std::vector<uint8_t> dirty(std::max<size_t>(numNodes, 1), pt::REFIT_CLEAN);
+  uint64_t             movedTris = 0;
+  for(size_t n = 0; n < numNodes; ++n)
+  {
+    const MiGltfRenderNode& rn       = pt->hostNodes[n];
+    const bool              ownsPrim = rn.renderPrimID >= 0 && size_t(rn.renderPrimID) < numPrims;
+    if(!moved[n] && !(ownsPrim && pt->primDirty[size_t(rn.renderPrimID)]))
+      continue;
+    const bool home = memcmp(rn.objectToWorld, pt->builtNodes[n].objectToWorld, sizeof(float) * 32) == 0 && !(ownsPrim && pt->primDeformed[size_t(rn.renderPrimID)]);
+    dirty[n]        = home ? pt::REFIT_HOME : pt::REFIT_MOVED;
+    if(ownsPrim && (pt->hostVisible.empty() || pt->hostVisible[n]))
+      movedTris += pt->primTriangles[size_t(rn.renderPrimID)];
+  }
+  const std::vector<uint8_t> flags = instanceFlags(pt);
+  const int                  rc    = [&]() -> int {
+    HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * numNodes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris, pt->refitSlotBox.ptr,
+                        uint32_t(pt->scene.numTris), nullptr);
+    pt::launchRefitLevels(pt->bvh8Nodes, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+    if(pt->bvh8Planes.ptr)
+      pt::launchBvh8Planes(pt->bvh8Nodes, uint32_t(pt->scene.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    if(int e = readSahCost(pt, pt->sahNow))
+      return e;
+    HIP_TRY(hipDeviceSynchronize());
+    return MI_PT_OK;
+  }();
+  if(rc != MI_PT_OK)
+  {
+    dropAcceleration(pt);
+    return rc;
+  }
+  std::fill(pt->primDirty.begin(), pt->primDirty.end(), uint8_t(0));
+  pt->sceneDevDirty = true;
+  if(buildTiming)
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "refit", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  if(pt->accelMode == MI_PT_ACCEL_AUTO && pt->sahNow > double(pt->accelRatio) * pt->sahAtBuild)
+    return buildAcceleration(pt);
+  ++pt->accelRefits;
+  pt->lastUpdate     = MI_PT_ACCEL_LAST_REFIT;
+  pt->trianglesMoved = movedTris;
+  return MI_PT_OK;
+}
+
+// An update of the node table or of the deformed geometry: a refit when the mode and the resident structure allow one and the update
+// keeps the topology (`sameTopology`: primitives, materials and visibility unchanged), a full build otherwise.
+int updateAcceleration(MiPt* pt, bool sameTopology, const std::vector<uint8_t>& moved)
+{
+  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refitLevels.empty() && pt->bvh8Nodes && pt->wide)
+    return refitAcceleration(pt, moved);
+  return buildAcceleration(pt);
+}
+
+uint64_t refitBytes(const MiPt* pt)
+{
+  auto bytes = [](const auto& b) { return uint64_t(b.count) * sizeof(*b.ptr); };
+  return bytes(pt->refitSlotBox) + bytes(pt->refitBuiltBox) + bytes(pt->refitNodeBox) + bytes(pt->refitSah) + bytes(pt->refitSahPartial) + bytes(pt->refitDirty);
 }
 
 }  // namespace
@@ -976,12 +1142,23 @@ int mi_pt_update_render_nodes(MiPt* pt, const MiGltfRenderNode* renderNodes, int
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_render_nodes: render node references a material beyond the table");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still walk the old structure
+  // what changed: matrices only (a refit may follow), or primitives, materials or visibility (a rebuild)
+  bool                 sameTopology = true;
+  std::vector<uint8_t> moved(size_t(numRenderNodes), 0);
+  for(int n = 0; n < numRenderNodes; ++n)
+  {
+    const MiGltfRenderNode &was = pt->hostNodes[size_t(n)], &now = renderNodes[n];
+    const bool              visWas = pt->hostVisible.empty() || pt->hostVisible[size_t(n)], visNow = !renderNodeVisible || renderNodeVisible[n];
+    if(was.materialID != now.materialID || was.renderPrimID != now.renderPrimID || visWas != visNow)
+      sameTopology = false;
+    moved[size_t(n)] = memcmp(was.objectToWorld, now.objectToWorld, sizeof(float) * 32) != 0;
+  }
   pt->hostNodes.assign(renderNodes, renderNodes + numRenderNodes);
   if(renderNodeVisible)
     pt->hostVisible.assign(renderNodeVisible, renderNodeVisible + numRenderNodes);
   else
     pt->hostVisible.clear();
-  return buildAcceleration(pt);
+  return updateAcceleration(pt, sameTopology, moved);
 }
 
 int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights)
@@ -1007,6 +1184,7 @@ static void releaseDeformation(MiPt* pt)
   pt->deformJointCount = pt->deformWeightCount = 0;
   pt->deformBlocks = 0;
   pt->deformSet    = false;
+  pt->deformPrimIDs.clear();
 }
 
 int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
@@ -1142,6 +1320,8 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
   pt->deformWeightCount = desc->numMorphWeights;
   pt->deformBlocks      = uint32_t(blockTask.size());
   pt->deformSet         = true;
+  for(int k = 0; k < desc->numPrims; ++k)
+    pt->deformPrimIDs.push_back(desc->prims[k].renderPrimID);
   return MI_PT_OK;
 }
 
@@ -1187,9 +1367,55 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
   HIP_TRY(hipDeviceSynchronize());
   if(buildTiming)
     fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "deform", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  for(int id : pt->deformPrimIDs)  // (what the next acceleration update refits; sized by a build that kept refit data)
+    if(size_t(id) < pt->primDirty.size())
+      pt->primDirty[size_t(id)] = pt->primDeformed[size_t(id)] = 1;
   if(flags & MI_PT_DEFORM_DEFER_BUILD)
     return MI_PT_OK;
-  return buildAcceleration(pt);
+  return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
+}
+
+int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_update: null instance");
+  if(mode != MI_PT_ACCEL_REBUILD && mode != MI_PT_ACCEL_REFIT && mode != MI_PT_ACCEL_AUTO)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_update: unknown mode " + std::to_string(mode));
+  if(!std::isfinite(rebuildCostRatio) || rebuildCostRatio < 1.0f)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_update: the rebuild cost ratio must be finite and at least 1");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still walk the structure
+  pt->accelMode  = mode;
+  pt->accelRatio = rebuildCostRatio;
+  if(mode == MI_PT_ACCEL_REBUILD)
+  {
+    releaseRefitData(pt);
+    return MI_PT_OK;
+  }
+  if(!pt->refitLevels.empty() || !pt->refitCapable)
+    return MI_PT_OK;  // (refit data held already, or the structure can never keep any -- BVH2 walk, host collapse, empty or one-reference scene: no build)
+  pt->switchBuild = true;
+  const int rc    = buildAcceleration(pt);
+  pt->switchBuild = false;
+  return rc;
+}
+
+int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* out)
+{
+  if(!pt || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_accel_info: null argument");
+  memset(out, 0, sizeof(*out));
+  out->mode             = pt->accelMode;
+  out->lastUpdate       = pt->lastUpdate;
+  out->rebuildCostRatio = pt->accelRatio;
+  out->builds           = uint64_t(std::max(pt->accelBuilds, 0));
+  out->refits           = pt->accelRefits;
+  out->sahCostAtBuild   = pt->sahAtBuild;
+  out->sahCost          = pt->sahNow;
+  out->trianglesMoved   = pt->trianglesMoved;
+  out->refitBytes       = refitBytes(pt);
+  return MI_PT_OK;
 }
 
 int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* normals, float* tangents)
@@ -1885,7 +2111,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   uint64_t scene = bytes(pt->materials) + bytes(pt->texInfos) + bytes(pt->nodes) + bytes(pt->prims) + bytes(pt->lights) + bytes(pt->textures) + bytes(pt->texels) + bytes(pt->texQuads)
                    + bytes(pt->geometry) + bytes(pt->instFlags) + bytes(pt->srgbLut) + bytes(pt->envPixels) + bytes(pt->envAccel) + bytes(pt->alphaTris)
                    + bytes(pt->shadeTris) + bytes(pt->texRefs) + bytes(pt->coreTex) + bytes(pt->bvh8Planes) + bytes(pt->deformPool) + bytes(pt->deformTasks)
-                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights);
+                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights) + refitBytes(pt);
   // the acceleration structure is raw allocations: 64-B BVH2 nodes or 80-B BVH8 nodes + 48-B triangle records
   scene += uint64_t(pt->staticStats.bvhNodeCount) * pt->staticStats.bvhNodeBytes + uint64_t(sc.numTris) * sizeof(pt::DevTri);
   const uint64_t pathState = bytes(pt->pathArrays) + bytes(pt->optThroughput) + bytes(pt->optMisc) + bytes(pt->optMedium) + bytes(pt->optPixelSum) + bytes(pt->optGuides)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "pt_scene.h"
 
@@ -36,18 +37,37 @@ struct BvhBuildOutput
 };
 bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, std::string& err);
 
+struct RefitBox;  // bvh_refit.h
+
 // 8-wide compressed BVH collapsed from the BVH2 above (bvh8.hip)
 struct Bvh8Output
 {
   uint4*   nodes    = nullptr;  // device, 5 uint4 per node
   DevTri*  tris     = nullptr;  // device, node order (triangles of a node's leaf children are contiguous)
   uint32_t numNodes = 0, numTris = 0;
+  // the refit data (Bvh8Options::keepRefit, device collapse only; the caller owns and frees them): per triangle slot the box the builder
+  // filed that reference under, per node room for its box (left for k_refit_level to fill), and the start of every level of the
+  // breadth-first node array (+ numNodes at the end)
+  RefitBox*             nodeBox = nullptr;
+  RefitBox*             slotBox = nullptr;
+  std::vector<uint32_t> levels;
 };
 struct Bvh8Options  // (MI_PT_COLLAPSE / MI_PT_HOST_COLLAPSE, read and validated once in mi_pt_create: RunSwitches)
 {
   bool sahCollapse  = true;   // SAH-optimal dynamic programme (default) | greedy by surface area
   bool hostCollapse = false;  // the greedy host collapse (A/B reference of the device one)
+  bool keepRefit    = false;  // also return the refit data (mi_pt_set_accel_update: REFIT / AUTO)
 };
+
+// In-place refit of the 8-wide BVH (bvh_refit.hip).  k_refit_tris: the triangle records and slot boxes of the slots whose render node's
+// byte in `dirty` is not REFIT_CLEAN (bvh_refit.h); k_refit_level, one launch per level, deepest first: every node requantised from its
+// children's boxes, its box into nodeBox and its SAH term into sahTerm; the SAH cost of the tree from those terms, in a fixed reduction order
+// (bit-reproducible).
+void launchRefitTris(const MiGltfRenderNode* nodes, const DevPrim* prims, const uint8_t* instFlags, const uint8_t* dirty, const RefitBox* builtBox,
+                     DevTri* tris, RefitBox* slotBox, uint32_t numTris, hipStream_t s);
+void launchRefitLevels(uint4* nodes, const std::vector<uint32_t>& levels, const RefitBox* slotBox, RefitBox* nodeBox, float* sahTerm, hipStream_t s);
+constexpr int REFIT_SAH_PARTIALS = 1024;  // partial sums of the cost reduction (the `partial` array: this + 1 doubles)
+void launchSahCost(const float* sahTerm, uint32_t numNodes, const RefitBox* nodeBox, double* partial, hipStream_t s);  // the cost -> partial[REFIT_SAH_PARTIALS]
 bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, std::string& err, const Bvh8Options& opt = Bvh8Options());
 
 }  // namespace pt

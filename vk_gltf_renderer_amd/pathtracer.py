@@ -205,6 +205,20 @@ class PathTracer:
         jm, mw = keep(joint_matrices), keep(morph_weights)
         _check_pt(self._l.mi_pt_update_deformation(self._p, ptr(jm), ptr(mw), capi.MI_PT_DEFORM_DEFER_BUILD if defer_build else 0))
 
+    ACCEL_MODES = {"rebuild": 0, "refit": 1, "auto": 2}
+
+    def set_accel_update(self, mode, rebuild_cost_ratio=1.5):
+        """How animated frames update the acceleration structure (mi_pt_set_accel_update): "rebuild" / 0 (default), "refit" / 1 (the 8-wide
+        tree refitted in place) or "auto" / 2 (refit while its SAH cost stays within rebuild_cost_ratio x the cost after the last build)."""
+        m = self.ACCEL_MODES[mode] if isinstance(mode, str) else int(mode)
+        _check_pt(self._l.mi_pt_set_accel_update(self._p, m, C.c_float(rebuild_cost_ratio)))
+
+    def accel_info(self):
+        """mi_pt_get_accel_info as a dict: mode, lastUpdate, builds, refits, SAH cost at the last build and now, triangles moved, refit bytes."""
+        a = capi.MiPtAccelInfo()
+        _check_pt(self._l.mi_pt_get_accel_info(self._p, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in a._fields_ if n != "reserved"}
+
     def read_vertices(self, prim):
         """The resident streams of render primitive `prim`: (positions (V, 3), normals (V, 3) or None, tangents (V, 4) or None)."""
         p = self._scene.desc.contents.renderPrimitives[prim]
