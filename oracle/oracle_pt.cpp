@@ -600,7 +600,7 @@ void brdf_ggx_smith_eval(BsdfEvaluateData& d, const PbrMaterial& mat, int lobe, 
     return absorbEval(d);
   float3 h   = normalize(d.k1 + d.k2);
   float  nh = dot(mat.N, h), k1h = dot(d.k1, h), k2h = dot(d.k2, h);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return absorbEval(d);
   float3 h0 = float3(dot(mat.T, h), dot(mat.B, h), nh);
   d.pdf     = hvd_ggx_eval(float2(1.0f / mat.roughness.x, 1.0f / mat.roughness.y), h0);
@@ -648,7 +648,7 @@ void btdf_ggx_smith_eval(BsdfEvaluateData& d, const PbrMaterial& mat, float3 tin
   bool   backside = (dot(d.k2, mat.Ng) < 0.0f);
   float3 h        = compute_half_vector(d.k1, d.k2, mat.N, ior, nk2, backside, thin);
   float  nh = dot(mat.N, h), k1h = dot(d.k1, h), k2h = dot(d.k2, h) * (backside ? -1.0f : 1.0f);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return absorbEval(d);
   float fr;
   if(!backside)
@@ -726,7 +726,7 @@ void brdf_sheen_eval(BsdfEvaluateData& d, const PbrMaterial& mat)
   float  nk1 = std::fabs(dot(d.k1, mat.N)), nk2 = std::fabs(dot(d.k2, mat.N));
   float3 h   = normalize(d.k1 + d.k2);
   float  nh = dot(mat.N, h), k1h = dot(d.k1, h), k2h = dot(d.k2, h);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return absorbEval(d);
   float invRoughness = 1.0f / (mat.sheenRoughness * mat.sheenRoughness);
   d.pdf              = hvd_sheen_eval(invRoughness, nh);
@@ -1464,13 +1464,16 @@ inline bool intersectBox(float3 bmin, float3 bmax, float3 org, float3 invDir, fl
   // conservative: widen by a few ulps so that no triangle accepted by intersectTri is ever missed
   return tn <= tf * 1.0000004f + 1e-30f;
 }
+// The walk's reciprocal direction: IEEE divisions (the device's makeRaySetup, pt_bvh.h, gives the same bits wherever |dir| >= 1e-30; below it the
+// device substitutes +-1e-30, here the quotient overflows to +-inf -- either way the slab of that axis is decided by the origin alone).
+inline float3 rayInvDir(float3 dir) { return float3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z); }
 // Visit every triangle whose box test passes; `visit` may shrink tmax by returning a new value.
 template <typename F>
 inline void traverse(const Accel& A, float3 org, float3 dir, float tmax, F&& visit, uint64_t* nodeCount = nullptr)
 {
   if(A.tris.empty())
     return;
-  float3 invDir(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+  float3 invDir = rayInvDir(dir);
   int    stack[128];
   int    sp    = 0;
   stack[sp++]  = 0;
@@ -3006,6 +3009,28 @@ float oracle_ray_cone_footprint(float width, float spreadAngle, float hitT, cons
   RayCone c;
   c.width = width; c.spreadAngle = spreadAngle;
   return rayConeWorldFootprint(c, hitT, float3(n), float3(v));
+}
+// ---- the ray / triangle test and the ray setup as the walks above use them (tests/test_gpu_device_kat.py: bit for bit with the device)
+// tri9 = v0 e1 e2; out5 = hit t u v front (0 / 1 as floats; t, u, v are 0 on a miss)
+void oracle_intersect_tri(const float* tri9, const float* org, const float* dir, float* out5)
+{
+  Tri T;
+  T.v0 = float3(tri9); T.e1 = float3(tri9 + 3); T.e2 = float3(tri9 + 6);
+  T.rnode = T.prim = 0;
+  TriHit h;
+  h.t = h.u = h.v = 0.0f;
+  h.front = false;
+  const bool hit = intersectTri(T, float3(org), float3(dir), h);
+  out5[0] = hit ? 1.0f : 0.0f;
+  out5[1] = hit ? h.t : 0.0f; out5[2] = hit ? h.u : 0.0f; out5[3] = hit ? h.v : 0.0f;
+  out5[4] = (hit && h.front) ? 1.0f : 0.0f;
+}
+// out6 = rayInvDir(dir), org * rayInvDir(dir)
+void oracle_ray_setup(const float* org, const float* dir, float* out6)
+{
+  const float3 i = rayInvDir(float3(dir)), o = float3(org);
+  out6[0] = i.x; out6[1] = i.y; out6[2] = i.z;
+  out6[3] = o.x * i.x; out6[4] = o.y * i.y; out6[5] = o.z * i.z;
 }
 void oracle_light_contribution(const MiGltfLight* light, const float* pos, const float* xi, float* out8)
 {

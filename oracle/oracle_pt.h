@@ -48,6 +48,9 @@ float oracle_ggx_g1(float ax, float ay, const float* k);
 void  oracle_ggx_sample_vndf(float ax, float ay, const float* k, float u, float v, float* h);
 float oracle_hg_pdf(float cosTheta, float g);
 void  oracle_hg_sample(float u, float v, float g, const float* wi, float* wo);
+/* the ray / triangle test (tri9 = v0 e1 e2; out5 = hit t u v front) and the walk's reciprocal direction (out6 = 1 / dir, org / dir) */
+void  oracle_intersect_tri(const float* tri9, const float* org, const float* dir, float* out5);
+void  oracle_ray_setup(const float* org, const float* dir, float* out6);
 /* out8 = incidentVector[3] distance intensity[3] pdf of singleLightContribution(light, pos, xi) */
 void  oracle_light_contribution(const MiGltfLight* light, const float* pos, const float* xi, float* out8);
 #ifdef __cplusplus

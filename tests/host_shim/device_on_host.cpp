@@ -4,34 +4,9 @@
 // restatements lobe by lobe on the CPU.  This library is built by the test session only and is never loaded by the product.
 #include "pt_shading.h"
 #include "pt_packet.h"
+#include "material_from_array.h"  // materialFromArray (layout: oracle/oracle_pt.h), shared with tests/device_kat/kat_device.hip
 
 using namespace pt;
-
-namespace {
-PbrMaterial materialFromArray(const float* m)  // layout: oracle/oracle_pt.h
-{
-  PbrMaterial p = defaultPbrMaterial();
-  p.baseColor = mk3(m[0], m[1], m[2]);
-  p.roughness = mk2(m[3], m[4]);
-  p.metallic  = m[5];
-  p.ior1 = m[6]; p.ior2 = m[7];
-  p.specular = m[8];
-  p.specularColor = mk3(m[9], m[10], m[11]);
-  p.transmission = m[12];
-  p.thickness = m[13];
-  p.clearcoat = m[14]; p.clearcoatRoughness = m[15];
-  p.sheenColor = mk3(m[16], m[17], m[18]); p.sheenRoughness = m[19];
-  p.iridescence = m[20]; p.iridescenceIor = m[21]; p.iridescenceThickness = m[22];
-  p.diffuseTransmissionFactor = m[23];
-  p.diffuseTransmissionColor = mk3(m[24], m[25], m[26]);
-  p.dispersion = m[27];
-  p.retroreflection = m[28];
-  p.N = p.Ng = p.Nc = mk3(0, 0, 1);
-  p.T = mk3(1, 0, 0);
-  p.B = mk3(0, 1, 0);
-  return p;
-}
-}  // namespace
 
 extern "C" {
 // FrameConsts::slotsMagic / slotsShift (pt_scene.h: divideMagic) as the camera-ray generation uses them: mulhi(n, magic) >> shift

@@ -72,6 +72,8 @@ def lib():
             "oracle_hg_pdf": (f32, [f32, f32]),
             "oracle_hg_sample": (None, [f32, f32, f32, P(f32), P(f32)]),
             "oracle_light_contribution": (None, [P(capi.MiGltfLight), P(f32), P(f32), P(f32)]),
+            "oracle_intersect_tri": (None, [P(f32), P(f32), P(f32), P(f32)]),
+            "oracle_ray_setup": (None, [P(f32), P(f32), P(f32)]),
             "oracle_sheen_ndf": (f32, [f32, f32]),
             "oracle_sheen_sample": (None, [f32, f32, f32, P(f32)]),
             "oracle_vcavities_g": (f32, [f32, f32, f32, f32, f32]),

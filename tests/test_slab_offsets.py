@@ -30,8 +30,10 @@ def _device_mask(P, s, qlo, qhi, org, dirv, tmax):
         Bn, Bf = F(t0 - e), F(t0 + e)
         neg = idir[a] < 0
         qn, qf = (qhi[a], qlo[a]) if neg else (qlo[a], qhi[a])
-        tn = np.maximum(tn, _fma32(qn.astype(F), np.full(8, A, F), np.full(8, Bn, F)))
-        tf = np.minimum(tf, _fma32(qf.astype(F), np.full(8, A, F), np.full(8, Bf, F)))
+        # fmaxf / fminf (np.fmax / np.fmin): a NaN operand -- 0 * inf where A = s * idir overflows and q == 0, inf - inf behind it -- is ignored, so
+        # that plane puts no constraint on the child; identical to np.maximum / np.minimum wherever nothing overflows
+        tn = np.fmax(tn, _fma32(qn.astype(F), np.full(8, A, F), np.full(8, Bn, F)))
+        tf = np.fmin(tf, _fma32(qf.astype(F), np.full(8, A, F), np.full(8, Bf, F)))
     return ~np.signbit((tf - tn).astype(F))
 
 
@@ -52,37 +54,47 @@ def _exact_mask(P, s, qlo, qhi, org, dirv, tmax):
     return hit & (t0 <= t1) & (qlo[0] <= qhi[0])
 
 
-@pytest.mark.parametrize("kind", ["outside", "inside", "graze", "axis", "far"])
+SLAB_KINDS = {"outside": 1, "inside": 2, "graze": 3, "axis": 4, "far": 5}  # kind -> seed
+
+
+def _slab_case(rng, kind):
+    """One node (frame P, per-axis scale s, byte planes qlo / qhi of eight children, a fifth of them empty = inverted) and one ray
+    (org, dir, tmax) of the given kind.  Shared with tests/test_gpu_device_kat.py, which feeds the same cases to the compiled function."""
+    P = rng.uniform(-50, 50, 3).astype(F)
+    s = np.exp2(rng.integers(-14, 3, 3)).astype(F)
+    qlo = rng.integers(0, 230, (3, 8))
+    qhi = np.minimum(qlo + rng.integers(0, 120, (3, 8)), 255)
+    empty = rng.random(8) < 0.2
+    qlo[:, empty], qhi[:, empty] = 255, 0
+    centre = P.astype(np.float64) + s * 128.0
+    ext = float(np.max(s) * 255.0)
+    if kind == "inside":
+        org = (P + s * rng.uniform(0, 255, 3)).astype(F)
+    elif kind == "far":
+        org = (centre + rng.normal(size=3) * ext * rng.uniform(1e3, 1e5)).astype(F)
+    else:
+        org = (centre + rng.normal(size=3) * ext * rng.uniform(0.6, 8.0)).astype(F)
+    c = int(rng.integers(0, 8))
+    target = P.astype(np.float64) + s * rng.uniform(qlo[:, c], np.maximum(qhi[:, c], qlo[:, c] + 1))
+    if kind == "graze":  # aim at a corner / edge of a child box
+        target = P.astype(np.float64) + s * np.where(rng.random(3) < 0.5, qlo[:, c], qhi[:, c])
+    d = target - org
+    d /= max(np.linalg.norm(d), 1e-30)
+    if kind == "axis":
+        a = int(rng.integers(0, 3))
+        org[a] = F(P[a] + s[a] * rng.uniform(0, 255))
+        d[a] = rng.choice([-1.0, 1.0]) * 10.0 ** rng.uniform(-40, -10)
+    d = d.astype(F)
+    tmax = F(np.inf) if rng.random() < 0.5 else F(np.linalg.norm(centre - org) * rng.uniform(0.3, 2.0))
+    return P, s, qlo, qhi, org, d, tmax
+
+
+@pytest.mark.parametrize("kind", sorted(SLAB_KINDS, key=SLAB_KINDS.get))
 def test_slab_offsets_keep_the_node_test_conservative(kind):
-    rng = np.random.default_rng({"outside": 1, "inside": 2, "graze": 3, "axis": 4, "far": 5}[kind])
+    rng = np.random.default_rng(SLAB_KINDS[kind])
     missed = checked = entered = 0
     for _ in range(3000):
-        P = rng.uniform(-50, 50, 3).astype(F)
-        s = np.exp2(rng.integers(-14, 3, 3)).astype(F)
-        qlo = rng.integers(0, 230, (3, 8))
-        qhi = np.minimum(qlo + rng.integers(0, 120, (3, 8)), 255)
-        empty = rng.random(8) < 0.2
-        qlo[:, empty], qhi[:, empty] = 255, 0
-        centre = P.astype(np.float64) + s * 128.0
-        ext = float(np.max(s) * 255.0)
-        if kind == "inside":
-            org = (P + s * rng.uniform(0, 255, 3)).astype(F)
-        elif kind == "far":
-            org = (centre + rng.normal(size=3) * ext * rng.uniform(1e3, 1e5)).astype(F)
-        else:
-            org = (centre + rng.normal(size=3) * ext * rng.uniform(0.6, 8.0)).astype(F)
-        c = int(rng.integers(0, 8))
-        target = P.astype(np.float64) + s * rng.uniform(qlo[:, c], np.maximum(qhi[:, c], qlo[:, c] + 1))
-        if kind == "graze":  # aim at a corner / edge of a child box
-            target = P.astype(np.float64) + s * np.where(rng.random(3) < 0.5, qlo[:, c], qhi[:, c])
-        d = target - org
-        d /= max(np.linalg.norm(d), 1e-30)
-        if kind == "axis":
-            a = int(rng.integers(0, 3))
-            org[a] = F(P[a] + s[a] * rng.uniform(0, 255))
-            d[a] = rng.choice([-1.0, 1.0]) * 10.0 ** rng.uniform(-40, -10)
-        d = d.astype(F)
-        tmax = F(np.inf) if rng.random() < 0.5 else F(np.linalg.norm(centre - org) * rng.uniform(0.3, 2.0))
+        P, s, qlo, qhi, org, d, tmax = _slab_case(rng, kind)
         dev = _device_mask(P, s, qlo, qhi, org, d, tmax)
         ex = _exact_mask(P, s, qlo, qhi, org, d, tmax)
         missed += int((ex & ~dev).sum())

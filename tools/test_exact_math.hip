@@ -1,5 +1,8 @@
 // Checks divExact / sqrtExact (csrc/device/pt_math.h) on the device, bit for bit, against `a / b` and sqrtf of THIS translation unit -- which is compiled
 // with the default -fhip-fp32-correctly-rounded-divide-sqrt, i.e. IEEE -- and that the fast forms pt_kernels.hip gets stay within their ulp bounds.
+// The suite now covers this claim, and against an independent reference: tests/test_gpu_device_kat.py (test_div_exact_and_sqrt_exact_are_ieee_bit_for_bit)
+// runs both helpers on the operand pairs of the two modes below, 2^20 of each, compiled with AND without the fast options, against numpy's correctly rounded
+// float32 division and square root.  This tool stays for the long run (2 x 2^28 pairs, device against device).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ivk_gltf_renderer_amd/csrc/device -Iinclude -o tools/_scratch/test_exact_math tools/test_exact_math.hip && tools/_scratch/test_exact_math
 #include <hip/hip_runtime.h>
 

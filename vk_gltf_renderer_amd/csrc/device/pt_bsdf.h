@@ -423,7 +423,7 @@ PT_DEV BsdfEval brdf_ggx_smith_eval(f3 k1, f3 k2, const PbrMaterial& mat, f3 N, 
     return evalAbsorb();
   f3    h  = normalize(k1 + k2);
   float nh = dot(N, h), k1h = dot(k1, h), k2h = dot(k2, h);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return evalAbsorb();
   f3    h0  = mk3(dot(mat.T, h), dot(mat.B, h), nh);
   float pdf = hvd_ggx_eval(mk2(1.0f / roughness.x, 1.0f / roughness.y), h0);
@@ -470,7 +470,7 @@ PT_DEV BsdfEval btdf_ggx_smith_eval(f3 k1, f3 k2, const PbrMaterial& mat, f3 tin
   bool  backside = (dot(k2, mat.Ng) < 0.0f);
   f3    h        = compute_half_vector(k1, k2, mat.N, ior, nk2, backside, thin);
   float nh = dot(mat.N, h), k1h = dot(k1, h), k2h = dot(k2, h) * (backside ? -1.0f : 1.0f);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return evalAbsorb();
   float fr;
   if(!backside)
@@ -547,7 +547,7 @@ PT_DEV BsdfEval brdf_sheen_eval(f3 k1, f3 k2, const PbrMaterial& mat)
   float nk1 = fabsf(dot(k1, mat.N)), nk2 = fabsf(dot(k2, mat.N));
   f3    h   = normalize(k1 + k2);
   float nh = dot(mat.N, h), k1h = dot(k1, h), k2h = dot(k2, h);
-  if(nk1 <= 0.0f || nh <= 0.0f || k1h < 0.0f || k2h < 0.0f)
+  if(nk1 <= 0.0f || !(nh > 0.0f) || k1h < 0.0f || k2h < 0.0f)  // (!(nh > 0): also the half vector that does not exist -- k2 == -k1, or index-matched refraction straight through: normalize(0))
     return evalAbsorb();
   float invRoughness = 1.0f / (mat.sheenRoughness * mat.sheenRoughness);
   float pdf          = hvd_sheen_eval(invRoughness, nh);

@@ -30,6 +30,9 @@ struct TriHit
 // Moeller-Trumbore with the evaluation order shared with the oracle (oracle_pt.cpp intersectTri): t, u, v are bit-identical.
 PT_DEV bool intersectTri(f3 v0, f3 e1, f3 e2, f3 org, f3 dir, TriHit& h)
 {
+  // No contraction beyond the explicit fmaf chains: left to itself the compiler fuses `u + v` with the product that makes v (also through __fadd_rn), the sum
+  // then sees an UNROUNDED v, and on the edge u + v == 1 a hit of the oracle is a miss here and the other way round (tests/test_gpu_device_kat.py).
+#pragma clang fp contract(off)
   f3    pvec = crossFma(dir, e2);
   float det  = dotFma(e1, pvec);
   if(det == 0.0f)
