@@ -57,20 +57,49 @@ MI_PT_API int                  mi_mikktspace(const float* positions, const float
  * opaque) reports what is seen through a removed part instead of the alpha-tested instance itself.  Returns the number of (sub-)triangles dropped (>= 0)
  * or a negative MiPtStatus; the MiPtSceneDesc changes (fetch mi_scene_desc again, create the renderer afterwards).
  * Skinned and morphed primitives (mi_scene_deformation) are never cut: skinning does not commute with the cut's barycentric
- * re-interpolation of the vertices. */
+ * re-interpolation of the vertices.  Neither is a material whose alpha state a KHR_animation_pointer channel of any clip animates
+ * (alphaCutoff, alphaMode, the base or diffuse colour factor or texture): the classification would hold for one moment of the clip
+ * only, and mi_pt_update_materials refuses an alpha change on cut geometry -- so the loader's own animations never meet that refusal. */
 MI_PT_API int64_t              mi_scene_cut_alpha(MiScene* scene, int subdivisions);
 
 /* Keyframe animation of node transforms (reference: nvvkgltf::AnimationSystem, src/gltf_scene_animation.hpp:93-122; AnimationInfo
  * src/gltf_scene.hpp:159-189; driven per frame by GltfRenderer::updateAnimation, src/renderer.cpp:2065-2170).  Translation /
- * rotation / scale channels and morph-target `weights` channels with LINEAR, STEP and CUBICSPLINE samplers; KHR_animation_pointer is
- * not evaluated.  mi_scene_update_animation poses the scene at `time` (seconds on the clip's own axis, [start, end] as reported by
+ * rotation / scale channels and morph-target `weights` channels with LINEAR, STEP and CUBICSPLINE samplers.
+ * KHR_animation_pointer channels (target path "pointer"; SCALAR, VEC2, VEC3 or VEC4 outputs, the three samplers componentwise, the same
+ * segment search and keyframe-range rule; reference: src/gltf_animation_pointer.cpp, src/gltf_scene_animation.cpp:373-437) are
+ * evaluated for: /materials/i/... (the value goes into the document and material i through the loader's conversion again, so every
+ * property the loader reads animates, every KHR_materials_* factor and the KHR_texture_transform offset / scale / rotation of any texture
+ * slot included; the material and texture-info tables of mi_scene_desc() are rewritten in place, same pointers and counts);
+ * /extensions/KHR_lights_punctual/lights/i/{color, intensity, range, spot/innerConeAngle, spot/outerConeAngle} (the light table, in place;
+ * placement stays with the node); /cameras/i/{perspective/{yfov, aspectRatio, znear, zfar}, orthographic/{xmag, ymag, znear, zfar}} (what
+ * mi_scene_camera returns; aspectRatio is the viewport's, as in the reference); /nodes/i/extensions/KHR_node_visibility/visible (value != 0,
+ * cascading to the children like at load, into renderNodeVisible in place); /nodes/i/{translation, rotation, scale}, routed into the pose
+ * code of the core channels -- the reference parses these and then drops them (syncNode, src/gltf_scene_animation.cpp:371-397) although
+ * the extension allows them.  `weights` by pointer is not evaluated.  A pointer that resolves to nothing, an index out of range or an
+ * output whose width does not fit the property drops the channel at load.
+ * mi_scene_update_animation poses the scene at `time` (seconds on the clip's own axis, [start, end] as reported by
  * mi_scene_animation_info) and rewrites the matrices of the render-node table and the light placements of mi_scene_desc() in
  * place -- same pointers, same counts -- ready for mi_pt_update_render_nodes() + mi_pt_update_lights(), and the per-frame tables of
  * mi_scene_deformation() (joint matrices, morph weights), ready for mi_pt_update_deformation().  Returns 1 when something moved
- * (a node or a weights channel covered `time`), 0 when no channel covered `time`, or a negative MiPtStatus. */
+ * (a node, weights or pointer channel covered `time`), 0 when no channel covered `time`, or a negative MiPtStatus -- among them
+ * MI_PT_ERR_ARGUMENT, with nothing changed, when a pointer channel would change the number of texture infos (it gives a material a
+ * texture it did not have).
+ * mi_scene_animation_changes: what the last mi_scene_update_animation changed, i.e. which device updates the caller owes: NODES or
+ * VISIBILITY -> mi_pt_update_render_nodes, LIGHTS -> mi_pt_update_lights, DEFORMATION -> mi_pt_update_deformation, MATERIALS ->
+ * mi_pt_update_materials, CAMERAS -> mi_scene_camera + the frame info again.  0 after an update that applied no channel. */
+enum
+{
+  MI_SCENE_CHANGED_NODES       = 1,
+  MI_SCENE_CHANGED_LIGHTS      = 2,
+  MI_SCENE_CHANGED_DEFORMATION = 4,
+  MI_SCENE_CHANGED_MATERIALS   = 8,
+  MI_SCENE_CHANGED_CAMERAS     = 16,
+  MI_SCENE_CHANGED_VISIBILITY  = 32
+};
 MI_PT_API int                  mi_scene_num_animations(const MiScene* scene);
 MI_PT_API int                  mi_scene_animation_info(const MiScene* scene, int index, float* start, float* end, char* name, int nameCapacity);
 MI_PT_API int                  mi_scene_update_animation(MiScene* scene, int index, float time);
+MI_PT_API int                  mi_scene_animation_changes(const MiScene* scene); /* of the last mi_scene_update_animation */
 
 /* Skins and morph targets (reference: AnimationSystem::parseSkinTasks / parseMorphPrimitives, src/gltf_scene_animation.cpp:196-320).
  * mi_scene_deformation: the tables mi_pt_set_deformation takes, NULL when the scene deforms nothing.  One entry per unique deforming render

@@ -185,6 +185,24 @@ MI_PT_API int mi_pt_update_render_nodes(MiPt* pt, const MiGltfRenderNode* render
  * work in flight; the caller restarts accumulation. */
 MI_PT_API int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights);
 
+/* replaces the material half of the scene sync of edited and animated scenes: a material marked dirty by the inspector, by undo / redo, by a
+ * variant or by a KHR_animation_pointer channel (reference: src/gltf_scene.cpp:1493, src/ui_inspector.cpp:1010) and uploaded record by record by
+ * SceneVk (src/gltf_scene_vk.cpp:430-487).  Takes BOTH tables again, complete: numMaterials must be the count at creation, numTextureInfos may
+ * differ (slot 0 stays the reserved "no texture" entry).  Textures themselves stay resident: their images and their count cannot change here.
+ * The call brings everything a build derives from the materials -- the instance-flag word of the triangle records, the alpha records, the
+ * per-slot texture records, the scene-wide summaries that select kernels and optional buffers -- to the state mi_pt_create would give it on the
+ * new tables: the next frames render bit for bit what a fresh instance renders.  It does so in place, without a build (one launch over the
+ * triangle slots when an instance flag or an alpha record changed, none for factor or UV-transform changes), except: (1) the transmissive bit
+ * of a material changes while the tree holds pre-split references, (2) the BVH2 walk (bvhBuilder bit 0) and a flag or alpha change; those
+ * rebuild and count in MiPtAccelInfo::builds.  Refit data stays valid across an in-place update.
+ * MI_PT_ERR_ARGUMENT, with NOTHING changed: a count mismatch, a material slot beyond the texture-info table, or a change of the alpha state
+ * (alphaMode, alphaCutoff, base / diffuse alpha factor or texture) of a material used by geometry that mi_scene_cut_alpha cut at load
+ * (opaqueTriangleCount > 0): that classification held for the old alpha state -- re-cut and re-create.  (mi_pt_create refuses no factor for
+ * being non-finite and reads a texture-info `index` outside the textures as "no texture"; so does this call.)
+ * Synchronises with the work in flight (queued frames render the old materials); the caller restarts accumulation. */
+MI_PT_API int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int numMaterials, const MiGltfTextureInfo* textureInfos,
+                                     int numTextureInfos);
+
 /* Vertex deformation of animated scenes: glTF skins (JOINTS_0 / WEIGHTS_0, four influences) and morph targets, evaluated on the device
  * into the resident geometry (reference: shaders/skinning.comp.slang, shaders/morph.comp.slang dispatched by AnimationVk::dispatchAnimation,
  * src/gltf_scene_animation_vk.cpp:413-592, from GltfRenderer::updateAnimation, src/renderer.cpp:2065-2170).  Per deforming render primitive:

@@ -163,6 +163,9 @@ assert C.sizeof(MiPtAccelInfo) == 64
 
 MI_PT_ABI_VERSION = 8  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
+# mi_scene_animation_changes (include/mi_host.h)
+(MI_SCENE_CHANGED_NODES, MI_SCENE_CHANGED_LIGHTS, MI_SCENE_CHANGED_DEFORMATION, MI_SCENE_CHANGED_MATERIALS, MI_SCENE_CHANGED_CAMERAS,
+ MI_SCENE_CHANGED_VISIBILITY) = 1, 2, 4, 8, 16, 32
 MI_PT_ACCEL_REBUILD, MI_PT_ACCEL_REFIT, MI_PT_ACCEL_AUTO = 0, 1, 2
 MI_PT_ACCEL_LAST_BUILD, MI_PT_ACCEL_LAST_REFIT = 0, 1
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
@@ -225,6 +228,7 @@ HOST_SYMBOLS = {
     "mi_scene_num_animations": (i32, [VP]),
     "mi_scene_animation_info": (i32, [VP, i32, P(f32), P(f32), C.c_char_p, i32]),
     "mi_scene_update_animation": (i32, [VP, i32, f32]),
+    "mi_scene_animation_changes": (i32, [VP]),
     "mi_scene_deformation": (P(MiPtDeformDesc), [VP]),
     "mi_scene_deform_on_host": (i32, [VP]),
     "mi_hdr_from_pixels": (i32, [i32, i32, P(f32), P(VP)]),
@@ -272,6 +276,7 @@ PT_SYMBOLS = {
     "mi_pt_abi_version": (i32, []),
     "mi_pt_update_render_nodes": (i32, [VP, P(MiGltfRenderNode), i32, P(C.c_uint8)]),
     "mi_pt_update_lights": (i32, [VP, P(MiGltfLight), i32]),
+    "mi_pt_update_materials": (i32, [VP, P(MiGltfShadeMaterial), i32, P(MiGltfTextureInfo), i32]),
     "mi_pt_set_deformation": (i32, [VP, P(MiPtDeformDesc)]),
     "mi_pt_update_deformation": (i32, [VP, P(f32), P(f32), i32]),
     "mi_pt_read_vertices": (i32, [VP, i32, P(f32), P(f32), P(f32)]),

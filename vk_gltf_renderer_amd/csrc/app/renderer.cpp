@@ -327,7 +327,28 @@ bool GltfRenderer::updateAnimation()
     fprintf(stderr, "updateAnimation: %s\n", mi_pt_last_error());
     return false;
   }
-  const MiPtSceneDesc* d = mi_scene_desc(sc);
+  const MiPtSceneDesc* d       = mi_scene_desc(sc);
+  const int            changes = mi_scene_animation_changes(sc);
+  // KHR_animation_pointer: the material tables only when a channel changed them (before the nodes: a rebuild then sees the new flags), the
+  // active camera's projection when a channel changed a camera (onRender derives the frame info from m_resources.camera)
+  if((changes & MI_SCENE_CHANGED_MATERIALS)
+     && mi_pt_update_materials(m_pathTracer.handle(), d->materials, d->numMaterials, d->textureInfos, d->numTextureInfos) != MI_PT_OK)
+  {
+    fprintf(stderr, "updateAnimation: %s\n", mi_pt_last_error());
+    return false;
+  }
+  if(changes & MI_SCENE_CHANGED_CAMERAS)
+  {
+    MiCamera cam;
+    if(mi_scene_camera(sc, std::max(m_gltfCamera, 0), &cam) == MI_PT_OK)
+    {
+      m_resources.camera.fovDegrees = cam.fovDegrees;
+      m_resources.camera.znear      = cam.znear;
+      m_resources.camera.zfar       = cam.zfar;
+      m_resources.camera.xmag       = cam.xmag;
+      m_resources.camera.ymag       = cam.ymag;
+    }
+  }
   if(mi_pt_update_render_nodes(m_pathTracer.handle(), d->renderNodes, d->numRenderNodes, d->renderNodeVisible) != MI_PT_OK
      || mi_pt_update_lights(m_pathTracer.handle(), d->lights, d->numLights) != MI_PT_OK)
   {

@@ -39,6 +39,14 @@ struct RefitBox  // 24 B
   float lo[3], hi[3];
 };
 
+// The flag word of triangle t's record (DevTri::c.w): its render node's instance flags, and FORCE_OPAQUE for a triangle the load-time
+// classification found opaque (DevPrim::opaqueTriangles), which counts like a triangle of an opaque instance.  One text for the build, the
+// refit and the material patch (material_patch.h).
+PT_DEV uint32_t triangleFlagWord(const DevPrim& rp, uint32_t t, uint32_t instFlags)
+{
+  return instFlags | (t < rp.opaqueTriangles ? uint32_t(INST_FORCE_OPAQUE) : 0u);
+}
+
 // Triangle t of render node `rnode` in world space (fixed fmaf order, shared with the oracle) and the box it is filed under: what
 // k_tri_setup writes for it, and what k_refit_tris rewrites.
 PT_DEV void worldTriangle(const MiGltfRenderNode& rn, const DevPrim& rp, int rnode, uint32_t t, uint32_t instFlags, DevTri& tri, float lo[3], float hi[3])
@@ -62,8 +70,7 @@ PT_DEV void worldTriangle(const MiGltfRenderNode& rn, const DevPrim& rp, int rno
   f3 e1 = p1 - p0, e2 = p2 - p0;
   tri.a = make_float4(p0.x, p0.y, p0.z, __int_as_float(rnode));
   tri.b = make_float4(e1.x, e1.y, e1.z, __int_as_float(int(t)));
-  // (a triangle the load-time classification found opaque -- DevPrim::opaqueTriangles -- counts as FORCE_OPAQUE like an opaque instance)
-  tri.c = make_float4(e2.x, e2.y, e2.z, __uint_as_float(instFlags | (t < rp.opaqueTriangles ? uint32_t(INST_FORCE_OPAQUE) : 0u)));
+  tri.c = make_float4(e2.x, e2.y, e2.z, __uint_as_float(triangleFlagWord(rp, t, instFlags)));
   // bounds from the same p0 + e arithmetic the intersector sees
   f3 q1 = p0 + e1, q2 = p0 + e2;
   lo[0] = fminf(p0.x, fminf(q1.x, q2.x)); hi[0] = fmaxf(p0.x, fmaxf(q1.x, q2.x));

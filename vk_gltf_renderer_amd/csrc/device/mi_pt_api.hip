@@ -15,6 +15,7 @@
 
 #include "mi_pt.h"
 #include "bvh_refit.h"
+#include "material_patch.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_deform.h"
@@ -209,6 +210,13 @@ struct MiPt
   std::vector<uint8_t>          hostVisible;    // empty = all visible
   std::vector<uint8_t>          matInstFlags;   // per material: INST_FORCE_OPAQUE | INST_CULL_DISABLE | INST_TRANSMISSIVE | INST_ALPHA_PASSES
   std::vector<uint8_t>          matFeatures;    // per material: bit0 volume scatter, bit1 needs the generic shade kernel
+  // host copies of the material and texture-info tables and of the resident textures' descriptors: what mi_pt_update_materials diffs a new
+  // table against and re-derives texRefs / coreTex from
+  std::vector<MiGltfShadeMaterial> hostMaterials;
+  std::vector<MiGltfTextureInfo>   hostTexInfos;
+  std::vector<pt::DevTexture>      hostTextures;
+  DevBuf<uint8_t>               matDirty;       // per render node: pt::MATERIAL_PATCH_* of the material update in progress (k_patch_materials)
+  bool                          splitRefs = false;  // the resident tree holds pre-split references (more triangle slots than scene triangles)
   std::vector<uint32_t>         primTriangles;  // per render primitive: triangle count, 0 when it has no usable geometry
   std::vector<pt::DevPrim>      hostPrims;      // the device addresses of every primitive's streams (mi_pt_read_vertices, deformation)
   std::vector<uint32_t>         primVertices;   // per render primitive: vertex count
@@ -644,6 +652,7 @@ int buildAccelerationUnguarded(MiPt* pt)
     pt->scene.bvh8NumNodes = 0;
     pt->staticStats.bvhNodeCount     = bo.numNodes;
     pt->staticStats.bvhTriangleCount = bo.numTris;
+    pt->splitRefs                    = bo.numTris > bo.sceneTris;
     pt->staticStats.bvhNodeBytes     = 64;
     pt->staticStats.bvhTriangleBytes = sizeof(pt::DevTri);
     pt->wide = (pt->bvhBuilder & 1) == 0;
@@ -810,6 +819,94 @@ uint64_t refitBytes(const MiPt* pt)
   return bytes(pt->refitSlotBox) + bytes(pt->refitBuiltBox) + bytes(pt->refitNodeBox) + bytes(pt->refitSah) + bytes(pt->refitSahPartial) + bytes(pt->refitDirty);
 }
 
+// What a material bakes into the triangles of the instances that use it (MiPt::matInstFlags; reference: getInstanceFlag, src/gltf_scene_rtx.cpp:271-295) ...
+uint8_t materialInstFlags(const MiGltfShadeMaterial& mat)
+{
+  uint32_t f = 0;
+  if(mat.transmissionFactor == 0.0f && mat.alphaMode == MI_ALPHA_OPAQUE && mat.diffuseTransmissionFactor == 0.0f)
+    f |= pt::INST_FORCE_OPAQUE;
+  if(mat.doubleSided == 1 || mat.thicknessFactor > 0.0f || mat.transmissionFactor > 0.0f)
+    f |= pt::INST_CULL_DISABLE;
+  if(mat.transmissionFactor > 0.01f)  // MIN_TRANSMISSION, shaders/pathtrace_functions.h.slang:36,256
+    f |= pt::INST_TRANSMISSIVE;
+  if(!(f & pt::INST_FORCE_OPAQUE) && mat.alphaMode == MI_ALPHA_OPAQUE)  // getOpacity == 1: the alpha draw always commits (pt_scene.h)
+    f |= pt::INST_ALPHA_PASSES;
+  return uint8_t(f);
+}
+// ... and what it asks of the shade kernels (MiPt::matFeatures)
+uint8_t materialFeatures(const MiGltfShadeMaterial& mat)
+{
+  uint32_t g = 0;
+  if(mat.multiscatterColorFactor[0] > 0.0f || mat.multiscatterColorFactor[1] > 0.0f || mat.multiscatterColorFactor[2] > 0.0f)
+    g |= 1u;
+  // the materials the specialised shade kernel cannot serve (see evaluateMaterial<SIMPLE>, pt_shading.h)
+  if(mat.transmissionFactor != 0.0f || mat.diffuseTransmissionFactor != 0.0f || mat.clearcoatFactor != 0.0f || mat.iridescenceFactor != 0.0f
+     || mat.anisotropyStrength > 0.0f || mat.retroreflectionFactor != 0.0f || mat.sheenColorFactor[0] != 0.0f || mat.sheenColorFactor[1] != 0.0f
+     || mat.sheenColorFactor[2] != 0.0f)
+    g |= 2u;
+  return uint8_t(g);
+}
+// The 22 texture-info slots of every material must lie within the texture-info table: the kernels index it without further checks
+bool materialSlotsInRange(const MiGltfShadeMaterial* materials, int numMaterials, int numTextureInfos, std::string& why)
+{
+  for(int m = 0; m < numMaterials; ++m)
+  {
+    const uint16_t* slots = &materials[m].pbrBaseColorTexture;  // the 22 texture-info slots are contiguous (mi_pt_shaderio.h)
+    for(int k = 0; k < 22; ++k)
+      if(int(slots[k]) >= numTextureInfos)
+      {
+        why = "material " + std::to_string(m) + " references texture info " + std::to_string(slots[k]) + " of " + std::to_string(numTextureInfos);
+        return false;
+      }
+  }
+  return true;
+}
+// Texture info + descriptor, flattened per texture slot (pt_scene.h: DevTexRef), and the five core map slots per material (DevCoreTex), in
+// the order of the material's slot words: derived from the tables and the resident textures (MiPt::hostTextures), at creation and again at
+// every material update (an animated uvTransform moves CT_TRANSFORM, a changed texCoord CT_TEXCOORD1).
+void deriveTextureRecords(const MiPt* pt, const MiGltfShadeMaterial* materials, int numMaterials, const MiGltfTextureInfo* textureInfos, int numTextureInfos,
+                          std::vector<pt::DevTexRef>& refs, std::vector<pt::DevCoreTex>& core)
+{
+  const int numTextures = int(pt->hostTextures.size());
+  refs.assign(size_t(std::max(numTextureInfos, 1)), pt::DevTexRef{});
+  memset(refs.data(), 0, refs.size() * sizeof(pt::DevTexRef));
+  for(int i = 0; i < numTextureInfos; ++i)
+  {
+    const MiGltfTextureInfo& ti = textureInfos[i];
+    pt::DevTexRef&           r  = refs[size_t(i)];
+    memcpy(r.uv, ti.uvTransform, sizeof(r.uv));
+    r.texCoord = uint8_t(ti.texCoord);
+    if(ti.index >= 0 && ti.index < numTextures)
+    {
+      const pt::DevTexture& d = pt->hostTextures[size_t(ti.index)];
+      r.level0 = d.levelOffset[0]; r.width = d.width; r.height = d.height; r.numLevels = d.numLevels; r.srgb = d.srgb;
+      r.magFilter = d.magFilter; r.minFilter = d.minFilter; r.mipmapMode = d.mipmapMode; r.wrapS = d.wrapS; r.wrapT = d.wrapT;
+    }
+  }
+  core.assign(size_t(std::max(numMaterials, 1)) * 5, pt::DevCoreTex{});
+  memset(core.data(), 0, core.size() * sizeof(pt::DevCoreTex));
+  static const float identityUv[6] = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
+  for(int m = 0; m < numMaterials; ++m)
+  {
+    const MiGltfShadeMaterial& M = materials[m];
+    const uint16_t slots[5] = {M.pbrBaseColorTexture, M.normalTexture, M.pbrMetallicRoughnessTexture, M.emissiveTexture, M.occlusionTexture};
+    for(int k = 0; k < 5; ++k)
+    {
+      pt::DevCoreTex& c = core[size_t(m) * 5 + size_t(k)];
+      c.ref = slots[k];
+      if(slots[k] == 0 || int(slots[k]) >= numTextureInfos)
+        continue;
+      const pt::DevTexRef& r = refs[slots[k]];
+      c.level0 = r.level0;
+      c.wh     = uint32_t(r.width) | (uint32_t(r.height) << 16);
+      const bool fast = pt->sw.coreTex && r.width > 0 && r.magFilter == MI_FILTER_LINEAR && r.minFilter == MI_FILTER_LINEAR && r.wrapS != MI_WRAP_MIRRORED_REPEAT && r.wrapT != MI_WRAP_MIRRORED_REPEAT;
+      c.flags  = (fast ? pt::CT_FAST : 0u) | (r.srgb ? pt::CT_SRGB : 0u) | (r.texCoord ? pt::CT_TEXCOORD1 : 0u) | (memcmp(r.uv, identityUv, sizeof(identityUv)) != 0 ? pt::CT_TRANSFORM : 0u)
+                | (r.mipmapMode == MI_FILTER_LINEAR ? pt::CT_MIP_LINEAR : 0u) | (uint32_t(r.wrapS) << pt::CT_WRAPS_SHIFT) | (uint32_t(r.wrapT) << pt::CT_WRAPT_SHIFT)
+                | (uint32_t(r.numLevels) << pt::CT_LEVELS_SHIFT);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -864,13 +961,10 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render node " + std::to_string(n) + " references material " + std::to_string(rn.materialID) + " of "
                                           + std::to_string(sd->numMaterials));
   }
-  for(int m = 0; m < sd->numMaterials; ++m)
   {
-    const uint16_t* slots = &sd->materials[m].pbrBaseColorTexture;  // the 22 texture-info slots are contiguous (mi_pt_shaderio.h)
-    for(int k = 0; k < 22; ++k)
-      if(int(slots[k]) >= sd->numTextureInfos)
-        return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: material " + std::to_string(m) + " references texture info " + std::to_string(slots[k]) + " of "
-                                            + std::to_string(sd->numTextureInfos));
+    std::string why;
+    if(!materialSlotsInRange(sd->materials, sd->numMaterials, sd->numTextureInfos, why))
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: " + why);
   }
   for(int i = 0; i < sd->numRenderPrimitives; ++i)
   {
@@ -978,29 +1072,12 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
     pt->hostVisible.assign(sd->renderNodeVisible, sd->renderNodeVisible + sd->numRenderNodes);
   pt->matInstFlags.resize(size_t(sd->numMaterials));
   pt->matFeatures.resize(size_t(sd->numMaterials));
+  pt->hostMaterials.assign(sd->materials, sd->materials + sd->numMaterials);
+  pt->hostTexInfos.assign(sd->textureInfos, sd->textureInfos + sd->numTextureInfos);
   for(int m = 0; m < sd->numMaterials; ++m)
   {
-    const MiGltfShadeMaterial& mat = sd->materials[m];
-    uint32_t                   f   = 0;
-    // reference: getInstanceFlag, src/gltf_scene_rtx.cpp:271-295
-    if(mat.transmissionFactor == 0.0f && mat.alphaMode == MI_ALPHA_OPAQUE && mat.diffuseTransmissionFactor == 0.0f)
-      f |= pt::INST_FORCE_OPAQUE;
-    if(mat.doubleSided == 1 || mat.thicknessFactor > 0.0f || mat.transmissionFactor > 0.0f)
-      f |= pt::INST_CULL_DISABLE;
-    if(mat.transmissionFactor > 0.01f)  // MIN_TRANSMISSION, shaders/pathtrace_functions.h.slang:36,256
-      f |= pt::INST_TRANSMISSIVE;
-    if(!(f & pt::INST_FORCE_OPAQUE) && mat.alphaMode == MI_ALPHA_OPAQUE)  // getOpacity == 1: the alpha draw always commits (pt_scene.h)
-      f |= pt::INST_ALPHA_PASSES;
-    pt->matInstFlags[size_t(m)] = uint8_t(f);
-    uint32_t g = 0;
-    if(mat.multiscatterColorFactor[0] > 0.0f || mat.multiscatterColorFactor[1] > 0.0f || mat.multiscatterColorFactor[2] > 0.0f)
-      g |= 1u;
-    // the materials the specialised shade kernel cannot serve (see evaluateMaterial<SIMPLE>, pt_shading.h)
-    if(mat.transmissionFactor != 0.0f || mat.diffuseTransmissionFactor != 0.0f || mat.clearcoatFactor != 0.0f || mat.iridescenceFactor != 0.0f
-       || mat.anisotropyStrength > 0.0f || mat.retroreflectionFactor != 0.0f || mat.sheenColorFactor[0] != 0.0f || mat.sheenColorFactor[1] != 0.0f
-       || mat.sheenColorFactor[2] != 0.0f)
-      g |= 2u;
-    pt->matFeatures[size_t(m)] = uint8_t(g);
+    pt->matInstFlags[size_t(m)] = materialInstFlags(sd->materials[m]);
+    pt->matFeatures[size_t(m)]  = materialFeatures(sd->materials[m]);
   }
   pt->primTriangles.resize(size_t(sd->numRenderPrimitives));
   for(int i = 0; i < sd->numRenderPrimitives; ++i)
@@ -1054,46 +1131,11 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
                                  d.wrapT, nullptr);
       HIP_TRY(hipGetLastError());
     }
-    // texture info + descriptor, flattened per texture slot (pt_scene.h: DevTexRef)
-    std::vector<pt::DevTexRef> refs(size_t(std::max(sd->numTextureInfos, 1)));
-    memset(refs.data(), 0, refs.size() * sizeof(pt::DevTexRef));
-    for(int i = 0; i < sd->numTextureInfos; ++i)
-    {
-      const MiGltfTextureInfo& ti = sd->textureInfos[i];
-      pt::DevTexRef&           r  = refs[size_t(i)];
-      memcpy(r.uv, ti.uvTransform, sizeof(r.uv));
-      r.texCoord = uint8_t(ti.texCoord);
-      if(ti.index >= 0 && ti.index < sd->numTextures)
-      {
-        const pt::DevTexture& d = dt[size_t(ti.index)];
-        r.level0 = d.levelOffset[0]; r.width = d.width; r.height = d.height; r.numLevels = d.numLevels; r.srgb = d.srgb;
-        r.magFilter = d.magFilter; r.minFilter = d.minFilter; r.mipmapMode = d.mipmapMode; r.wrapS = d.wrapS; r.wrapT = d.wrapT;
-      }
-    }
+    pt->hostTextures = dt;
+    std::vector<pt::DevTexRef>  refs;
+    std::vector<pt::DevCoreTex> core;
+    deriveTextureRecords(pt.get(), sd->materials, sd->numMaterials, sd->textureInfos, sd->numTextureInfos, refs, core);
     HIP_TRY(pt->texRefs.upload(refs.data(), refs.size()));
-    // the five core map slots per material (pt_scene.h: DevCoreTex), in the order of the material's slot words
-    std::vector<pt::DevCoreTex> core(size_t(std::max(sd->numMaterials, 1)) * 5);
-    memset(core.data(), 0, core.size() * sizeof(pt::DevCoreTex));
-    static const float identityUv[6] = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};
-    for(int m = 0; m < sd->numMaterials; ++m)
-    {
-      const MiGltfShadeMaterial& M = sd->materials[m];
-      const uint16_t slots[5] = {M.pbrBaseColorTexture, M.normalTexture, M.pbrMetallicRoughnessTexture, M.emissiveTexture, M.occlusionTexture};
-      for(int k = 0; k < 5; ++k)
-      {
-        pt::DevCoreTex& c = core[size_t(m) * 5 + size_t(k)];
-        c.ref = slots[k];
-        if(slots[k] == 0 || int(slots[k]) >= sd->numTextureInfos)
-          continue;
-        const pt::DevTexRef& r = refs[slots[k]];
-        c.level0 = r.level0;
-        c.wh     = uint32_t(r.width) | (uint32_t(r.height) << 16);
-        const bool fast = pt->sw.coreTex && r.width > 0 && r.magFilter == MI_FILTER_LINEAR && r.minFilter == MI_FILTER_LINEAR && r.wrapS != MI_WRAP_MIRRORED_REPEAT && r.wrapT != MI_WRAP_MIRRORED_REPEAT;
-        c.flags  = (fast ? pt::CT_FAST : 0u) | (r.srgb ? pt::CT_SRGB : 0u) | (r.texCoord ? pt::CT_TEXCOORD1 : 0u) | (memcmp(r.uv, identityUv, sizeof(identityUv)) != 0 ? pt::CT_TRANSFORM : 0u)
-                  | (r.mipmapMode == MI_FILTER_LINEAR ? pt::CT_MIP_LINEAR : 0u) | (uint32_t(r.wrapS) << pt::CT_WRAPS_SHIFT) | (uint32_t(r.wrapT) << pt::CT_WRAPT_SHIFT)
-                  | (uint32_t(r.numLevels) << pt::CT_LEVELS_SHIFT);
-      }
-    }
     HIP_TRY(pt->coreTex.upload(core.data(), core.size()));
   }
   {
@@ -1172,6 +1214,169 @@ int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights)
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still sample the old table
   HIP_TRY(hipMemcpy(pt->lights.ptr, lights, sizeof(MiGltfLight) * size_t(numLights), hipMemcpyHostToDevice));
   return MI_PT_OK;
+}
+
+// What makeAlphaRecord (pt_shading.h) reads of a material and its base / diffuse texture info, as it reads it: two materials with equal
+// keys give equal alpha records for the same triangle.  (An OPAQUE material's record is the default one whatever else it holds.)
+struct AlphaKey
+{
+  int32_t  alphaMode = MI_ALPHA_OPAQUE;
+  float    cutoff = 0.0f, factorAlpha = 0.0f;
+  uint32_t slot = 0;
+  int32_t  index = 0, texCoord = 0;
+};
+static AlphaKey alphaKey(const MiGltfShadeMaterial& mat, const MiGltfTextureInfo* infos)
+{
+  AlphaKey k;
+  if(mat.alphaMode == MI_ALPHA_OPAQUE)
+    return k;
+  const bool sg = mat.pbrModel == MI_PBR_SPECULAR_GLOSSINESS;
+  k.alphaMode   = mat.alphaMode;
+  k.cutoff      = mat.alphaCutoff;
+  k.factorAlpha = sg ? mat.pbrDiffuseFactor[3] : mat.pbrBaseColorFactor[3];
+  k.slot        = sg ? mat.pbrDiffuseTexture : mat.pbrBaseColorTexture;
+  if(k.slot > 0)
+  {
+    k.index    = infos[k.slot].index;
+    k.texCoord = infos[k.slot].texCoord;
+  }
+  return k;
+}
+
+int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int numMaterials, const MiGltfTextureInfo* textureInfos, int numTextureInfos)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !materials || !textureInfos || numMaterials != int(pt->hostMaterials.size()))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_materials: the material count must be the one the instance was created with");
+  if(numTextureInfos <= 0)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_materials: the texture-info table needs the reserved slot 0");
+  {
+    std::string why;
+    if(!materialSlotsInRange(materials, numMaterials, numTextureInfos, why))
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_materials: " + why);
+  }
+  // ---- the diff, per material: what of the per-triangle data a build baked from it is now stale
+  const size_t         nm = size_t(numMaterials);
+  std::vector<uint8_t> newFlags(nm), newFeatures(nm), alphaChanged(nm, 0), flagsChanged(nm, 0);
+  bool                 anyAlpha = false, anyFlags = false, transmissiveChanged = false;
+  for(size_t m = 0; m < nm; ++m)
+  {
+    newFlags[m]    = materialInstFlags(materials[m]);
+    newFeatures[m] = materialFeatures(materials[m]);
+    const AlphaKey was = alphaKey(pt->hostMaterials[m], pt->hostTexInfos.data()), now = alphaKey(materials[m], textureInfos);
+    alphaChanged[m] = memcmp(&was, &now, sizeof(AlphaKey)) != 0;
+    flagsChanged[m] = newFlags[m] != pt->matInstFlags[m];
+    anyAlpha |= alphaChanged[m] != 0;
+    anyFlags |= flagsChanged[m] != 0;
+  }
+  const int numNodes = int(pt->hostNodes.size()), numPrims = int(pt->hostPrims.size());
+  auto      materialOf = [&](int n) { return size_t(std::max(0, std::min(pt->hostNodes[size_t(n)].materialID, numMaterials - 1))); };
+  for(int n = 0; n < numNodes; ++n)
+  {
+    const size_t m    = materialOf(n);
+    const int    prim = pt->hostNodes[size_t(n)].renderPrimID;
+    // the OPAQUE class of the load-time alpha cut was found under the old alpha state: its triangles skip the alpha test for good
+    if(alphaChanged[m] && prim >= 0 && prim < numPrims && pt->hostPrims[size_t(prim)].opaqueTriangles > 0)
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_materials: alpha state of a material whose geometry was cut at load: re-cut and re-create (material "
+                                          + std::to_string(m) + ", render node " + std::to_string(n) + ")");
+    if(((newFlags[m] ^ pt->matInstFlags[m]) & pt::INST_TRANSMISSIVE) != 0)
+      transmissiveChanged = true;
+  }
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still shade with the old tables
+  // ---- the tables, and what is derived from them per texture slot and per material
+  {
+    std::vector<pt::DevTexRef>  refs;
+    std::vector<pt::DevCoreTex> core;
+    deriveTextureRecords(pt, materials, numMaterials, textureInfos, numTextureInfos, refs, core);
+    if(size_t(numTextureInfos) != pt->texInfos.count)  // (the table grew or shrank: new buffers, taken over only when both exist)
+    {
+      DevBuf<MiGltfTextureInfo> infos;
+      DevBuf<pt::DevTexRef>     drefs;
+      HIP_TRY(infos.upload(textureInfos, size_t(numTextureInfos)));
+      HIP_TRY(drefs.upload(refs.data(), refs.size()));
+      std::swap(pt->texInfos.ptr, infos.ptr); std::swap(pt->texInfos.count, infos.count);
+      std::swap(pt->texRefs.ptr, drefs.ptr); std::swap(pt->texRefs.count, drefs.count);
+      pt->scene.texInfos = pt->texInfos.ptr;
+      pt->scene.texRefs  = pt->texRefs.ptr;
+    }
+    else
+    {
+      HIP_TRY(hipMemcpy(pt->texInfos.ptr, textureInfos, sizeof(MiGltfTextureInfo) * size_t(numTextureInfos), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(pt->texRefs.ptr, refs.data(), sizeof(pt::DevTexRef) * refs.size(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(pt->materials.ptr, materials, sizeof(MiGltfShadeMaterial) * nm, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->coreTex.ptr, core.data(), sizeof(pt::DevCoreTex) * core.size(), hipMemcpyHostToDevice));
+  }
+  pt->hostMaterials.assign(materials, materials + numMaterials);
+  pt->hostTexInfos.assign(textureInfos, textureInfos + numTextureInfos);
+  pt->matInstFlags = newFlags;
+  pt->matFeatures  = newFeatures;
+  pt->sceneDevDirty = true;
+  // ---- the scene-wide summaries, and the buffers they call for at the next render
+  const bool hadTransmissive = pt->hasTransmissive, wasSimple = pt->simpleMaterials;
+  const std::vector<uint8_t> flags = instanceFlags(pt);
+  auto followSummaries = [&]() -> int {
+    if(pt->simpleMaterials != wasSimple)  // the medium array comes back zeroed, on demand, when the generic shade kernel needs it (ensureOptionalPathArrays)
+    {
+      pt->optMedium.release();
+      pt->paths.medium = nullptr;
+    }
+    if(pt->hasTransmissive != hadTransmissive)  // the candidate pool and lists are part of the path resources
+    {
+      pt->candPool.release();
+      pt->candLists.release();
+      if(pt->width > 0)
+        return allocPathResources(pt, pt->framesCap);
+    }
+    return MI_PT_OK;
+  };
+  // ---- what the resident structure cannot take in place is rebuilt: the BVH2 walk (no patch path), and a transmissive bit that changes
+  // while the tree holds pre-split references (triangles of transmissive instances keep ONE reference: bvh_build.hip, k_split_refs)
+  if((anyAlpha || anyFlags) && pt->scene.numTris > 0 && (!pt->wide || (transmissiveChanged && pt->splitRefs)))
+  {
+    if(int rc = buildAcceleration(pt))
+      return rc;
+    return followSummaries();
+  }
+  if(pt->scene.numTris > 0)
+  {
+    HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    pt::DevScene& S          = pt->scene;
+    const bool    hadRecords = pt->alphaTris.ptr != nullptr;
+    if(!pt->hasAlpha)
+    {
+      pt->alphaTris.release();
+      S.alphaTris = nullptr;
+    }
+    else if(!hadRecords)
+      HIP_TRY(pt->alphaTris.alloc(size_t(S.numTris)));
+    // the dirty byte of every render node, from its material's classes; no launch when no byte is set (factor-only and UV-transform updates)
+    std::vector<uint8_t> dirty(size_t(std::max(numNodes, 1)), 0);
+    bool                 anyDirty = false;
+    for(int n = 0; n < numNodes; ++n)
+    {
+      const size_t m = materialOf(n);
+      dirty[size_t(n)] = uint8_t((flagsChanged[m] ? pt::MATERIAL_PATCH_FLAGS : 0) | (alphaChanged[m] && pt->hasAlpha && hadRecords ? pt::MATERIAL_PATCH_ALPHA : 0));
+      anyDirty |= dirty[size_t(n)] != 0;
+    }
+    if(anyDirty)
+    {
+      if(pt->matDirty.count != dirty.size())
+        HIP_TRY(pt->matDirty.alloc(dirty.size()));
+      HIP_TRY(hipMemcpy(pt->matDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+      pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris, hadRecords ? pt->alphaTris.ptr : nullptr, uint32_t(S.numTris), nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    if(pt->hasAlpha && !hadRecords)  // the scene had no alpha records: all of them, as a build makes them
+    {
+      pt::launchBuildAlphaRecords(S, uint32_t(S.numTris), pt->alphaTris.ptr, nullptr);
+      HIP_TRY(hipGetLastError());
+      S.alphaTris = pt->alphaTris.ptr;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  return followSummaries();
 }
 
 static void releaseDeformation(MiPt* pt)

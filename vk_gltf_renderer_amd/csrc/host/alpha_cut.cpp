@@ -113,6 +113,10 @@ uint64_t GltfScene::cutAlphaMasked(int subdivisions)
     const MiGltfShadeMaterial& mat = m_materials[size_t(mi)];
     if(mat.alphaMode != MI_ALPHA_MASK)
       continue;
+    // a material whose alpha state some KHR_animation_pointer channel animates (alphaCutoff, alphaMode, the base / diffuse colour factor or
+    // texture) stays whole: the classification below would hold for one moment of the clip only (mi_pt_update_materials refuses such an update)
+    if(size_t(mi) < m_alphaAnimated.size() && m_alphaAnimated[size_t(mi)])
+      continue;
     const bool     sg     = mat.pbrModel == MI_PBR_SPECULAR_GLOSSINESS;
     const uint16_t slot   = sg ? mat.pbrDiffuseTexture : mat.pbrBaseColorTexture;
     const float    factor = sg ? mat.pbrDiffuseFactor[3] : mat.pbrBaseColorFactor[3];

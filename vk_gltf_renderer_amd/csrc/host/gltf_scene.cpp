@@ -856,7 +856,7 @@ bool GltfScene::decompressMeshopt()
 }
 
 //----------------------------------------------------------------------------------------------------------------------
-uint16_t GltfScene::addTextureInfo(const Value& tinfo)  // reference: src/gltf_material_cache.cpp:60-98
+uint16_t GltfScene::addTextureInfo(const Value& tinfo, std::vector<MiGltfTextureInfo>& infos) const  // reference: src/gltf_material_cache.cpp:60-98
 {
   if(!tinfo.isObject())
     return 0;
@@ -886,8 +886,8 @@ uint16_t GltfScene::addTextureInfo(const Value& tinfo)  // reference: src/gltf_m
   ti.uvTransform[3] = c1[1];
   ti.uvTransform[4] = c0[2];
   ti.uvTransform[5] = c1[2];
-  uint16_t idx      = uint16_t(m_textureInfos.size());
-  m_textureInfos.push_back(ti);
+  uint16_t idx      = uint16_t(infos.size());
+  infos.push_back(ti);
   return idx;
 }
 
@@ -901,6 +901,7 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
   m_textureInfos.push_back(sentinel);
   m_materials.clear();
 
+  m_materialFirstInfo.clear();
   const Value& mats  = m_doc["materials"];
   size_t       count = std::max<size_t>(mats.size(), 1);  // at least one material (reference: src/gltf_scene.cpp:1391-1395)
   for(size_t i = 0; i < count; ++i)
@@ -910,7 +911,17 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
       v.type = Value::Object;
       return v;
     }();
-    const Value& src = i < mats.size() ? mats[i] : emptyObj;
+    m_materialFirstInfo.push_back(uint32_t(m_textureInfos.size()));
+    m_materials.push_back(convertMaterial(i < mats.size() ? mats[i] : emptyObj, m_textureInfos));
+  }
+  m_materialFirstInfo.push_back(uint32_t(m_textureInfos.size()));
+}
+
+// One glTF material -> one MiGltfShadeMaterial; its texture infos are appended to `infos` in a fixed order (so a material converted again
+// from a document whose values changed -- KHR_animation_pointer, gltf_scene_animation.cpp -- fills the same slots).
+MiGltfShadeMaterial GltfScene::convertMaterial(const Value& src, std::vector<MiGltfTextureInfo>& infos) const
+{
+  {
     MiGltfShadeMaterial d;
     memset(&d, 0, sizeof(d));
     // struct defaults (reference: shaders/gltf_scene_io.h.slang:147-310)
@@ -943,15 +954,15 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
     d.occlusionStrength  = getFloat(src["occlusionTexture"], "strength", 1.0f);
     getFloats(src, "emissiveFactor", 3, d.emissiveFactor);
 
-    d.emissiveTexture             = addTextureInfo(src["emissiveTexture"]);
-    d.normalTexture               = addTextureInfo(src["normalTexture"]);
-    d.pbrBaseColorTexture         = addTextureInfo(pbr["baseColorTexture"]);
-    d.pbrMetallicRoughnessTexture = addTextureInfo(pbr["metallicRoughnessTexture"]);
-    d.occlusionTexture            = addTextureInfo(src["occlusionTexture"]);
+    d.emissiveTexture             = addTextureInfo(src["emissiveTexture"], infos);
+    d.normalTexture               = addTextureInfo(src["normalTexture"], infos);
+    d.pbrBaseColorTexture         = addTextureInfo(pbr["baseColorTexture"], infos);
+    d.pbrMetallicRoughnessTexture = addTextureInfo(pbr["metallicRoughnessTexture"], infos);
+    d.occlusionTexture            = addTextureInfo(src["occlusionTexture"], infos);
 
     const Value& tr       = ext(src, "KHR_materials_transmission");
     d.transmissionFactor  = getFloat(tr, "transmissionFactor", 0.0f);
-    d.transmissionTexture = addTextureInfo(tr["transmissionTexture"]);
+    d.transmissionTexture = addTextureInfo(tr["transmissionTexture"], infos);
 
     d.ior = getFloat(ext(src, "KHR_materials_ior"), "ior", 1.5f);
 
@@ -959,20 +970,20 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
     getFloats(vol, "attenuationColor", 3, d.attenuationColor);
     d.thicknessFactor     = getFloat(vol, "thicknessFactor", 0.0f);
     d.attenuationDistance = getFloat(vol, "attenuationDistance", FLT_MAX);
-    d.thicknessTexture    = addTextureInfo(vol["thicknessTexture"]);
+    d.thicknessTexture    = addTextureInfo(vol["thicknessTexture"], infos);
 
     const Value& cc             = ext(src, "KHR_materials_clearcoat");
     d.clearcoatFactor           = getFloat(cc, "clearcoatFactor", 0.0f);
     d.clearcoatRoughness        = getFloat(cc, "clearcoatRoughnessFactor", 0.0f);
-    d.clearcoatRoughnessTexture = addTextureInfo(cc["clearcoatRoughnessTexture"]);
-    d.clearcoatTexture          = addTextureInfo(cc["clearcoatTexture"]);
-    d.clearcoatNormalTexture    = addTextureInfo(cc["clearcoatNormalTexture"]);
+    d.clearcoatRoughnessTexture = addTextureInfo(cc["clearcoatRoughnessTexture"], infos);
+    d.clearcoatTexture          = addTextureInfo(cc["clearcoatTexture"], infos);
+    d.clearcoatNormalTexture    = addTextureInfo(cc["clearcoatNormalTexture"], infos);
 
     const Value& sp  = ext(src, "KHR_materials_specular");
     d.specularFactor = getFloat(sp, "specularFactor", 1.0f);
     getFloats(sp, "specularColorFactor", 3, d.specularColorFactor);
-    d.specularTexture      = addTextureInfo(sp["specularTexture"]);
-    d.specularColorTexture = addTextureInfo(sp["specularColorTexture"]);
+    d.specularTexture      = addTextureInfo(sp["specularTexture"], infos);
+    d.specularColorTexture = addTextureInfo(sp["specularColorTexture"], infos);
 
     float strength = getFloat(ext(src, "KHR_materials_emissive_strength"), "emissiveStrength", 1.0f);
     for(int c = 0; c < 3; ++c)
@@ -985,21 +996,21 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
     d.iridescenceIor              = getFloat(ir, "iridescenceIor", 1.3f);
     d.iridescenceThicknessMinimum = getFloat(ir, "iridescenceThicknessMinimum", 100.0f);
     d.iridescenceThicknessMaximum = getFloat(ir, "iridescenceThicknessMaximum", 400.0f);
-    d.iridescenceTexture          = addTextureInfo(ir["iridescenceTexture"]);
-    d.iridescenceThicknessTexture = addTextureInfo(ir["iridescenceThicknessTexture"]);
+    d.iridescenceTexture          = addTextureInfo(ir["iridescenceTexture"], infos);
+    d.iridescenceThicknessTexture = addTextureInfo(ir["iridescenceThicknessTexture"], infos);
 
     const Value& an         = ext(src, "KHR_materials_anisotropy");
     float        anRotation = getFloat(an, "anisotropyRotation", 0.0f);
     d.anisotropyRotation[0] = std::sin(anRotation);
     d.anisotropyRotation[1] = std::cos(anRotation);
     d.anisotropyStrength    = getFloat(an, "anisotropyStrength", 0.0f);
-    d.anisotropyTexture     = addTextureInfo(an["anisotropyTexture"]);
+    d.anisotropyTexture     = addTextureInfo(an["anisotropyTexture"], infos);
 
     const Value& sh = ext(src, "KHR_materials_sheen");
     getFloats(sh, "sheenColorFactor", 3, d.sheenColorFactor);
     d.sheenRoughnessFactor  = getFloat(sh, "sheenRoughnessFactor", 0.0f);
-    d.sheenColorTexture     = addTextureInfo(sh["sheenColorTexture"]);
-    d.sheenRoughnessTexture = addTextureInfo(sh["sheenRoughnessTexture"]);
+    d.sheenColorTexture     = addTextureInfo(sh["sheenColorTexture"], infos);
+    d.sheenRoughnessTexture = addTextureInfo(sh["sheenRoughnessTexture"], infos);
 
     d.dispersion = getFloat(ext(src, "KHR_materials_dispersion"), "dispersion", 0.0f);
 
@@ -1011,24 +1022,24 @@ void GltfScene::buildMaterials()  // reference: src/gltf_material_cache.cpp:103-
       getFloats(sg, "specularFactor", 3, d.pbrSpecularFactor);
       d.pbrGlossinessFactor = getFloat(sg, "glossinessFactor", 1.0f);
     }
-    d.pbrDiffuseTexture            = addTextureInfo(sg["diffuseTexture"]);
-    d.pbrSpecularGlossinessTexture = addTextureInfo(sg["specularGlossinessTexture"]);
+    d.pbrDiffuseTexture            = addTextureInfo(sg["diffuseTexture"], infos);
+    d.pbrSpecularGlossinessTexture = addTextureInfo(sg["specularGlossinessTexture"], infos);
 
     const Value& dt             = ext(src, "KHR_materials_diffuse_transmission");
     d.diffuseTransmissionFactor = getFloat(dt, "diffuseTransmissionFactor", 0.0f);
     getFloats(dt, "diffuseTransmissionColorFactor", 3, d.diffuseTransmissionColor);
-    d.diffuseTransmissionTexture      = addTextureInfo(dt["diffuseTransmissionTexture"]);
-    d.diffuseTransmissionColorTexture = addTextureInfo(dt["diffuseTransmissionColorTexture"]);
+    d.diffuseTransmissionTexture      = addTextureInfo(dt["diffuseTransmissionTexture"], infos);
+    d.diffuseTransmissionColorTexture = addTextureInfo(dt["diffuseTransmissionColorTexture"], infos);
 
     const Value& rr          = ext(src, "KHR_materials_retroreflection");
     d.retroreflectionFactor  = getFloat(rr, "retroreflectionFactor", 0.0f);
-    d.retroreflectionTexture = addTextureInfo(rr["retroreflectionTexture"]);
+    d.retroreflectionTexture = addTextureInfo(rr["retroreflectionTexture"], infos);
 
     const Value& vs = ext(src, "KHR_materials_volume_scatter");
     getFloats(vs, "multiscatterColor", 3, d.multiscatterColorFactor);
     d.scatterAnisotropy = getFloat(vs, "scatterAnisotropy", 0.0f);
 
-    m_materials.push_back(d);
+    return d;
   }
 }
 
@@ -1259,26 +1270,10 @@ void GltfScene::traverse(int nodeID, const mx::mat4& parent, bool parentVisible,
       const Value& gl = lights[size_t(li)];
       MiGltfLight  info{};
       placeLight(info, world);
-      info.innerAngle   = getFloat(gl["spot"], "innerConeAngle", 0.0f);
-      info.outerAngle   = getFloat(gl["spot"], "outerConeAngle", 0.7853981633974483f);
-      info.color[0] = info.color[1] = info.color[2] = 1.0f;
-      getFloats(gl, "color", 3, info.color);
-      info.intensity       = getFloat(gl, "intensity", 1.0f);
-      std::string type     = gl["type"].string("directional");
-      info.type            = type == "point" ? MI_LIGHT_POINT : (type == "spot" ? MI_LIGHT_SPOT : MI_LIGHT_DIRECTIONAL);
-      info.radius          = getFloat(gl["extras"], "radius", 0.0f);
-      if(info.type == MI_LIGHT_DIRECTIONAL)
-      {
-        const double sunDistance  = 149597870.0;  // km
-        info.angularSizeOrInvRange = float(2.0 * std::atan(double(info.radius) / sunDistance));
-      }
-      else
-      {
-        double range               = gl["range"].number(0.0);
-        info.angularSizeOrInvRange = range > 0.0 ? 1.0f / float(range) : 0.0f;
-      }
+      lightProperties(gl, info);
       m_lights.push_back(info);
       m_lightNode.push_back(nodeID);
+      m_lightIndex.push_back(li);
       m_lightPath.push_back(m_curPath);
     }
   }
@@ -1378,6 +1373,29 @@ mx::mat4 GltfScene::localMatrix(int nodeID) const
   return nodeLocalMatrix(m_doc["nodes"][size_t(nodeID)]);
 }
 
+// What a KHR_lights_punctual light says of itself (everything but the placement); again after a KHR_animation_pointer channel changed it
+void GltfScene::lightProperties(const Value& gl, MiGltfLight& info) const
+{
+  info.innerAngle   = getFloat(gl["spot"], "innerConeAngle", 0.0f);
+  info.outerAngle   = getFloat(gl["spot"], "outerConeAngle", 0.7853981633974483f);
+  info.color[0] = info.color[1] = info.color[2] = 1.0f;
+  getFloats(gl, "color", 3, info.color);
+  info.intensity       = getFloat(gl, "intensity", 1.0f);
+  std::string type     = gl["type"].string("directional");
+  info.type            = type == "point" ? MI_LIGHT_POINT : (type == "spot" ? MI_LIGHT_SPOT : MI_LIGHT_DIRECTIONAL);
+  info.radius          = getFloat(gl["extras"], "radius", 0.0f);
+  if(info.type == MI_LIGHT_DIRECTIONAL)
+  {
+    const double sunDistance  = 149597870.0;  // km
+    info.angularSizeOrInvRange = float(2.0 * std::atan(double(info.radius) / sunDistance));
+  }
+  else
+  {
+    double range               = gl["range"].number(0.0);
+    info.angularSizeOrInvRange = range > 0.0 ? 1.0f / float(range) : 0.0f;
+  }
+}
+
 // reference: src/gltf_scene.cpp:2269-2300 (position = the node's origin, direction = its -Z axis)
 void GltfScene::placeLight(MiGltfLight& info, const mx::mat4& world) const
 {
@@ -1387,6 +1405,31 @@ void GltfScene::placeLight(MiGltfLight& info, const mx::mat4& world) const
   info.direction[0] = -world.at(2, 0);
   info.direction[1] = -world.at(2, 1);
   info.direction[2] = -world.at(2, 2);
+}
+
+// Projection of a glTF camera (again after a KHR_animation_pointer channel changed it; aspectRatio is the viewport's, as in the reference)
+void GltfScene::cameraIntrinsics(const Value& tcam, RenderCamera& cam) const
+{
+  if(tcam["type"].string("perspective") == "perspective")
+  {
+    const Value& p = tcam["perspective"];
+    cam.type       = RenderCamera::ePerspective;
+    cam.znear      = p["znear"].number(0.1);
+    cam.zfar       = p["zfar"].number(0.0);
+    cam.yfov       = p["yfov"].number(0.785398);
+  }
+  else
+  {
+    const Value& o = tcam["orthographic"];
+    cam.type       = RenderCamera::eOrthographic;
+    cam.znear      = o["znear"].number(0.1);
+    cam.zfar       = o["zfar"].number(0.0);
+    cam.xmag       = o["xmag"].number(1.0);
+    cam.ymag       = o["ymag"].number(1.0);
+  }
+  float radius = boundsRadius();
+  if(cam.zfar <= cam.znear)
+    cam.zfar = std::max(cam.znear * 2.0, 4.0 * double(radius));
 }
 
 void GltfScene::traverseCameras(int nodeID, const mx::mat4& parent)  // reference: src/gltf_scene.cpp:2215-2267
@@ -1401,26 +1444,7 @@ void GltfScene::traverseCameras(int nodeID, const mx::mat4& parent)  // referenc
   {
     const Value& tcam = m_doc["cameras"][size_t(camID)];
     RenderCamera cam;
-    if(tcam["type"].string("perspective") == "perspective")
-    {
-      const Value& p = tcam["perspective"];
-      cam.type       = RenderCamera::ePerspective;
-      cam.znear      = p["znear"].number(0.1);
-      cam.zfar       = p["zfar"].number(0.0);
-      cam.yfov       = p["yfov"].number(0.785398);
-    }
-    else
-    {
-      const Value& o = tcam["orthographic"];
-      cam.type       = RenderCamera::eOrthographic;
-      cam.znear      = o["znear"].number(0.1);
-      cam.zfar       = o["zfar"].number(0.0);
-      cam.xmag       = o["xmag"].number(1.0);
-      cam.ymag       = o["ymag"].number(1.0);
-    }
-    float radius = boundsRadius();
-    if(cam.zfar <= cam.znear)
-      cam.zfar = std::max(cam.znear * 2.0, 4.0 * double(radius));
+    cameraIntrinsics(tcam, cam);
     // extractCameraVectors (reference: src/gltf_scene.cpp:2170-2182)
     mx::vec3 eye{world.at(3, 0), world.at(3, 1), world.at(3, 2)};
     mx::vec3 forward{-world.at(2, 0), -world.at(2, 1), -world.at(2, 2)};
@@ -1444,6 +1468,7 @@ void GltfScene::traverseCameras(int nodeID, const mx::mat4& parent)  // referenc
       getD3("camera::up", cam.up);
     }
     m_cameras.push_back(cam);
+    m_cameraIndex.push_back(camID);
   }
   const Value& children = node["children"];
   for(size_t c = 0; c < children.size(); ++c)
@@ -1473,6 +1498,8 @@ bool GltfScene::parse(const std::string& baseDir)  // reference: src/gltf_scene.
   m_gpuInstanceLocalMatrices.clear();
   m_renderNodeSource.clear();
   m_lightNode.clear();
+  m_lightIndex.clear();
+  m_cameraIndex.clear();
   m_lightPath.clear();
   m_curPath.clear();
   m_roots.clear();
@@ -1581,6 +1608,7 @@ bool GltfScene::parse(const std::string& baseDir)  // reference: src/gltf_scene.
     cam.zfar   = double(radius * 10.0f);
     cam.znear  = double(radius * 0.1f);
     m_cameras.push_back(cam);
+    m_cameraIndex.push_back(-1);
   }
   finalizeDesc();
   return true;

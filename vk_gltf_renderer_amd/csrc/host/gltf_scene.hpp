@@ -5,7 +5,8 @@
 // src/gltf_material_cache.cpp:103-260; src/gltf_scene_vk.cpp:493-501, :741-870, :909-947, :1102-1154, :1354-1392).
 // Keyframe animation of node transforms (gltf_scene_animation.cpp here; reference: src/gltf_scene_animation.cpp:355-700) feeds
 // mi_pt_update_render_nodes / mi_pt_update_lights; skins and morph targets (same file; reference: src/gltf_scene_animation.cpp:196-320)
-// feed mi_pt_update_deformation.  Editing, saving, merging, KHR_animation_pointer and the variants UI are out of scope.
+// feed mi_pt_update_deformation; KHR_animation_pointer channels (same file; reference: src/gltf_animation_pointer.cpp) rewrite the material, light,
+// camera and visibility tables and feed mi_pt_update_materials.  Editing, saving, merging and the variants UI are out of scope.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -80,10 +81,14 @@ public:
   uint32_t recomputeTangents(bool forceCreation, bool mikktspace);
   // Animation clips (translation / rotation / scale channels; LINEAR, STEP, CUBICSPLINE).  updateAnimation evaluates clip `index`
   // at its info's currentTime, recomputes the world matrices and rewrites the matrices of renderNodes() and the placement of
-  // lights() IN PLACE (same order, same count, desc() pointers stay valid).  Returns true when something moved.
+  // lights() IN PLACE (same order, same count, desc() pointers stay valid); KHR_animation_pointer channels rewrite materials(),
+  // textureInfos(), lights(), cameras() and renderNodeVisible() in place likewise.  Returns 1 when a channel was applied, 0 when none
+  // covered the time, -1 (error() set, nothing changed) when a pointer channel would change the number of texture infos.
+  // lastAnimationChanges(): MI_SCENE_CHANGED_* of the last updateAnimation.
   int            numAnimations() const { return int(m_animations.size()); }
   AnimationInfo& animationInfo(int index) { return m_animations[size_t(index)].info; }
-  bool           updateAnimation(int index);
+  int            updateAnimation(int index);
+  int            lastAnimationChanges() const { return m_lastChanges; }
   // Skins and morph targets (see mi_host.h: mi_scene_deformation).  deformation() is NULL when nothing deforms; deformOnHost writes the
   // posed vertices of the current frame tables into renderPrimitives() and returns the number of primitives deformed.
   const MiPtDeformDesc* deformation() const { return m_deform.empty() ? nullptr : &m_deformDesc; }
@@ -112,7 +117,10 @@ private:
   void traverse(int nodeID, const mx::mat4& parent, bool parentVisible, const std::map<std::string, int>& primMap);
   void traverseCameras(int nodeID, const mx::mat4& parent);
   void finalizeDesc();
-  uint16_t addTextureInfo(const mijson::Value& texInfo);
+  uint16_t addTextureInfo(const mijson::Value& texInfo, std::vector<MiGltfTextureInfo>& infos) const;
+  MiGltfShadeMaterial convertMaterial(const mijson::Value& src, std::vector<MiGltfTextureInfo>& infos) const;
+  void     lightProperties(const mijson::Value& light, MiGltfLight& info) const;
+  void     cameraIntrinsics(const mijson::Value& camera, RenderCamera& cam) const;
   mx::mat4 localMatrix(int nodeID) const;
   void     parseAnimations();
   void     parseDeformation();
@@ -129,9 +137,14 @@ private:
   };
   struct AnimationChannel
   {
-    enum Path { eTranslation, eRotation, eScale, eWeights } path = eTranslation;
+    enum Path { eTranslation, eRotation, eScale, eWeights, ePointer } path = eTranslation;
     int node = -1, sampler = 0;
     int numWeights = 0;  // eWeights: values per keyframe (the morph targets the channel drives)
+    // ePointer (KHR_animation_pointer), resolved at parse: what the pointer addresses, its index, and the keys from the document root
+    // down to the property (node TRS pointers become eTranslation / eRotation / eScale channels instead)
+    enum Target { eMaterial, eLight, eCamera, eVisibility } target = eMaterial;
+    int                      index = -1;
+    std::vector<std::string> keys;
   };
   struct Animation
   {
@@ -156,6 +169,11 @@ private:
   std::vector<NodePose>         m_nodePose;
   std::vector<RenderNodeSource> m_renderNodeSource;
   std::vector<int>              m_lightNode, m_roots;
+  std::vector<int>              m_lightIndex, m_cameraIndex;  // per light / camera of the tables: its index in the document (-1: the default camera)
+  std::vector<uint32_t>         m_materialFirstInfo;          // per material (+ the end): its first texture info; they are contiguous
+  std::vector<uint8_t>          m_alphaAnimated;              // per material: a pointer channel of some clip targets its alpha state (never cut)
+  int                           m_lastChanges = 0;
+  bool resolvePointer(const std::string& pointer, int components, AnimationChannel& ch);
   AlphaCutStats                 m_alphaCutStats;
   bool                          m_alphaCutDone = false;
   std::vector<uint8_t>          m_onPath;  // nodes on the current traversal path (cycle guard)

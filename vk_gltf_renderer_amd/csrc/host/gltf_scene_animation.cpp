@@ -9,7 +9,15 @@
 // Skins and morph targets (parseDeformation, reference: src/gltf_scene_animation.cpp:196-320): the vertex data they change is deformed
 // on the device (mi_pt_update_deformation, csrc/device/deform.hip) from the per-frame tables built here -- joint matrices
 // inverse(world[refNode]) * world[joint] * IBM (reference: src/gltf_scene_animation_vk.cpp:454-478) and the mesh weights -- or on the
-// host by deformOnHost, the CPU restatement of that kernel.  KHR_animation_pointer channels are skipped.
+// host by deformOnHost, the CPU restatement of that kernel.
+// KHR_animation_pointer (reference: src/gltf_animation_pointer.cpp, src/gltf_scene_animation.cpp:373-437): a channel whose target path is
+// "pointer" addresses a property of the document by JSON pointer; SCALAR / VEC2 / VEC3 / VEC4 outputs, all three samplers componentwise.
+// Pointers are resolved once, at parse (resolvePointer): materials, KHR_lights_punctual lights, cameras, KHR_node_visibility and -- which the
+// reference parses but drops in syncNode (:371-397) although the extension allows them -- node translation / rotation / scale, routed into
+// the pose code of the core channels (`weights` by pointer is not evaluated).  A material, light or camera value is written into the document
+// (the reference's shadow JSON) and the ONE conversion of the loader runs again for that object, so every property the loader understands
+// animates; the tables are rewritten in place.  Unresolvable pointers, out-of-range indices and outputs whose width does not fit the property
+// are dropped at parse: scene files are untrusted.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -18,6 +26,7 @@
 #include <set>
 
 #include "gltf_scene.hpp"
+#include "mi_host.h"  // MI_SCENE_CHANGED_*
 
 namespace mihost {
 
@@ -41,8 +50,231 @@ float AnimationInfo::incrementTime(float deltaTime, bool loop)  // reference: sr
   return currentTime;
 }
 
+namespace {
+
+std::vector<std::string> splitPointer(const std::string& p)  // RFC 6901: "/a/b" -> {a, b}, ~1 = '/', ~0 = '~'
+{
+  std::vector<std::string> out;
+  if(p.empty() || p[0] != '/')
+    return out;
+  std::string cur;
+  for(size_t i = 1; i <= p.size(); ++i)
+  {
+    if(i == p.size() || p[i] == '/')
+    {
+      out.push_back(cur);
+      cur.clear();
+    }
+    else if(p[i] == '~' && i + 1 < p.size() && (p[i + 1] == '0' || p[i + 1] == '1'))
+      cur += p[++i] == '1' ? '/' : '~';
+    else
+      cur += p[i];
+  }
+  return out;
+}
+bool parseIndex(const std::string& s, size_t count, int& out)
+{
+  if(s.empty() || s.size() > 9)
+    return false;
+  for(char c : s)
+    if(c < '0' || c > '9')
+      return false;
+  const long v = std::strtol(s.c_str(), nullptr, 10);
+  if(size_t(v) >= count)
+    return false;
+  out = int(v);
+  return true;
+}
+const Value* findKey(const Value& o, const std::string& key)
+{
+  return o.isObject() ? o.find(key) : nullptr;
+}
+// The components a material property takes when the document does not hold it yet (glTF 2.0 and the KHR_materials_* / KHR_texture_transform
+// schemas): by its key, and by the object it lives in where a key has two meanings.
+int materialPropertyWidth(const std::vector<std::string>& keys)
+{
+  const std::string& key    = keys.back();
+  const std::string  parent = keys.size() >= 2 ? keys[keys.size() - 2] : std::string();
+  if(parent == "KHR_texture_transform")
+    return (key == "offset" || key == "scale") ? 2 : 1;
+  if(key == "baseColorFactor" || key == "diffuseFactor")
+    return 4;
+  if(key == "specularFactor")
+    return parent == "KHR_materials_pbrSpecularGlossiness" ? 3 : 1;
+  if(key == "emissiveFactor" || key == "attenuationColor" || key == "specularColorFactor" || key == "sheenColorFactor"
+     || key == "diffuseTransmissionColorFactor" || key == "multiscatterColor")
+    return 3;
+  return 1;
+}
+// Writes `n` floats at keys[from ...] below `at`, creating absent objects on the way (a number for n == 1, an array otherwise; a bool for
+// `asBool`).  Array elements on the way must exist.  False (and nothing written) when the way leads through something that is not a container.
+bool writeValue(Value& at, const std::vector<std::string>& keys, size_t from, const float* v, int n, bool asBool)
+{
+  Value* cur = &at;
+  for(size_t k = from; k < keys.size(); ++k)
+  {
+    if(cur->type == Value::Array)
+    {
+      int i = 0;
+      if(!parseIndex(keys[k], cur->arr.size(), i))
+        return false;
+      cur = &cur->arr[size_t(i)];
+      continue;
+    }
+    if(cur->type == Value::Null)
+      cur->type = Value::Object;
+    if(cur->type != Value::Object)
+      return false;
+    Value* next = nullptr;
+    for(auto& kv : cur->obj)
+      if(kv.first == keys[k])
+        next = &kv.second;
+    if(!next)
+    {
+      cur->obj.emplace_back(keys[k], Value());
+      next = &cur->obj.back().second;
+    }
+    cur = next;
+  }
+  Value out;
+  if(asBool)
+  {
+    out.type = Value::Bool;
+    out.b    = v[0] != 0.0f;  // (reference: src/gltf_animation_pointer.cpp:155)
+  }
+  else if(n == 1)
+  {
+    out.type = Value::Number;
+    out.num  = double(v[0]);
+  }
+  else
+  {
+    out.type = Value::Array;
+    out.arr.resize(size_t(n));
+    for(int c = 0; c < n; ++c)
+    {
+      out.arr[size_t(c)].type = Value::Number;
+      out.arr[size_t(c)].num  = double(v[c]);
+    }
+  }
+  *cur = std::move(out);
+  return true;
+}
+
+}  // namespace
+
+// Resolves a KHR_animation_pointer target once (reference: parseResourceInfo, src/gltf_animation_pointer.cpp:103-139).  True: `ch` is a usable
+// channel -- a pointer channel with target / index / keys, or, for /nodes/i/{translation, rotation, scale}, a core channel on node i.
+bool GltfScene::resolvePointer(const std::string& pointer, int components, AnimationChannel& ch)
+{
+  const std::vector<std::string> keys = splitPointer(pointer);
+  if(keys.size() < 3 || components < 1 || components > 4)
+    return false;
+  // the property as the document holds it, if it does: a number or an array of numbers, whose width the output must have
+  auto widthInDocument = [&](int& width) -> bool {  // false: the way is blocked (not a container, or a value that is neither number nor array)
+    const Value* cur = &m_doc;
+    width            = 0;
+    for(size_t k = 0; k < keys.size(); ++k)
+    {
+      if(cur->isArray())
+      {
+        int i = 0;
+        if(!parseIndex(keys[k], cur->arr.size(), i))
+          return false;
+        cur = &cur->arr[size_t(i)];
+      }
+      else if(cur->isObject())
+      {
+        cur = findKey(*cur, keys[k]);
+        if(!cur)
+          return true;  // absent from here on: created at the first write
+      }
+      else
+        return false;
+    }
+    if(cur->isNumber())
+      width = 1;
+    else if(cur->isArray() && !cur->arr.empty() && cur->arr.size() <= 4)
+    {
+      for(const Value& e : cur->arr)
+        if(!e.isNumber())
+          return false;
+      width = int(cur->arr.size());
+    }
+    else if(cur->type == Value::Bool && ch.target == AnimationChannel::eVisibility)
+      width = 1;
+    else
+      return false;
+    return true;
+  };
+  int index = -1, width = 0;
+  if(keys[0] == "materials" && parseIndex(keys[1], m_doc["materials"].size(), index))
+  {
+    ch.target = AnimationChannel::eMaterial;
+    if(!widthInDocument(width))
+      return false;
+    if(width == 0)
+      width = materialPropertyWidth(keys);
+    if(width != components)
+      return false;
+    // its alpha state: never cut by cutAlphaMasked
+    bool alpha = keys.back() == "alphaCutoff" || keys.back() == "alphaMode";
+    for(const std::string& k : keys)
+      alpha = alpha || k == "baseColorFactor" || k == "diffuseFactor" || k == "baseColorTexture" || k == "diffuseTexture";
+    if(alpha)
+    {
+      m_alphaAnimated.resize(std::max(m_alphaAnimated.size(), m_materials.size()), 0);
+      if(size_t(index) < m_alphaAnimated.size())
+        m_alphaAnimated[size_t(index)] = 1;
+    }
+  }
+  else if(keys[0] == "extensions" && keys.size() >= 5 && keys[1] == "KHR_lights_punctual" && keys[2] == "lights"
+          && parseIndex(keys[3], m_doc["extensions"]["KHR_lights_punctual"]["lights"].size(), index))
+  {
+    ch.target = AnimationChannel::eLight;
+    const std::string& k = keys[4];
+    if(keys.size() == 5 && k == "color")
+      width = 3;
+    else if(keys.size() == 5 && (k == "intensity" || k == "range"))
+      width = 1;
+    else if(keys.size() == 6 && k == "spot" && (keys[5] == "innerConeAngle" || keys[5] == "outerConeAngle"))
+      width = 1;
+    else
+      return false;
+    if(width != components)
+      return false;
+  }
+  else if(keys[0] == "cameras" && keys.size() == 4 && parseIndex(keys[1], m_doc["cameras"].size(), index))
+  {
+    ch.target = AnimationChannel::eCamera;
+    const std::string &g = keys[2], &k = keys[3];
+    const bool persp = g == "perspective" && (k == "yfov" || k == "aspectRatio" || k == "znear" || k == "zfar");
+    const bool ortho = g == "orthographic" && (k == "xmag" || k == "ymag" || k == "znear" || k == "zfar");
+    if((!persp && !ortho) || components != 1)
+      return false;
+  }
+  else if(keys[0] == "nodes" && parseIndex(keys[1], m_doc["nodes"].size(), index))
+  {
+    if(keys.size() == 3 && (keys[2] == "translation" || keys[2] == "rotation" || keys[2] == "scale"))
+    {
+      ch.path = keys[2] == "translation" ? AnimationChannel::eTranslation : (keys[2] == "rotation" ? AnimationChannel::eRotation : AnimationChannel::eScale);
+      ch.node = index;
+      return true;  // (the caller checks the width like a core channel's)
+    }
+    if(!(keys.size() == 5 && keys[2] == "extensions" && keys[3] == "KHR_node_visibility" && keys[4] == "visible") || components != 1)
+      return false;
+    ch.target = AnimationChannel::eVisibility;
+  }
+  else
+    return false;
+  ch.index = index;
+  ch.keys  = keys;
+  return true;
+}
+
 void GltfScene::parseAnimations()
 {
+  m_alphaAnimated.assign(m_materials.size(), 0);
   const Value& anims = m_doc["animations"];
   for(size_t a = 0; a < anims.size(); ++a)
   {
@@ -96,11 +328,26 @@ void GltfScene::parseAnimations()
         ch.path = AnimationChannel::eScale;
       else if(path == "weights")
         ch.path = AnimationChannel::eWeights;
+      else if(path == "pointer")
+        ch.path = AnimationChannel::ePointer;
       else
-        continue;  // pointer
+        continue;
       ch.node    = gc["target"]["node"].integer(-1);
       ch.sampler = gc["sampler"].integer(-1);
-      if(ch.node < 0 || size_t(ch.node) >= m_nodePose.size() || ch.sampler < 0 || size_t(ch.sampler) >= anim.samplers.size())
+      if(ch.sampler < 0 || size_t(ch.sampler) >= anim.samplers.size())
+        continue;
+      if(ch.path == AnimationChannel::ePointer)
+      {
+        const Value& ptr = gc["target"]["extensions"]["KHR_animation_pointer"]["pointer"];
+        if(!ptr.isString() || !resolvePointer(ptr.str, anim.samplers[size_t(ch.sampler)].components, ch))
+          continue;
+        if(ch.path == AnimationChannel::ePointer)  // (node TRS pointers became core channels and go on below)
+        {
+          anim.channels.push_back(ch);
+          continue;
+        }
+      }
+      if(ch.node < 0 || size_t(ch.node) >= m_nodePose.size())
         continue;
       if(ch.path == AnimationChannel::eWeights)
       {
@@ -161,36 +408,39 @@ void slerpNormalized(const float* a, const float* b, float t, float* out)
 
 }  // namespace
 
-bool GltfScene::updateAnimation(int index)
+int GltfScene::updateAnimation(int index)
 {
+  m_lastChanges = 0;
   if(index < 0 || size_t(index) >= m_animations.size())
-    return false;
+    return 0;
   const Animation& anim = m_animations[size_t(index)];
   const float      time = anim.info.currentTime;
-  bool             any  = false, anyWeights = false;
+  bool             any  = false, anyWeights = false, anyPointer = false;
 
-  for(const AnimationChannel& ch : anim.channels)
-  {
+  // The value of a channel at `time` into vbuf (at least 4 floats; nc of them count): false when the time lies outside its keyframe range or
+  // the sampler is unusable.
+  auto sample = [&](const AnimationChannel& ch, std::vector<float>& vbuf, int& ncOut) -> bool {
     const AnimationSampler& sm = anim.samplers[size_t(ch.sampler)];
     const size_t            nk = sm.inputs.size();
     if(nk < 2)
-      continue;
+      return false;
     // the segment [i, i+1] that holds `time` (first keyframe strictly after it, minus one)
     auto it = std::upper_bound(sm.inputs.begin(), sm.inputs.end(), time);
     if(it == sm.inputs.begin())
-      continue;
+      return false;
     size_t i = size_t(it - sm.inputs.begin()) - 1;
     if(i + 1 >= nk)
       i = nk - 2;
     const float t0 = sm.inputs[i], t1 = sm.inputs[i + 1];
     if(!(time >= t0 && time <= t1))
-      continue;
+      return false;
     const float keyDelta = t1 - t0;
     const float t        = std::fabs(keyDelta) < std::numeric_limits<float>::epsilon() ? 0.0f : std::min(std::max((time - t0) / keyDelta, 0.0f), 1.0f);
     const bool  weights  = ch.path == AnimationChannel::eWeights;
     const int   nc       = weights ? ch.numWeights : sm.components;
     const size_t numOut  = sm.outputs.size() / size_t(nc);
-    std::vector<float> vbuf(size_t(std::max(nc, 4)), 0.0f);
+    vbuf.assign(size_t(std::max(nc, 4)), 0.0f);
+    ncOut                = nc;
     float*      v        = vbuf.data();
     v[3]                 = weights ? v[3] : 1.0f;
     bool        have     = false;
@@ -237,8 +487,84 @@ bool GltfScene::updateAnimation(int index)
         }
         break;
     }
-    if(!have)
+    return have;
+  };
+
+  // ---- KHR_animation_pointer on materials, first: the one step that can fail, and nothing else may have changed when it does.  The values
+  // go into the document, the dirty materials through the loader's conversion again, into the slots they hold.
+  std::vector<float> vbuf;
+  int                nc = 0;
+  {
+    auto materialJson = [&](int m) -> Value* {
+      for(auto& kv : m_doc.obj)
+        if(kv.first == "materials" && kv.second.isArray() && size_t(m) < kv.second.arr.size())
+          return &kv.second.arr[size_t(m)];
+      return nullptr;
+    };
+    std::map<int, Value> saved;  // the dirty materials as the document held them
+    for(const AnimationChannel& ch : anim.channels)
+    {
+      if(ch.path != AnimationChannel::ePointer || ch.target != AnimationChannel::eMaterial || !sample(ch, vbuf, nc))
+        continue;
+      Value* json = materialJson(ch.index);
+      if(!json || size_t(ch.index) + 1 >= m_materialFirstInfo.size())
+        continue;
+      if(!saved.count(ch.index))
+        saved.emplace(ch.index, *json);
+      writeValue(m_doc, ch.keys, 0, vbuf.data(), nc, false);
+    }
+    std::map<int, std::pair<MiGltfShadeMaterial, std::vector<MiGltfTextureInfo>>> converted;
+    bool                                                                          fits = true;
+    for(const auto& kv : saved)
+    {
+      const uint32_t first = m_materialFirstInfo[size_t(kv.first)], end = m_materialFirstInfo[size_t(kv.first) + 1];
+      std::vector<MiGltfTextureInfo> infos(first);  // (placeholders: the material's slot indices come out as they are in the table)
+      const MiGltfShadeMaterial      d = convertMaterial(*materialJson(kv.first), infos);
+      fits                             = fits && infos.size() == end;
+      converted[kv.first]              = {d, std::vector<MiGltfTextureInfo>(infos.begin() + std::min<size_t>(first, infos.size()), infos.end())};
+    }
+    if(!fits)
+    {
+      for(const auto& kv : saved)
+        *materialJson(kv.first) = kv.second;
+      m_error = "updateAnimation: a KHR_animation_pointer channel would change the number of texture infos";
+      return -1;
+    }
+    for(const auto& kv : converted)
+    {
+      m_materials[size_t(kv.first)] = kv.second.first;
+      std::copy(kv.second.second.begin(), kv.second.second.end(), m_textureInfos.begin() + m_materialFirstInfo[size_t(kv.first)]);
+    }
+    if(!converted.empty())
+    {
+      anyPointer = true;
+      m_lastChanges |= MI_SCENE_CHANGED_MATERIALS;
+    }
+  }
+
+  std::set<int> lightsDirty, camerasDirty;
+  bool          visibilityDirty = false;
+  for(const AnimationChannel& ch : anim.channels)
+  {
+    if(ch.path == AnimationChannel::ePointer && ch.target == AnimationChannel::eMaterial)
       continue;
+    if(!sample(ch, vbuf, nc))
+      continue;
+    float*     v       = vbuf.data();
+    const bool weights = ch.path == AnimationChannel::eWeights;
+    if(ch.path == AnimationChannel::ePointer)
+    {
+      if(!writeValue(m_doc, ch.keys, 0, v, nc, ch.target == AnimationChannel::eVisibility))
+        continue;
+      if(ch.target == AnimationChannel::eLight)
+        lightsDirty.insert(ch.index);
+      else if(ch.target == AnimationChannel::eCamera)
+        camerasDirty.insert(ch.index);
+      else
+        visibilityDirty = true;
+      anyPointer = true;
+      continue;
+    }
     if(weights)
     {
       std::vector<float>& mw = m_meshWeights[size_t(m_doc["nodes"][size_t(ch.node)]["mesh"].integer(-1))];
@@ -266,12 +592,48 @@ bool GltfScene::updateAnimation(int index)
     memcpy(dst, v, sizeof(float) * size_t(nc));
     any = true;
   }
+  // ---- what the pointer channels changed, through the loader's own conversions (placement stays with the node path)
+  if(!lightsDirty.empty())
+  {
+    const Value& lights = m_doc["extensions"]["KHR_lights_punctual"]["lights"];
+    for(size_t l = 0; l < m_lights.size(); ++l)
+      if(lightsDirty.count(m_lightIndex[l]))
+        lightProperties(lights[size_t(m_lightIndex[l])], m_lights[l]);
+    m_lastChanges |= MI_SCENE_CHANGED_LIGHTS;
+  }
+  if(!camerasDirty.empty())
+  {
+    for(size_t c = 0; c < m_cameras.size(); ++c)
+      if(camerasDirty.count(m_cameraIndex[c]))
+        cameraIntrinsics(m_doc["cameras"][size_t(m_cameraIndex[c])], m_cameras[c]);
+    m_lastChanges |= MI_SCENE_CHANGED_CAMERAS;
+  }
+  if(visibilityDirty)
+  {
+    // the cascade of the load-time traversal: a render node is visible when no node on its path says otherwise
+    const Value& nodes = m_doc["nodes"];
+    for(size_t n = 0; n < m_renderNodes.size(); ++n)
+    {
+      bool visible = true;
+      for(int id : m_renderNodeSource[n].path)
+      {
+        const Value& vis = nodes[size_t(id)]["extensions"]["KHR_node_visibility"]["visible"];
+        visible          = visible && !(vis.type == Value::Bool && !vis.b);
+      }
+      m_renderNodeVisible[n] = visible ? 1 : 0;
+    }
+    m_lastChanges |= MI_SCENE_CHANGED_VISIBILITY;
+  }
   if(!any)
   {
     if(anyWeights)
+    {
       updateDeformTables();
-    return anyWeights;
+      m_lastChanges |= MI_SCENE_CHANGED_DEFORMATION;
+    }
+    return (anyWeights || anyPointer) ? 1 : 0;
   }
+  m_lastChanges |= MI_SCENE_CHANGED_NODES | (m_lights.empty() ? 0 : MI_SCENE_CHANGED_LIGHTS) | (m_deform.empty() ? 0 : MI_SCENE_CHANGED_DEFORMATION);
 
   // World matrices (reference: Scene::updateNodeWorldMatrices), per PATH from a scene root: glTF hierarchies are strict trees, but
   // load-time traversal instantiates a node of a non-conforming file under every parent it is listed by -- each such render node
@@ -301,7 +663,7 @@ bool GltfScene::updateAnimation(int index)
   for(size_t l = 0; l < m_lights.size(); ++l)
     placeLight(m_lights[l], worldOf(m_lightPath[l]));
   updateDeformTables();
-  return true;
+  return 1;
 }
 
 //----------------------------------------------------------------------------------------------------------------------

@@ -125,13 +125,23 @@ int mi_scene_update_animation(MiScene* scene, int index, float time)
   try
   {
     scene->scene.animationInfo(index).currentTime = time;
-    return scene->scene.updateAnimation(index) ? 1 : 0;
+    const int r = scene->scene.updateAnimation(index);
+    if(r < 0)
+    {
+      g_hostError = scene->scene.error();
+      return MI_PT_ERR_ARGUMENT;
+    }
+    return r;
   }
   catch(const std::exception& e)
   {
     g_hostError = e.what();
     return MI_PT_ERR_IO;
   }
+}
+int mi_scene_animation_changes(const MiScene* scene)
+{
+  return scene ? scene->scene.lastAnimationChanges() : 0;
 }
 const MiPtDeformDesc* mi_scene_deformation(const MiScene* scene)
 {

@@ -79,12 +79,18 @@ class Scene:
         return name.value.decode(), a.value, b.value
 
     def update_animation(self, index, time):
-        """Poses the scene at `time`: the render-node matrices and light placements of `desc` change in place.  True when something
-        moved; follow with PathTracer.update_from_scene(scene)."""
+        """Poses the scene at `time`: the render-node matrices and light placements of `desc` change in place -- and, for
+        KHR_animation_pointer channels, its material, texture-info and light tables, visibility flags and cameras.  True when something
+        moved; follow with PathTracer.update_from_scene(scene).  animation_changes says what changed."""
         r = self._h.mi_scene_update_animation(self._p, index, float(time))
         if r < 0:
             _check_host(r)
         return bool(r)
+
+    @property
+    def animation_changes(self):
+        """capi.MI_SCENE_CHANGED_* bits of the last update_animation (mi_scene_animation_changes)."""
+        return int(self._h.mi_scene_animation_changes(self._p))
 
     @property
     def deformation(self):
@@ -188,6 +194,11 @@ class PathTracer:
         """New placement / colour / cone of the lights (same count as at creation)."""
         _check_pt(self._l.mi_pt_update_lights(self._p, lights, count))
 
+    def update_materials(self, materials, num_materials, texture_infos, num_texture_infos):
+        """New material and texture-info tables (mi_pt_update_materials): the same number of materials as at creation; everything a build
+        derives from them is updated in place, with a rebuild only where include/mi_pt.h lists one.  Restart the accumulation afterwards."""
+        _check_pt(self._l.mi_pt_update_materials(self._p, materials, int(num_materials), texture_infos, int(num_texture_infos)))
+
     def set_deformation(self, scene):
         """Static upload of the scene's skin / morph tables (mi_pt_set_deformation); None, or a scene without deformers, releases them."""
         d = scene.deformation if scene is not None else None
@@ -232,11 +243,14 @@ class PathTracer:
 
     def update_from_scene(self, scene):
         """After Scene.update_animation: hands the scene's render-node and light tables to the device again -- and, after set_deformation,
-        deforms the skinned / morphed geometry first (with the rebuild left to update_render_nodes: one per frame)."""
+        deforms the skinned / morphed geometry first (with the rebuild left to update_render_nodes: one per frame); the material tables
+        only when a KHR_animation_pointer channel changed them.  A changed camera is the caller's: scene.camera() -> set_frame_info."""
         d = scene.desc.contents
         deform = scene.deformation if getattr(self, "_deforming", False) else None
         if deform is not None:
             self.update_deformation(deform.jointMatrices, deform.morphWeights, defer_build=True)
+        if scene.animation_changes & capi.MI_SCENE_CHANGED_MATERIALS:  # (KHR_animation_pointer; before the nodes: a rebuild then sees the new flags)
+            self.update_materials(d.materials, d.numMaterials, d.textureInfos, d.numTextureInfos)
         self.update_render_nodes(d.renderNodes, d.numRenderNodes, d.renderNodeVisible)
         self.update_lights(d.lights, d.numLights)
 

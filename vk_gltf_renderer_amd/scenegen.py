@@ -210,6 +210,22 @@ class GlbBuilder:
         self.doc.setdefault("animations", []).append(anim)
         return len(self.doc["animations"]) - 1
 
+    def animation_pointer(self, channels, name=None):
+        """KHR_animation_pointer channels: [(json pointer, times, values, interpolation)]; values (keys, components), or (keys, 3, components)
+        for CUBICSPLINE; one component is stored as SCALAR."""
+        self.ext_used.add("KHR_animation_pointer")
+        anim = {"samplers": [], "channels": []}
+        if name:
+            anim["name"] = name
+        for pointer, times, values, interp in channels:
+            values = np.asarray(values, np.float32)
+            out = values.reshape(-1, values.shape[-1])
+            anim["samplers"].append({"input": self.accessor(np.asarray(times, np.float32), minmax=True), "output": self.accessor(out[:, 0] if out.shape[1] == 1 else out),
+                                     "interpolation": interp})
+            anim["channels"].append({"sampler": len(anim["samplers"]) - 1, "target": {"path": "pointer", "extensions": {"KHR_animation_pointer": {"pointer": pointer}}}})
+        self.doc.setdefault("animations", []).append(anim)
+        return len(self.doc["animations"]) - 1
+
     def save(self, path):
         doc = dict(self.doc)
         if self.ext_used:
@@ -1086,6 +1102,83 @@ def scene_animated(path, seed=5, tess=12):
     b.animation([(still, "translation", [1.0, 3.0], [[-2.0, -0.6, -1.0], [-2.0, 0.8, -1.0]], "LINEAR")], name="lift")
     b.ext_used.add("EXT_mesh_gpu_instancing")
     return b.save(path)
+
+
+def scene_material_animated(path, seed=23, tess=12, tex_size=32):
+    """A small stage for material updates and KHR_animation_pointer: a textured OPAQUE floor whose UV offset (LINEAR) and rotation (CUBICSPLINE)
+    are animated, two spheres SHARING one material with an animated emissive strength and roughness, a third sphere whose node visibility is
+    animated (STEP), an alpha-MASK card with an animated cutoff (STEP) next to a MASK card nothing animates, an alpha-BLEND card with an animated
+    base-colour alpha, a point light (intensity) and a spot light (outer cone), a camera (yfov); a second clip over another time range.
+    558 triangles: more than two blocks of triangle slots, not a multiple of 64.  Returns the path; scene_material_animated.LAYOUT names
+    the indices the channels point at."""
+    rng = np.random.default_rng(seed)
+    b = GlbBuilder()
+    L = scene_material_animated.LAYOUT
+    checker = ((np.add.outer(np.arange(tex_size) // 4, np.arange(tex_size) // 4) % 2)[..., None] * np.array([0.7, 0.5, 0.2]) + 0.25)
+    floor_tex = b.texture(b.image((np.concatenate([np.clip(checker, 0, 1), np.ones((tex_size, tex_size, 1))], -1) * 255 + 0.5).astype(np.uint8)), b.sampler())
+    a = value_noise(rng, tex_size, 3, 1)[..., 0]
+    card = np.concatenate([np.clip(value_noise(rng, tex_size, 3, 3), 0, 1), np.clip(a * 1.3, 0, 1)[..., None]], -1)
+    card_tex = b.texture(b.image((card * 255 + 0.5).astype(np.uint8)), b.sampler())
+    mats = [None] * 6
+    mats[L["mat_floor"]] = {"pbrMetallicRoughness": {"baseColorTexture": {"index": floor_tex, "extensions": {"KHR_texture_transform": {"offset": [0.0, 0.0], "rotation": 0.0}}},
+                                                   "metallicFactor": 0.0, "roughnessFactor": 0.9}}
+    mats[L["mat_shared"]] = {"pbrMetallicRoughness": {"baseColorFactor": [0.8, 0.3, 0.2, 1.0], "metallicFactor": 0.2, "roughnessFactor": 0.4}, "emissiveFactor": [0.2, 0.5, 0.9],
+                             "extensions": {"KHR_materials_emissive_strength": {"emissiveStrength": 1.0}}}
+    mats[L["mat_plain"]] = lambert_material((0.3, 0.7, 0.4))
+    mats[L["mat_mask"]] = {"pbrMetallicRoughness": {"baseColorTexture": {"index": card_tex}, "metallicFactor": 0.0, "roughnessFactor": 0.8}, "alphaMode": "MASK",
+                           "alphaCutoff": 0.5, "doubleSided": True}
+    mats[L["mat_mask_still"]] = {"pbrMetallicRoughness": {"baseColorTexture": {"index": card_tex}, "metallicFactor": 0.0, "roughnessFactor": 0.8}, "alphaMode": "MASK",
+                                 "alphaCutoff": 0.45, "doubleSided": True}
+    mats[L["mat_blend"]] = {"pbrMetallicRoughness": {"baseColorFactor": [0.9, 0.8, 0.2, 0.6], "metallicFactor": 0.0, "roughnessFactor": 0.7}, "alphaMode": "BLEND",
+                            "doubleSided": True}
+    for m in mats:
+        b.material(m)
+    fp, fn, fuv, fi = grid(6, 6, (10, 10), "y")
+    nodes = [None] * 7
+    b.node(mesh=b.mesh([b.primitive(fp, fi, fn, fuv * 3.0, material=L["mat_floor"])]))
+    sp = uv_sphere(tess, tess // 2, 0.45)
+    ball = b.mesh([b.primitive(sp[0], sp[3], sp[1], sp[2], material=L["mat_shared"])])
+    b.node(mesh=ball, translation=[-1.6, 0.46, 0.3])
+    b.node(mesh=ball, translation=[1.6, 0.46, -0.2], scale=[1.0, 1.3, 1.0])
+    blinker = b.node(mesh=b.mesh([b.primitive(sp[0], sp[3], sp[1], sp[2], material=L["mat_plain"])]), translation=[0.0, 0.46, -0.9],
+                     extensions={"KHR_node_visibility": {"visible": True}})
+    assert blinker == L["node_blinker"]
+    cp, cn, cuv, ci = grid(3, 3, (1.4, 1.0), "z")
+    for k, m in enumerate(("mat_mask", "mat_mask_still", "mat_blend")):
+        b.node(mesh=b.mesh([b.primitive(cp, ci, cn, cuv, material=L[m])]), translation=[-1.7 + 1.7 * k, 1.3, 1.0], rotation=_quat((1, 0, 0), -0.5))
+    b.light({"type": "point", "intensity": 40.0, "color": [1, 1, 1], "extras": {"radius": 0.15}})
+    b.node(extensions={"KHR_lights_punctual": {"light": 0}}, translation=[0.0, 3.5, 2.5])
+    b.light({"type": "spot", "intensity": 300.0, "color": [1.0, 0.8, 0.6], "spot": {"innerConeAngle": 0.2, "outerConeAngle": 0.5}})
+    b.node(extensions={"KHR_lights_punctual": {"light": 1}}, translation=[-2.5, 3.0, 0.5], rotation=_quat((1, 0.2, 0.6), -1.2))
+    b.camera_node((0.0, 2.4, 5.2), (0, 0.5, 0), yfov=0.7)
+    mat = lambda i, rest: "/materials/%d/%s" % (L[i], rest)
+    light = lambda i, rest: "/extensions/KHR_lights_punctual/lights/%d/%s" % (i, rest)
+    cub = np.zeros((3, 3, 1), np.float32)  # (in-tangent, value, out-tangent) per key
+    cub[:, 1, 0] = [0.0, 0.8, -0.4]
+    cub[:, 0, 0] = [0.0, 0.5, -0.3]
+    cub[:, 2, 0] = [0.7, -0.2, 0.0]
+    b.animation_pointer([
+        (mat("mat_floor", "pbrMetallicRoughness/baseColorTexture/extensions/KHR_texture_transform/offset"), [0.0, 1.0, 2.0], [[0, 0], [0.35, -0.2], [0.1, 0.6]], "LINEAR"),
+        (mat("mat_floor", "pbrMetallicRoughness/baseColorTexture/extensions/KHR_texture_transform/rotation"), [0.5, 1.25, 2.0], cub, "CUBICSPLINE"),
+        (mat("mat_shared", "extensions/KHR_materials_emissive_strength/emissiveStrength"), [0.0, 0.75, 2.0], [[1.0], [6.0], [0.5]], "LINEAR"),
+        (mat("mat_shared", "pbrMetallicRoughness/roughnessFactor"), [0.25, 1.75], [[0.4], [0.05]], "LINEAR"),
+        (mat("mat_mask", "alphaCutoff"), [0.0, 0.8, 1.6, 2.0], [[0.5], [0.3], [0.7], [0.5]], "STEP"),
+        (mat("mat_blend", "pbrMetallicRoughness/baseColorFactor"), [0.0, 2.0], [[0.9, 0.8, 0.2, 0.6], [0.2, 0.8, 0.9, 0.15]], "LINEAR"),
+        (light(0, "intensity"), [0.0, 1.0, 2.0], [[40.0], [12.0], [60.0]], "LINEAR"),
+        (light(1, "spot/outerConeAngle"), [0.0, 2.0], [[0.5], [0.9]], "LINEAR"),
+        ("/cameras/0/perspective/yfov", [0.5, 1.5], [[0.7], [0.95]], "LINEAR"),
+        ("/nodes/%d/extensions/KHR_node_visibility/visible" % blinker, [0.0, 0.6, 1.2, 2.0], [[1.0], [0.0], [1.0], [1.0]], "STEP"),
+    ], name="stage")
+    b.animation_pointer([
+        (mat("mat_shared", "emissiveFactor"), [3.0, 5.0], [[0.2, 0.5, 0.9], [0.9, 0.1, 0.1]], "LINEAR"),
+        (light(1, "color"), [3.5, 4.5], [[1.0, 0.8, 0.6], [0.3, 0.4, 1.0]], "LINEAR"),
+    ], name="encore")
+    b.ext_used.update(("KHR_texture_transform", "KHR_node_visibility"))
+    return b.save(path)
+
+
+scene_material_animated.LAYOUT = {"mat_floor": 0, "mat_shared": 1, "mat_plain": 2, "mat_mask": 3, "mat_mask_still": 4, "mat_blend": 5, "node_blinker": 3,
+                                  "node_mask": 4, "node_mask_still": 5, "node_blend": 6}
 
 
 def _rot_matrix(q):
