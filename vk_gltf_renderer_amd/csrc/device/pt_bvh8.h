@@ -15,6 +15,9 @@ struct NodeGroup
   uint32_t bits;  // hits (8 bits, priority space: bit p = slot ^ octinv) << 8 | imask
 };
 
+// s_waitcnt operand "vmcnt(0)" and nothing else (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 at their maxima = not waited for)
+constexpr int WAIT_VMCNT0 = 0x0f70;
+
 struct LaneStack2
 {
   int*     lds;  // 2 * BVH8_STACK_LDS * stride ints
@@ -48,6 +51,12 @@ struct LaneStack2
     {
       g.base = privBase[sp - BVH8_STACK_LDS];
       g.bits = privBits[sp - BVH8_STACK_LDS];
+      // The overflow words come from scratch, a vector-memory load into the registers the LDS path reads into.  Left to
+      // itself the compiler waits for them where the branches meet -- and in front of the LDS read, which reuses the
+      // registers -- with vmcnt(0), on EVERY pop, whether or not a lane is this deep: that drained the triangle records
+      // a round keeps in flight across the node step (TriRound, pt_kernels.hip).  Waiting here keeps the wait in the
+      // branch that needs it; the LDS path and the join then carry no vector-memory wait at all.
+      __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);
     }
     else
       g.base = g.bits = 0;

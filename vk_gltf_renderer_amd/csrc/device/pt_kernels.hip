@@ -559,6 +559,15 @@ PT_DEV uint32_t laneRead(uint32_t v, uint32_t lane) { return uint32_t(__builtin_
 // pure function of (seed, renderNode, primitive), so the outcome does not depend on who tests what or in which order.
 // The round is split in two so that the triangle records are in flight while the wave does its next node step:
 // triRoundPublish (owners publish, every lane issues the loads of its triangle) ... node step ... triRoundFinish.
+// That is a property of the COMPILED code, and until the closest-hit walk was restructured it did not have it (LABNOTES.md,
+// "The triangle fetch overlaps the node step"): the intersection test works on the record's (y, z) pairs as packed
+// operands, which need even-aligned register pairs the three loads (dwordx3, dwordx3, dwordx4) do not deliver; as long as
+// the record was a value merged across branches -- behind `if(tr.has)`, then across `if(round)` around the node step --
+// the copies into those pairs sat at the end of the loading block, each behind a wait for its load.  Now the walk loads
+// in every lane (triRoundPublish<true>) and has publish, node step and finish in one block, so the copies are made where
+// the record is used; the first wait that can stall on the record is the node record's own first wait.
+// tests/test_walk_overlap_isa.py reads the assembly for it.  (The shadow walk finishes a round right behind its publish
+// -- a committing hit ends the ray -- and keeps the guarded load.)
 struct TriRound
 {
   uint32_t off, n;   // owner: first published item and how many
@@ -566,6 +575,7 @@ struct TriRound
   bool     has;
   DevTri   T;
 };
+template <bool ALL_LANES_LOAD = false>
 PT_DEV void triRoundPublish(const DevScene& sc, bool active, uint32_t& pBase, uint32_t& pMask, uint32_t& qBase, uint32_t& qMask, uint32_t* waveItems, TriRound& tr)
 {
   const uint32_t lane = laneId();
@@ -590,7 +600,9 @@ PT_DEV void triRoundPublish(const DevScene& sc, bool active, uint32_t& pBase, ui
   tr.has  = lane < total;
   tr.item = tr.has ? waveItems[lane] : 0u;
   __builtin_amdgcn_wave_barrier();
-  if(tr.has)
+  // ALL_LANES_LOAD (closest-hit walk): a lane without an item loads triangle 0 -- one address for all of them, and the memory
+  // instruction costs the same with 5 or 64 lanes -- so that the record is not a value merged behind a branch (TriRound, above)
+  if(ALL_LANES_LOAD || tr.has)
     tr.T = sc.tris[tr.item & 0x3ffffffu];
 }
 // Candidates on alpha-tested materials are not resolved where they are found: the test is a chain of two dependent fetches
@@ -970,64 +982,71 @@ __global__ void __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) k_trace_closest(
     {
       if(WIDE)
       {
-        // Triangle round, first half: once enough lanes have parked triangles (or a lane has no room left, or few lanes are
-        // still walking) they are published and every lane starts loading one; the loads fly during the node step below.
-        const unsigned long long tTri0 = PROF_T();
-        TriRound           tr;
-        bool               round = false;
-        unsigned long long pend  = __ballot(active && leafPending(pMask));
-        if(pend != 0ull)
-        {
-          const bool drain = lastVisiting < TRI_PHASE_LANES;  // few lanes left walking: nothing to wait for
-          // (round 6, review item 4a: a round started on the number of TRIANGLES the wave would hand in -- 32 / 48 / 60 instead of 20 lanes holding some --
-          //  measured atrium closest-hit walk 1.365 -> 1.464 / 1.387 / 1.385 ms per frame, street 5.44 -> 5.82 / 5.51 / 5.50: profiles/r06_shade_walk_ab.txt)
-          round            = drain || __popcll(pend) >= TRI_ROUND_LANES;
-          if(round)
-          {
-            PROF_CNT(2, 1);
-            PROF_CNT(3, __popcll(pend));
-            triRoundPublish(sc, active, pBase, pMask, qBase, qMask, reinterpret_cast<uint32_t*>(s_slots + (threadIdx.x & ~63u)), tr);
-          }
-        }
-        PROF_ADD(2, tTri0);
-        const unsigned long long tNode = PROF_T();
         // Node step: lanes with room for one more leaf record visit their next node.  Triangles are NOT tested here: a
         // memory instruction costs the CU's address unit the same 64 lane-slots whether 3 or 64 lanes are active, and
         // straight after a node visit only a few lanes have triangles.  The hits are parked (two records per lane) and
         // tested in a dense phase once enough lanes have some; the closest hit does not depend on the test order.
-        bool visited = false;
-        if(active && !leafPending(qMask))
-        {
-          if((G.bits >> 8) == 0u && st2.sp > 0)
-            G = st2.pop();
-          if(G.bits >> 8)
+        // (A lambda with two call sites, both inlined: see the round below.)
+        const auto nodeStep = [&]() -> bool {
+          const unsigned long long tNode = PROF_T();
+          bool visited = false;
+          if(active && !leafPending(qMask))
           {
-            const uint32_t child = groupPopChild(G, octinv);
+            if((G.bits >> 8) == 0u && st2.sp > 0)
+              G = st2.pop();
             if(G.bits >> 8)
-              st2.push(G);
-            uint32_t tBase, tMask;
-            bvh8Visit(sc, r, best.t, octinv, child, G, tBase, tMask, s_nodes, cachedNodes);
-            if(COUNT) ++nodes;
-            visited = true;
-            if(leafPending(tMask))
             {
-              if(!leafPending(pMask)) { pBase = tBase; pMask = tMask; }
-              else                    { qBase = tBase; qMask = tMask; }
+              const uint32_t child = groupPopChild(G, octinv);
+              if(G.bits >> 8)
+                st2.push(G);
+              uint32_t tBase, tMask;
+              bvh8Visit(sc, r, best.t, octinv, child, G, tBase, tMask, s_nodes, cachedNodes);
+              if(COUNT) ++nodes;
+              visited = true;
+              if(leafPending(tMask))
+              {
+                if(!leafPending(pMask)) { pBase = tBase; pMask = tMask; }
+                else                    { qBase = tBase; qMask = tMask; }
+              }
             }
           }
-        }
-        PROF_ADD(1, tNode);
-        PROF_CNT(0, 1);
-        PROF_CNT(1, __popcll(__ballot(visited)));
-        PROF_CNT(7, __popcll(__ballot(active && leafPending(qMask))));
-        lastVisiting = __popcll(__ballot(visited));
-        const unsigned long long tTri = PROF_T();
-        if(round)
+          PROF_ADD(1, tNode);
+          return visited;
+        };
+        // Triangle round: once enough lanes have parked triangles (or a lane has no room left, or few lanes are still
+        // walking) they are published and every lane starts loading one; the loads fly during the node step, and the
+        // tests follow it.  The step is written INSIDE the round's branch, so that the triangle record is defined and
+        // used within one block: as a value merged across `if(round)` blocks before and behind a shared node step it
+        // was waited for where it was loaded (TriRound, above).
+        bool               visited = false;
+        unsigned long long pend    = __ballot(active && leafPending(pMask));
+        const bool         drain   = lastVisiting < TRI_PHASE_LANES;  // few lanes left walking: nothing to wait for
+        // (round 6, review item 4a: a round started on the number of TRIANGLES the wave would hand in -- 32 / 48 / 60 instead of 20 lanes holding some --
+        //  measured atrium closest-hit walk 1.365 -> 1.464 / 1.387 / 1.385 ms per frame, street 5.44 -> 5.82 / 5.51 / 5.50: profiles/r06_shade_walk_ab.txt)
+        if(pend != 0ull && (drain || __popcll(pend) >= TRI_ROUND_LANES))
+        {
+          const unsigned long long tTri0 = PROF_T();
+          TriRound           tr;
+          PROF_CNT(2, 1);
+          PROF_CNT(3, __popcll(pend));
+          triRoundPublish<true>(sc, active, pBase, pMask, qBase, qMask, reinterpret_cast<uint32_t*>(s_slots + (threadIdx.x & ~63u)), tr);
+          PROF_ADD(2, tTri0);
+          visited = nodeStep();
+          const unsigned long long tFinish = PROF_T();
 #ifdef TRACE_PROFILE
           triRoundFinish<HAS_ALPHA, COUNT>(sc, r, best, seed0, tr, tris, s_slots + (threadIdx.x & ~63u), waveAlpha, aCount, aPending, profAcc);
 #else
           triRoundFinish<HAS_ALPHA, COUNT>(sc, r, best, seed0, tr, tris, s_slots + (threadIdx.x & ~63u), waveAlpha, aCount, aPending);
 #endif
+          PROF_ADD(2, tFinish);
+        }
+        else
+          visited = nodeStep();
+        PROF_CNT(0, 1);
+        PROF_CNT(1, __popcll(__ballot(visited)));
+        PROF_CNT(7, __popcll(__ballot(active && leafPending(qMask))));
+        lastVisiting = __popcll(__ballot(visited));
+        const unsigned long long tTri = PROF_T();
         if(HAS_ALPHA && aCount != 0u)
         {
           // alpha round: the list is long enough, or the walk is running dry, or rays have nothing left to do but wait for it
