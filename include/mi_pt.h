@@ -371,6 +371,50 @@ MI_PT_API int mi_pt_denoise(MiPt* pt, int iterations, float sigmaColor, float si
  * demodulated before and re-applied after filtering.  The temporal half of SVGF is the running mean itself (the camera of a
  * progressive accumulation stands still), so there is no reprojection.  Asynchronous on hipStream unless hostRGBA32F is given. */
 MI_PT_API int mi_pt_denoise_svgf(MiPt* pt, int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, float* hostRGBA32F, void* hipStream);
+
+/* Motion vectors and temporal reprojection: the temporal half of SVGF (Schied et al. 2017, section 4.1) for scenes and cameras that move, fed by the
+ * reference's first-hit G-buffer -- previous-frame position of the first hit under prevRenderNodeObjectToWorld (shaders/gltf_pathtrace.slang:228-241),
+ * pixel-space motion vector with the background as points at infinity (:637-645, shaders/dlss_util.h:63-96), matrices snapshot once per rendered pose
+ * (shaders/snapshot_prev_transforms.comp.slang).  It stands where the reference runs DLSS-RR; DLSS itself stays out of scope.
+ * Call order per pose: update calls, mi_pt_set_frame_info (prevMVP = the viewProjMatrix of the pose before), a batch with MI_PT_FIRST_FRAME |
+ * MI_PT_USE_OPTIX_DENOISER (more frames of the same pose may follow), mi_pt_denoise_temporal ONCE.  INTEGRATION.md, "Temporal reprojection". */
+
+/* The record of the last MI_PT_FIRST_FRAME batch's first hit, four floats per pixel: xyz = world position (the ray direction where the id is 0), w = the
+ * BITS of an id: renderNode + 1 on a mesh, 0 for a miss and for the infinite plane, 0xffffffff on the shadow-catcher path (no position).  Pixels another
+ * rank owns read 0.  MI_PT_ERR_STATE before the first such batch (and after a resize or a larger mi_pt_render_frames batch, until the next one). */
+MI_PT_API int mi_pt_read_first_hit(MiPt* pt, float* hostXYZW);
+/* enable != 0: allocates the motion image (16 B per pixel), the history (96 B per pixel: two sets of three 16-byte records) and the previous objectToWorld
+ * of every render node (64 B each, initialised to the current ones); from then on every MI_PT_FIRST_FRAME batch is followed, on its stream, by the motion
+ * kernel and the snapshot of the matrices.  0 frees all of it.  Accumulator, guides, depth and selection do not depend on the setting. */
+MI_PT_API int mi_pt_set_temporal(MiPt* pt, int enable);
+/* The motion image of the last MI_PT_FIRST_FRAME batch, four floats per pixel: xy = (prevNDC - currNDC) * 0.5 * resolution in pixels (add to a pixel
+ * centre to find where its point was; mesh hits move with their render node only, skinned or morphed vertices relative to it do not count),
+ * z = the NDC depth the point had under prevMVP (1 where the id is 0), w = the id bits as above (0xffffffff: zero motion).
+ * MI_PT_ERR_STATE while the feature is off or before the first such batch. */
+MI_PT_API int mi_pt_read_motion(MiPt* pt, float* hostRGBA32F);
+typedef struct MiPtTemporalParams
+{
+  int   iterations;     /* a-trous iterations after the temporal stage, 0..8; 0 = the re-modulated temporal stage alone */
+  float sigmaLuminance; /* as mi_pt_denoise_svgf */
+  float sigmaNormal;
+  float sigmaDepth;
+  float alpha;          /* weight of the new pose in the illumination: max(alpha, 1 / history length); 0.2 */
+  float momentsAlpha;   /* ... in the two luminance moments; 0.2 */
+  float maxHistory;     /* the history length saturates here; 32 */
+  float normalCos;      /* a history tap is valid when dot(normal then, normal now) >= normalCos ... */
+  float depthTolerance; /* ... and its depth agrees with the reprojected one within this, relative */
+} MiPtTemporalParams;
+MI_PT_API void mi_pt_default_temporal(MiPtTemporalParams* params);
+/* mi_pt_denoise_svgf with the temporal stage in front: the history is reprojected along the motion image (four bilinear taps, each valid when it lies
+ * inside the image, carries this pixel's id, an agreeing normal and the depth the point had), blended with this pose's demodulated accumulator
+ * (history length h = min(h + 1, maxHistory), weight max(alpha, 1 / h); no valid tap: h = 1), the variance comes from the blended luminance moments
+ * from h = 4 on (the 7x7 spatial estimate below), then the a-trous iterations and the re-modulation run as in mi_pt_denoise_svgf.  Same I/O contract:
+ * result in hostRGBA32F (may be NULL) and in the denoised image (mi_pt_tonemap source 1); alpha passes through.  Call it once per pose: every call
+ * advances the history.  MI_PT_ERR_STATE: the feature is off, no first-frame batch since, or a tile partition with world > 1. */
+MI_PT_API int mi_pt_denoise_temporal(MiPt* pt, const MiPtTemporalParams* params, float* hostRGBA32F, void* hipStream);
+/* Forgets the history: the next mi_pt_denoise_temporal starts from its pose alone.  (mi_pt_resize, mi_pt_set_tile_partition and mi_pt_set_temporal do too.) */
+MI_PT_API int mi_pt_reset_history(MiPt* pt);
+
 /* device address of the last denoise result (NULL before the first), valid until the next denoise / resize */
 MI_PT_API const void* mi_pt_denoised_device_ptr(MiPt* pt);
 
@@ -412,8 +456,10 @@ MI_PT_API const char* mi_pt_version(void);
  * header must refuse to run -- `if(mi_pt_abi_version() != MI_PT_ABI_VERSION) fail` right after loading the library.
  * 6: MiPtMemory grew pathStateBytes / pathSlots (round 5); mi_pt_render_frames refuses maxDepth 0; mi_pt_set_frame_queue.
  * 7: MiPtDeformPrimitive / MiPtDeformDesc and the deformation entry points (skins and morph targets on the device).
- * 8: MiPtAccelInfo and the refit entry points (mi_pt_set_accel_update, mi_pt_get_accel_info). */
-#define MI_PT_ABI_VERSION 8
+ * 8: MiPtAccelInfo and the refit entry points (mi_pt_set_accel_update, mi_pt_get_accel_info).
+ * 9: MiPtTemporalParams and the motion / temporal entry points (mi_pt_read_first_hit, mi_pt_set_temporal, mi_pt_read_motion, mi_pt_denoise_temporal,
+ *    mi_pt_reset_history). */
+#define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 
 #ifdef __cplusplus

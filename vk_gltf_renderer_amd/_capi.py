@@ -149,6 +149,11 @@ class MiPtAccelInfo(C.Structure):
                 ("sahCostAtBuild", C.c_double), ("sahCost", C.c_double), ("trianglesMoved", C.c_uint64), ("refitBytes", C.c_uint64)]
 
 
+class MiPtTemporalParams(C.Structure):
+    _fields_ = [("iterations", i32), ("sigmaLuminance", f32), ("sigmaNormal", f32), ("sigmaDepth", f32), ("alpha", f32), ("momentsAlpha", f32),
+                ("maxHistory", f32), ("normalCos", f32), ("depthTolerance", f32)]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -161,7 +166,7 @@ assert C.sizeof(MiGltfShadeMaterial) == 288
 assert C.sizeof(MiSceneFrameInfo) == 396
 assert C.sizeof(MiPtAccelInfo) == 64
 
-MI_PT_ABI_VERSION = 8  # include/mi_pt.h
+MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
 # mi_scene_animation_changes (include/mi_host.h)
 (MI_SCENE_CHANGED_NODES, MI_SCENE_CHANGED_LIGHTS, MI_SCENE_CHANGED_DEFORMATION, MI_SCENE_CHANGED_MATERIALS, MI_SCENE_CHANGED_CAMERAS,
@@ -282,6 +287,12 @@ PT_SYMBOLS = {
     "mi_pt_read_vertices": (i32, [VP, i32, P(f32), P(f32), P(f32)]),
     "mi_pt_set_accel_update": (i32, [VP, i32, f32]),
     "mi_pt_get_accel_info": (i32, [VP, P(MiPtAccelInfo)]),
+    "mi_pt_read_first_hit": (i32, [VP, P(f32)]),
+    "mi_pt_set_temporal": (i32, [VP, i32]),
+    "mi_pt_read_motion": (i32, [VP, P(f32)]),
+    "mi_pt_default_temporal": (None, [P(MiPtTemporalParams)]),
+    "mi_pt_denoise_temporal": (i32, [VP, P(MiPtTemporalParams), P(f32), VP]),
+    "mi_pt_reset_history": (i32, [VP]),
 }
 
 

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 PathTracer::PathTracer()
 {
@@ -51,6 +52,8 @@ void PathTracer::registerParameters(ParameterRegistry* r)
   r->add("ptCounters", "Collect traversal counters (MiPtStats; slower) and print them at the end of a headless run", &m_collectCounters);
   // (our own) how animated frames update the acceleration structure: mi_pt_set_accel_update, applied right after mi_pt_create
   r->add("accelUpdate", "Acceleration structure on animated frames [rebuild:0, refit:1, auto:2]", &m_accelUpdate);
+  // (our own) motion vectors and temporal reprojection for scenes and cameras that move: mi_pt_set_temporal right after mi_pt_create
+  r->add("temporal", "Denoiser: temporal reprojection across poses (animated clips, camera moves); implies the denoiser", &m_temporal);
   r->add("accelRebuildRatio", "auto: rebuild once the refitted tree's SAH cost exceeds this x the cost after the last build", &m_accelRebuildRatio);
 }
 
@@ -87,6 +90,16 @@ void PathTracer::onSceneInvalidated(Resources& res)
     m_pt = nullptr;
     return;
   }
+  m_poseOpen = m_havePoseViewProj = false;
+  if(m_temporal)
+  {
+    m_denoiser.enable = true;  // the temporal pass reads the guides
+    if(mi_pt_set_temporal(m_pt, 1) != MI_PT_OK)
+    {
+      m_error = mi_pt_last_error();
+      fprintf(stderr, "PathTracer: mi_pt_set_temporal failed: %s\n", m_error.c_str());
+    }
+  }
   if(res.hdrIbl)
     mi_pt_set_environment(m_pt, mi_hdr_env(res.hdrIbl));
   if(res.renderSize.width > 0)
@@ -120,6 +133,17 @@ void PathTracer::setupPushConstant(Resources& res, const Extent2D& renderingSize
   m_pushConst.flags        = (res.frameCount == 0 ? MI_PT_FIRST_FRAME : 0) | (m_denoiser.enable ? MI_PT_USE_OPTIX_DENOISER : 0);
   if(res.frameCount == 0)
     m_hasDenoisedOutput = false;
+  if(m_temporal)
+  {
+    // prevMVP: the camera of the pose before (reference: SceneFrameInfo::prevMVP, the previous app frame's matrix); a pose's later frames keep it
+    if(res.frameCount == 0)
+    {
+      memcpy(m_prevMVP, m_havePoseViewProj ? m_poseViewProj : res.frameInfo.viewProjMatrix, sizeof(m_prevMVP));
+      memcpy(m_poseViewProj, res.frameInfo.viewProjMatrix, sizeof(m_poseViewProj));
+      m_havePoseViewProj = true;
+    }
+    memcpy(res.frameInfo.prevMVP, m_prevMVP, sizeof(m_prevMVP));
+  }
   m_pushConst.totalSamples = m_totalSamplesAccumulated;
   // pixelAngle = 2 |projInv[1][1]| / viewportHeight
   m_pushConst.pixelAngle = 2.0f * std::fabs(res.frameInfo.projInv[5]) / std::max(float(renderingSize.height), 1.0f);
@@ -151,7 +175,16 @@ bool PathTracer::denoiseOneShot()
 {
   if(!m_pt)
     return false;
-  const int rc = m_denoiser.method == 0 ? mi_pt_denoise(m_pt, 5, 0.6f, 64.0f, 0.2f, nullptr, nullptr) : mi_pt_denoise_svgf(m_pt, 5, 4.0f, 128.0f, 1.0f, nullptr, nullptr);
+  int rc;
+  if(m_temporal)
+  {
+    MiPtTemporalParams tp;
+    mi_pt_default_temporal(&tp);
+    rc         = mi_pt_denoise_temporal(m_pt, &tp, nullptr, nullptr);
+    m_poseOpen = false;
+  }
+  else
+    rc = m_denoiser.method == 0 ? mi_pt_denoise(m_pt, 5, 0.6f, 64.0f, 0.2f, nullptr, nullptr) : mi_pt_denoise_svgf(m_pt, 5, 4.0f, 128.0f, 1.0f, nullptr, nullptr);
   if(rc != MI_PT_OK)
   {
     m_error = mi_pt_last_error();
@@ -169,6 +202,11 @@ bool PathTracer::denoiseOneShot()
 // the frame's stream behind the frame it denoises.
 void PathTracer::updateDenoiser(Resources& res)
 {
+  if(m_temporal)  // once per pose (onRender, saveHeadlessOutputImage), not on the cadence: every temporal pass advances the history
+  {
+    m_poseOpen = true;
+    return;
+  }
   if(!m_denoiser.enable || !m_denoiser.autoDenoiseEnabled || m_denoiser.autoDenoiseInterval <= 0)
     return;
   const int frame = res.frameCount + 1;  // frames accumulated so far
@@ -188,6 +226,8 @@ void PathTracer::onRender(StreamHandle cmd, Resources& res)
 {
   if(!m_pt)
     return;
+  if(m_temporal && res.frameCount == 0 && m_poseOpen)
+    denoiseOneShot();  // the pose that just ended: its one temporal pass, before this frame overwrites the images it reads
   updateAdaptiveSampling(res);  // reference order: src/renderer_pathtracer.cpp:552-553, before the push constants are set up
   setupPushConstant(res, res.renderSize);
   mi_pt_set_frame_info(m_pt, &res.frameInfo);

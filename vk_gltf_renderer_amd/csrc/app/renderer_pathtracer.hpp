@@ -47,6 +47,7 @@ public:
   bool denoiseOneShot();                                               // reference: OptiXDenoiser::denoiseOneShot
   int  denoiseCount() const { return m_denoiseCount; }
   bool denoisedIsCurrent() const { return m_hasDenoisedOutput && m_denoisedAtSamples == m_totalSamplesAccumulated; }
+  bool isTemporal() const { return m_temporal; }
 
   // frames the next onRender traces in one go (1 = the reference's behaviour); what it actually did (1 whenever the adaptive
   // controller or the denoiser cadence need every frame's boundary)
@@ -75,6 +76,13 @@ private:
   bool        m_collectCounters{false};    // --ptCounters (our own): MiPtCreateOptions::collectCounters
   int         m_accelUpdate{0};            // --accelUpdate (our own): MI_PT_ACCEL_REBUILD / REFIT / AUTO
   float       m_accelRebuildRatio{1.5f};   // --accelRebuildRatio: AUTO's bound (mi_pt_set_accel_update)
+  // --temporal (our own): motion vectors + temporal reprojection (mi_pt_set_temporal); the denoiser is then the temporal pass, run ONCE per
+  // pose -- when the next pose starts or the image is saved -- instead of on the auto-denoise cadence
+  bool        m_temporal{false};
+  bool        m_poseOpen{false};           // the current pose has frames the temporal pass has not seen
+  bool        m_havePoseViewProj{false};
+  float       m_poseViewProj[16]{};        // viewProjMatrix of the current pose: the next pose's prevMVP
+  float       m_prevMVP[16]{};             // what the current pose's frames carry as prevMVP
   double      m_lastFrameDeviceMs{0.0};
   int         m_totalSamplesAccumulated{0};
   int         m_framesThisCall{1}, m_framesLastCall{1};

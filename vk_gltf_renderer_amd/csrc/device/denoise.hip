@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
+#include "pt_temporal.h"
 
 namespace pt {
 
@@ -62,23 +63,7 @@ __global__ void __launch_bounds__(256) k_atrous(const float4* __restrict__ in, f
 //   3. finish: re-modulate, alpha passes through.
 // Image-space passes: 25 taps x (16 + 16 + 4 B) per pixel and iteration out of L2; the HBM side is 2 x 16 B per pixel and pass.
 //--------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float lum709(float x, float y, float z)
-{
-  return 0.2126f * x + 0.7152f * y + 0.0722f * z;
-}
-
-__device__ __forceinline__ float3 demodulator(const float4 a)
-{
-  return a.w > 0.5f ? make_float3(fmaxf(a.x, 0.02f), fmaxf(a.y, 0.02f), fmaxf(a.z, 0.02f)) : make_float3(1.0f, 1.0f, 1.0f);
-}
-
-// view-depth-like quantity from the stored NDC depth: proportional to the distance for a perspective projection with a far plane
-// much further than the scene (1 - z ~ near / distance), monotonic for any other; only ratios of its differences are used
-__device__ __forceinline__ float depthKey(float ndc)
-{
-  return 1.0f / fmaxf(1.0f - ndc, 1e-7f);
-}
-
+// (lum709, demodulator, depthKey and the 7x7 spatial variance are shared with the temporal stage: pt_temporal.h)
 __global__ void __launch_bounds__(256) k_svgf_prepare(const float4* __restrict__ color, const float4* __restrict__ albedo, const float4* __restrict__ normal,
                                                      float4* __restrict__ illum, int W, int H, float frames)
 {
@@ -87,8 +72,8 @@ __global__ void __launch_bounds__(256) k_svgf_prepare(const float4* __restrict__
     return;
   const size_t c  = size_t(y) * W + x;
   const float4 cc = color[c], ca = albedo[c];
-  const float3 dm = demodulator(ca);
-  const float3 il = make_float3(cc.x / dm.x, cc.y / dm.y, cc.z / dm.z);
+  const f3     dm = demodulator(ca);
+  const f3     il = mk3(cc.x / dm.x, cc.y / dm.y, cc.z / dm.z);
   float        var;
   if(frames >= 4.0f)
   {
@@ -97,31 +82,7 @@ __global__ void __launch_bounds__(256) k_svgf_prepare(const float4* __restrict__
     var            = fmaxf(0.0f, normal[c].w - l * l) / frames / (dl * dl);
   }
   else
-  {
-    // spatial estimate over the 7x7 neighbourhood of the same kind (geometry / background) with a similar normal
-    const float4 cn = normal[c];
-    float        s1 = 0.0f, s2 = 0.0f, sw = 0.0f;
-    for(int dy = -3; dy <= 3; ++dy)
-      for(int dx = -3; dx <= 3; ++dx)
-      {
-        const int qx = x + dx, qy = y + dy;
-        if(qx < 0 || qy < 0 || qx >= W || qy >= H)
-          continue;
-        const size_t q  = size_t(qy) * W + qx;
-        const float4 qa = albedo[q];
-        if((qa.w > 0.5f) != (ca.w > 0.5f))
-          continue;
-        const float4 qn = normal[q], qc = color[q];
-        const float  w  = ca.w > 0.5f ? (fmaxf(0.0f, qn.x * cn.x + qn.y * cn.y + qn.z * cn.z) > 0.9f ? 1.0f : 0.0f) : 1.0f;
-        const float3 qd = demodulator(qa);
-        const float  l  = lum709(qc.x / qd.x, qc.y / qd.y, qc.z / qd.z);
-        s1 += w * l;
-        s2 += w * l * l;
-        sw += w;
-      }
-    const float m = sw > 0.0f ? s1 / sw : 0.0f;
-    var           = sw > 0.0f ? fmaxf(0.0f, s2 / sw - m * m) : 0.0f;
-  }
+    var = spatialVariance7x7(color, albedo, normal, W, H, x, y, ca, normal[c]);
   illum[c] = make_float4(il.x, il.y, il.z, var);
 }
 
@@ -195,7 +156,7 @@ __global__ void __launch_bounds__(256) k_svgf_finish(const float4* __restrict__ 
   if(i >= n)
     return;
   const float4 il = illum[i];
-  const float3 dm = demodulator(albedo[i]);
+  const f3     dm = demodulator(albedo[i]);
   out[i]          = make_float4(il.x * dm.x, il.y * dm.y, il.z * dm.z, color[i].w);
 }
 
@@ -208,13 +169,13 @@ void launchAtrous(const float4* in, float4* out, const float4* albedo, const flo
   hipLaunchKernelGGL(k_atrous, grid, dim3(256), 0, s, in, out, albedo, normal, width, height, step, sigmaColor, sigmaNormal, sigmaAlbedo);
 }
 
-// SVGF pass: returns the buffer (bufA or bufB) that holds the result
-const float4* launchSvgf(const float4* color, const float4* albedo, const float4* normal, const float* depth, float4* bufA, float4* bufB, int width, int height,
-                         int iterations, float frames, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s)
+// The a-trous iterations and the re-modulation over a prepared (illumination, variance) image in `in`; `other` is the second buffer.
+// Returns the buffer that holds the result.  Shared by the spatial pass below and the temporal pass (temporal.hip prepares `in`).
+const float4* launchSvgfFilter(float4* in, float4* other, const float4* color, const float4* albedo, const float4* normal, const float* depth, int width,
+                               int height, int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s)
 {
-  dim3 grid((width + 15) / 16, (height + 15) / 16);
-  hipLaunchKernelGGL(k_svgf_prepare, grid, dim3(256), 0, s, color, albedo, normal, bufA, width, height, frames);
-  float4 *in = bufA, *out = bufB;
+  dim3    grid((width + 15) / 16, (height + 15) / 16);
+  float4* out = other;
   for(int i = 0; i < iterations; ++i)
   {
     hipLaunchKernelGGL(k_svgf_atrous, grid, dim3(256), 0, s, in, out, albedo, normal, depth, width, height, 1 << i, sigmaLuminance, sigmaNormal, sigmaDepth);
@@ -225,6 +186,15 @@ const float4* launchSvgf(const float4* color, const float4* albedo, const float4
   const size_t n = size_t(width) * size_t(height);
   hipLaunchKernelGGL(k_svgf_finish, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, in, color, albedo, out, n);
   return out;
+}
+
+// SVGF pass: returns the buffer (bufA or bufB) that holds the result
+const float4* launchSvgf(const float4* color, const float4* albedo, const float4* normal, const float* depth, float4* bufA, float4* bufB, int width, int height,
+                         int iterations, float frames, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s)
+{
+  dim3 grid((width + 15) / 16, (height + 15) / 16);
+  hipLaunchKernelGGL(k_svgf_prepare, grid, dim3(256), 0, s, color, albedo, normal, bufA, width, height, frames);
+  return launchSvgfFilter(bufA, bufB, color, albedo, normal, depth, width, height, iterations, sigmaLuminance, sigmaNormal, sigmaDepth, s);
 }
 
 }  // namespace pt

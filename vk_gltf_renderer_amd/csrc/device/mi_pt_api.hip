@@ -280,6 +280,14 @@ struct MiPt
   float                   momentFrames = 0.0f; // frames folded into the luminance second moment (normal.w): only batches rendered with the guides on
                                                // feed it, so it may lag behind accumFrames -- the SVGF pass then falls back to its spatial variance
   const float4*           denoised = nullptr;  // result of the last mi_pt_denoise (one of denoiseA / denoiseB)
+  // motion vectors and temporal reprojection (mi_pt_set_temporal; temporal.hip)
+  bool                    temporal = false;
+  bool                    haveFirstHit = false;  // pt->firstHit holds the records of a first-frame batch
+  bool                    haveMotion = false, haveHistory = false;
+  int                     historyCur = 0;        // which of the two history sets the last mi_pt_denoise_temporal wrote
+  DevBuf<float4>          motion, history;       // history: 2 sets x 3 records x pixels
+  DevBuf<float>           prevObjectToWorld;     // 16 floats per render node: the matrices of the pose rendered before
+  std::vector<uint32_t>   ownedTilesHost;        // host copy of ownedTiles (mi_pt_read_first_hit)
   DevBuf<uint32_t>        tonemapped, tmHistogram;
   DevBuf<float>           tmAutoState;
   float4*                 accum = nullptr;  // accumOwn.ptr or caller-bound memory
@@ -341,6 +349,7 @@ int allocPathResources(MiPt* pt, int frames)
   // records of the previous size are dropped and come back on demand.
   HIP_TRY(pt->pathArrays.alloc(n));
   HIP_TRY(pt->firstHit.alloc(std::max(size_t(pt->numSlots), size_t(1))));
+  pt->haveFirstHit = false;
   pt->optThroughput.release(); pt->optMisc.release(); pt->optMedium.release(); pt->optPixelSum.release(); pt->optGuides.release(); pt->optShadowAux2.release();
   pt::PathSoA& P = pt->paths;
   P              = pt::PathSoA{};
@@ -450,6 +459,28 @@ int ensureOptionalPathArrays(MiPt* pt, bool stateBySlot, bool multiSample, bool 
   return MI_PT_OK;
 }
 
+// The motion image, the history and the previous matrices of mi_pt_set_temporal, at the current size; nothing is valid afterwards.
+int allocTemporal(MiPt* pt)
+{
+  pt->haveMotion = pt->haveHistory = false;
+  pt->historyCur = 0;
+  pt->motion.release();
+  pt->history.release();
+  pt->prevObjectToWorld.release();
+  if(!pt->temporal)
+    return MI_PT_OK;
+  const size_t px = size_t(std::max(pt->width, 0)) * size_t(std::max(pt->height, 0));
+  HIP_TRY(pt->motion.alloc(px));
+  HIP_TRY(pt->history.alloc(6 * px));
+  HIP_TRY(pt->prevObjectToWorld.alloc(pt->nodes.count * 16));
+  if(px)
+    HIP_TRY(hipMemset(pt->motion.ptr, 0, px * sizeof(float4)));
+  pt::launchSnapshotTransforms(pt->nodes.ptr, pt->prevObjectToWorld.ptr, int(pt->nodes.count), nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return MI_PT_OK;
+}
+
 int allocFrameResources(MiPt* pt)
 {
   const int W = pt->width, H = pt->height, T = pt->tileSize;
@@ -461,6 +492,7 @@ int allocFrameResources(MiPt* pt)
       owned.push_back(uint32_t((t % pt->tilesX) * T) | (uint32_t((t / pt->tilesX) * T) << 16));
   pt->numSlots = int(owned.size()) * T * T;
   HIP_TRY(pt->ownedTiles.upload(owned.data(), owned.size()));
+  pt->ownedTilesHost = owned;
   if(int rc = allocPathResources(pt, pt->framesCap))
     return rc;
   const size_t px = size_t(W) * size_t(H);
@@ -483,7 +515,7 @@ int allocFrameResources(MiPt* pt)
   pt->tonemapped.release();
   pt->tmHistogram.release();
   pt->tmAutoState.release();
-  return MI_PT_OK;
+  return allocTemporal(pt);
 }
 
 hipEvent_t getEvent(MiPt* pt, size_t& cursor)
@@ -2101,7 +2133,16 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     });
   }
   if(params->flags & MI_PT_FIRST_FRAME)
+  {
     pt::launchSelection(c, pt->selection.ptr);
+    pt->haveFirstHit = true;
+    if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
+    {
+      pt::launchMotionVectors(pt->firstHit.ptr, pt->ownedTiles.ptr, uint32_t(pt->numSlots), c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr,
+                              pt->prevObjectToWorld.ptr, int(pt->nodes.count), pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->motion.ptr, stream);
+      pt->haveMotion = true;
+    }
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(pt->fcDone[fcSlot], stream));
   if(pt->timingEnabled)
@@ -2246,6 +2287,119 @@ int mi_pt_denoise_svgf(MiPt* pt, int iterations, float sigmaLuminance, float sig
   return MI_PT_OK;
 }
 
+int mi_pt_read_first_hit(MiPt* pt, float* host)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !host || pt->width <= 0)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_first_hit: bad arguments");
+  if(!pt->haveFirstHit)
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_first_hit: no MI_PT_FIRST_FRAME batch rendered at this size yet");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<float4> bySlot(size_t(std::max(pt->numSlots, 0)));
+  if(!bySlot.empty())
+    HIP_TRY(hipMemcpy(bySlot.data(), pt->firstHit.ptr, bySlot.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  memset(host, 0, size_t(pt->width) * size_t(pt->height) * sizeof(float4));
+  int tileShift = 0;
+  while((1 << tileShift) < pt->tileSize)
+    ++tileShift;
+  for(uint32_t slot = 0; slot < uint32_t(bySlot.size()); ++slot)
+  {
+    int px, py;
+    if(pt::pixelOfSlot(pt->ownedTilesHost.data(), tileShift, pt->width, pt->height, slot, px, py))
+      memcpy(host + 4 * (size_t(py) * size_t(pt->width) + size_t(px)), &bySlot[slot], sizeof(float4));
+  }
+  return MI_PT_OK;
+}
+
+int mi_pt_set_temporal(MiPt* pt, int enable)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_temporal: null instance");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  pt->temporal = enable != 0;
+  return allocTemporal(pt);
+}
+
+int mi_pt_read_motion(MiPt* pt, float* host)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !host || pt->width <= 0)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_motion: bad arguments");
+  if(!pt->temporal || !pt->haveMotion)
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_motion: needs mi_pt_set_temporal and a MI_PT_FIRST_FRAME batch after it");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host, pt->motion.ptr, size_t(pt->width) * size_t(pt->height) * sizeof(float4), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+
+void mi_pt_default_temporal(MiPtTemporalParams* p)
+{
+  if(!p)
+    return;
+  *p                = MiPtTemporalParams{};
+  p->iterations     = 5;
+  p->sigmaLuminance = 4.0f;
+  p->sigmaNormal    = 128.0f;
+  p->sigmaDepth     = 1.0f;
+  p->alpha          = 0.2f;  // Schied et al. 2017, section 4.1
+  p->momentsAlpha   = 0.2f;
+  p->maxHistory     = 32.0f;
+  p->normalCos      = 0.9f;  // (the spatial variance estimate's notion of "the same surface")
+  p->depthTolerance = 0.1f;
+}
+
+int mi_pt_denoise_temporal(MiPt* pt, const MiPtTemporalParams* tp, float* host, void* hipStream)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !tp || pt->width <= 0 || tp->iterations < 0 || tp->iterations > 8 || !(tp->sigmaLuminance > 0.0f) || !(tp->sigmaDepth > 0.0f) || !(tp->sigmaNormal >= 0.0f)
+     || !(tp->alpha > 0.0f && tp->alpha <= 1.0f) || !(tp->momentsAlpha > 0.0f && tp->momentsAlpha <= 1.0f) || !(tp->maxHistory >= 1.0f)
+     || !(tp->normalCos <= 1.0f) || !(tp->depthTolerance >= 0.0f))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_denoise_temporal: bad arguments");
+  if(!pt->temporal || !pt->haveMotion || !(pt->accumFrames >= 1.0f))
+    return fail(MI_PT_ERR_STATE, "mi_pt_denoise_temporal: needs mi_pt_set_temporal and a MI_PT_FIRST_FRAME batch after it");
+  if(pt->tileWorld > 1)
+    return fail(MI_PT_ERR_STATE, "mi_pt_denoise_temporal: not under a tile partition (the history is not reduced across ranks)");
+  HIP_TRY(hipSetDevice(pt->device));
+  hipStream_t  stream = reinterpret_cast<hipStream_t>(hipStream);
+  const size_t px     = size_t(pt->width) * size_t(pt->height);
+  if(pt->denoiseA.count != px)
+  {
+    HIP_TRY(pt->denoiseA.alloc(px));
+    HIP_TRY(pt->denoiseB.alloc(px));
+  }
+  auto set = [&](int i) {
+    float4* base = pt->history.ptr + size_t(i) * 3 * px;
+    return pt::TemporalHistory{base, base + px, base + 2 * px};
+  };
+  const pt::TemporalConsts tc{tp->alpha, tp->momentsAlpha, tp->maxHistory, tp->normalCos, tp->depthTolerance};
+  pt::launchSvgfReproject(pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->motion.ptr, set(pt->historyCur), set(pt->historyCur ^ 1), pt->denoiseA.ptr,
+                          pt->width, pt->height, tc, pt->haveHistory, stream);
+  pt->historyCur ^= 1;
+  pt->haveHistory = true;
+  pt->denoised    = pt::launchSvgfFilter(pt->denoiseA.ptr, pt->denoiseB.ptr, pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->width, pt->height,
+                                         tp->iterations, tp->sigmaLuminance, tp->sigmaNormal, tp->sigmaDepth, stream);
+  HIP_TRY(hipGetLastError());
+  if(host)
+  {
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(host, pt->denoised, px * sizeof(float4), hipMemcpyDeviceToHost));
+  }
+  return MI_PT_OK;
+}
+
+int mi_pt_reset_history(MiPt* pt)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_reset_history: null instance");
+  pt->haveHistory = false;
+  return MI_PT_OK;
+}
+
 void mi_pt_default_tonemapper(MiTonemapperData* tm, int autoExposure)
 {
   if(!tm)
@@ -2323,7 +2477,8 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                              + bytes(pt->optShadowAux2) + bytes(pt->queueMem) + bytes(pt->queuePayload) + bytes(pt->candPool) + bytes(pt->candLists);
   const uint64_t renderer = pathState + bytes(pt->firstHit) + bytes(pt->accumOwn)
                             + bytes(pt->albedo) + bytes(pt->normal) + bytes(pt->denoiseA) + bytes(pt->denoiseB) + bytes(pt->tonemapped) + bytes(pt->depth)
-                            + bytes(pt->selection) + bytes(pt->ownedTiles) + bytes(pt->sceneDev) + bytes(pt->fcRing) + bytes(pt->stats);
+                            + bytes(pt->selection) + bytes(pt->ownedTiles) + bytes(pt->sceneDev) + bytes(pt->fcRing) + bytes(pt->stats)
+                            + bytes(pt->motion) + bytes(pt->history) + bytes(pt->prevObjectToWorld);
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
   out->sceneBytes       = scene;

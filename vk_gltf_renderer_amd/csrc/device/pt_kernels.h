@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_scene.h"
+#include "pt_temporal.h"
 
 namespace pt {
 
@@ -54,6 +55,19 @@ void launchAtrous(const float4* in, float4* out, const float4* albedo, const flo
 
 const float4* launchSvgf(const float4* color, const float4* albedo, const float4* normal, const float* depth, float4* bufA, float4* bufB, int width, int height,
                          int iterations, float frames, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s);
+
+// the a-trous iterations + re-modulation of the pass above over an (illumination, variance) image prepared elsewhere (the temporal stage)
+const float4* launchSvgfFilter(float4* in, float4* other, const float4* color, const float4* albedo, const float4* normal, const float* depth, int width,
+                               int height, int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s);
+
+// motion vectors and temporal reprojection (temporal.hip, pt_temporal.h).  launchMotionVectors: the motion image of a first-frame batch from its
+// first-hit records (by pixel slot), then the snapshot of the render nodes' matrices as the next pose's "previous" ones
+void launchMotionVectors(const float4* firstHit, const uint32_t* ownedTiles, uint32_t numSlots, int tileShift, int width, int height,
+                         const MiGltfRenderNode* nodes, float* prevObjectToWorld, int numNodes, const float* viewProj, const float* prevMVP, float4* motion,
+                         hipStream_t s);
+void launchSnapshotTransforms(const MiGltfRenderNode* nodes, float* prevObjectToWorld, int numNodes, hipStream_t s);
+void launchSvgfReproject(const float4* color, const float4* albedo, const float4* normal, const float* depth, const float4* motion, const TemporalHistory& in,
+                         const TemporalHistory& out, float4* illum, int width, int height, const TemporalConsts& tc, bool haveHistory, hipStream_t s);
 
 // tonemapper (tonemap.hip): optional auto-exposure metering (histogram: 256 u32, autoState: 2 floats) + the curve, RGBA32F -> RGBA8
 void launchTonemap(const float4* in, uint32_t* outRgba8, int width, int height, const MiTonemapperData& tm, uint32_t* histogram, float* autoState,

@@ -326,7 +326,7 @@ struct PathSoA
   float4*   radiance;     // rgb, maxRoughness.x (>= 0) with the sign bit = !solid (RADW_NOT_SOLID); RADW_PRIMARY_MISS: rgb = the camera
                           // ray's direction (k_trace_primary) -- k_finish_sample reads this record alone.  Written when a path ENDS (its
                           // queue entry carries it while it lives), or at every bounce when the state lives by slot
-  float4*   firstHit;     // firstHitPos.xyz, unused.  Per PIXEL slot (pathSlotPixel): only frame 0 of a first-frame batch has one (NDC depth)
+  float4*   firstHit;     // firstHitPos.xyz (the ray direction of a miss), id bits (pt_temporal.h).  Per PIXEL slot (pathSlotPixel): only frame 0 of a first-frame batch has one (NDC depth)
   float4*   misc;         // maxRoughness.y, flags (uint bits), seed (uint bits), cone.width.  Multi-sample frames (the next sample starts from the
                           // seed) and state-by-slot frames; else null
   float4*   throughput;   // rgb, lastSamplePdf.  State-by-slot frames (shadow-catcher plane, MI_PT_STATE_BY_SLOT); else null

@@ -305,7 +305,7 @@
         {
           solid             = false;
           if(needFirstHit)
-            P.firstHit[pathSlotPixel(fc, slot)] = make_float4(rayDir.x, rayDir.y, rayDir.z, 0.0f);
+            P.firstHit[pathSlotPixel(fc, slot)] = make_float4(rayDir.x, rayDir.y, rayDir.z, 0.0f);  // (.w: id 0, a direction -- pt_temporal.h)
           backplate = primaryMissBackplate(sc, fc, rayDir, radiance);
         }
         if(!backplate)
@@ -344,7 +344,7 @@
             catcherPlane = true;
             coneWidth    = worldFoot;
             if(FIRST && needFirstHit)  // the reference leaves SampleResult::hitPosition at its 1e34 default on this path
-              P.firstHit[pathSlotPixel(fc, slot)] = make_float4(1e34f, 1e34f, 1e34f, 0.0f);
+              P.firstHit[pathSlotPixel(fc, slot)] = make_float4(1e34f, 1e34f, 1e34f, __uint_as_float(TEMPORAL_ID_INVALID));
             DirectLight dl;
             sampleLights(sc, fc, hit.pos, seed, dl);
             const bool traceIt = dot(dl.direction, hit.nrm) > 0.0f && dl.pdf != 0.0f;
@@ -402,7 +402,9 @@
           if(firstRay)  // gltf_pathtrace.slang:228-264
           {
             if(needFirstHit)
-              P.firstHit[pathSlotPixel(fc, slot)] = make_float4(hit.pos.x, hit.pos.y, hit.pos.z, 0.0f);
+              // .w: the bits of the first hit's id for the motion vectors (pt_temporal.h): renderNode + 1; 0 on the infinite plane, tested first --
+              // a plane in front of a mesh hit keeps that triangle's rnodeID
+              P.firstHit[pathSlotPixel(fc, slot)] = make_float4(hit.pos.x, hit.pos.y, hit.pos.z, __uint_as_float(hitInfinitePlane ? 0u : uint32_t(rnodeID + 1)));
             if(P.guideAlbedo)
             {
               float4 ga = make_float4(0, 0, 0, 0), gn = ga;

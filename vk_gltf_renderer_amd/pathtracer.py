@@ -185,6 +185,7 @@ class PathTracer:
         opts.bvhBuilder = bvh  # 0: 8-wide compressed BVH (default), 1: plain BVH2
         _check_pt(self._l.mi_pt_create(scene.desc, C.byref(opts), C.byref(self._p)))
         self.width = self.height = 0
+        self.temporal = False
 
     def update_render_nodes(self, render_nodes, count, visible=None):
         """New transforms / materials / visibility for the instances: rebuilds the acceleration structure on the device."""
@@ -331,6 +332,48 @@ class PathTracer:
                                              out.ctypes.data_as(C.POINTER(C.c_float)) if read else None, C.c_void_p(stream or 0)))
         return out
 
+    def set_temporal(self, enable=True):
+        """Motion vectors and temporal reprojection on / off (mi_pt_set_temporal): allocates the motion image, the history and the render
+        nodes' previous matrices; every first-frame batch is then followed by the motion kernel.  Drops the history."""
+        _check_pt(self._l.mi_pt_set_temporal(self._p, 1 if enable else 0))
+        self.temporal = bool(enable)
+
+    def read_first_hit(self):
+        """(H, W, 4) float32 of the last first-frame batch: xyz = first-hit position (ray direction where the id is 0); view the last
+        channel as uint32 for the id: renderNode + 1, 0 = miss / infinite plane, 0xffffffff = shadow-catcher path."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        _check_pt(self._l.mi_pt_read_first_hit(self._p, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def read_motion(self):
+        """(H, W, 4) float32 motion image of the last first-frame batch: xy = motion in pixels (towards where the point was), z = the NDC
+        depth it had, w = the id bits of read_first_hit."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        _check_pt(self._l.mi_pt_read_motion(self._p, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def default_temporal(self, **fields):
+        """MiPtTemporalParams with the library's defaults (mi_pt_default_temporal), fields overridden by name."""
+        tp = capi.MiPtTemporalParams()
+        self._l.mi_pt_default_temporal(C.byref(tp))
+        for k, v in fields.items():
+            setattr(tp, k, v)
+        return tp
+
+    def denoise_temporal(self, tp=None, read=True, stream=None, **fields):
+        """SVGF with temporal reprojection (mi_pt_denoise_temporal), once per pose; tp = MiPtTemporalParams (default: default_temporal()),
+        fields override members; read=False leaves the result on the device (tonemap(source=1) picks it up)."""
+        if tp is None:
+            tp = self.default_temporal()
+        for k, v in fields.items():
+            setattr(tp, k, v)
+        out = np.empty((self.height, self.width, 4), dtype=np.float32) if read else None
+        _check_pt(self._l.mi_pt_denoise_temporal(self._p, C.byref(tp), out.ctypes.data_as(C.POINTER(C.c_float)) if read else None, C.c_void_p(stream or 0)))
+        return out
+
+    def reset_history(self):
+        _check_pt(self._l.mi_pt_reset_history(self._p))
+
     def tonemap(self, tm=None, source=0, dt_seconds=-1.0, **fields):
         """HDR -> display RGBA8 (H, W, 4 uint8) on the device; tm = MiTonemapperData (default: the reference's defaults with auto exposure
         off), fields override members (method may be a name from capi.TONEMAP_METHODS); source 1 = the last denoise() result."""
@@ -387,9 +430,19 @@ class HeadlessRenderer:
         self.params = params
         self.frame_count = -1
         self.total_samples = 0
+        self._last_view_proj = None
 
     def reset_frame(self):
         self.frame_count = -1
+
+    def set_frame_info(self, fi):
+        """The camera of the next pose.  With the tracer's temporal reprojection on, prevMVP is filled with the viewProjMatrix of the
+        pose before (the first pose: its own), as the reference's onRender keeps it (src/renderer.cpp:675-705); starts a new accumulation."""
+        if self.tracer.temporal:
+            fi.prevMVP[:] = self._last_view_proj if self._last_view_proj is not None else fi.viewProjMatrix[:]
+            self._last_view_proj = fi.viewProjMatrix[:]
+        self.tracer.set_frame_info(fi)
+        self.reset_frame()
 
     def render(self, frames=1, stream=None, in_flight=1):
         """Advance `frames` frames; in_flight > 1 issues them in batches that share the wavefront launches."""
