@@ -388,7 +388,8 @@ MI_PT_API int mi_pt_read_first_hit(MiPt* pt, float* hostXYZW);
  * kernel and the snapshot of the matrices.  0 frees all of it.  Accumulator, guides, depth and selection do not depend on the setting. */
 MI_PT_API int mi_pt_set_temporal(MiPt* pt, int enable);
 /* The motion image of the last MI_PT_FIRST_FRAME batch, four floats per pixel: xy = (prevNDC - currNDC) * 0.5 * resolution in pixels (add to a pixel
- * centre to find where its point was; mesh hits move with their render node only, skinned or morphed vertices relative to it do not count),
+ * centre to find where its point was; mesh hits move with their render node only -- skinned or morphed vertices relative to it count under
+ * mi_pt_set_vertex_motion alone),
  * z = the NDC depth the point had under prevMVP (1 where the id is 0), w = the id bits as above (0xffffffff: zero motion).
  * MI_PT_ERR_STATE while the feature is off or before the first such batch. */
 MI_PT_API int mi_pt_read_motion(MiPt* pt, float* hostRGBA32F);
@@ -412,8 +413,32 @@ MI_PT_API void mi_pt_default_temporal(MiPtTemporalParams* params);
  * result in hostRGBA32F (may be NULL) and in the denoised image (mi_pt_tonemap source 1); alpha passes through.  Call it once per pose: every call
  * advances the history.  MI_PT_ERR_STATE: the feature is off, no first-frame batch since, or a tile partition with world > 1. */
 MI_PT_API int mi_pt_denoise_temporal(MiPt* pt, const MiPtTemporalParams* params, float* hostRGBA32F, void* hipStream);
-/* Forgets the history: the next mi_pt_denoise_temporal starts from its pose alone.  (mi_pt_resize, mi_pt_set_tile_partition and mi_pt_set_temporal do too.) */
+/* Forgets the history: the next mi_pt_denoise_temporal starts from its pose alone.  (mi_pt_resize, mi_pt_set_tile_partition, mi_pt_set_temporal and
+ * mi_pt_set_vertex_motion do too.) */
 MI_PT_API int mi_pt_reset_history(MiPt* pt);
+
+/* Vertex motion: carries skinned and morphed vertices in the motion image (our own; the reference moves a mesh hit with its render node alone).
+ * Off by default, and inert until mi_pt_set_temporal AND mi_pt_set_deformation are in force too -- the three may be called in any order; while it is not
+ * in force nothing is allocated and every image, read-back and byte of memory is what it is without it.  In force:
+ *   - every MI_PT_FIRST_FRAME batch records, next to the first hit, its triangle (16 B per owned pixel slot, in rendererBytes);
+ *   - the object-space positions of the pose rendered before are kept for every deforming render primitive (12 B per vertex, each primitive's array
+ *     padded to 16 B, + 32 B per render primitive of the scene + 4 B per deforming one, in sceneBytes), initialised to the resident positions here and by
+ *     every mi_pt_set_deformation, and copied from the resident positions on the batch's stream after the motion kernel of a MI_PT_FIRST_FRAME batch --
+ *     only when mi_pt_update_deformation ran since the last copy: they follow the RENDERED pose, not the update calls;
+ *   - a mesh hit on such a primitive gets, as its previous world position, prevObjectToWorld x (b0 p0 + b1 p1 + b2 p2): p the previous positions of the
+ *     hit triangle's vertices, b the hit's barycentrics.  A triangle whose nine previous floats equal its nine current ones BIT FOR BIT takes the rigid
+ *     path instead (a still character, the first pose, an update with unchanged tables), so zero motion stays exactly zero; so do hits on primitives
+ *     that do not deform.
+ * Flushes the frame queue, synchronises and forgets the history like mi_pt_set_temporal.  enable == 0 frees everything again. */
+MI_PT_API int mi_pt_set_vertex_motion(MiPt* pt, int enable);
+/* The triangle of the last MI_PT_FIRST_FRAME batch's first hit, four words per pixel in image order: render primitive, triangle index inside it (the whole
+ * source triangle, also where the acceleration structure holds pre-split references), the bits of the barycentrics b1 and b2 (b0 = 1 - b1 - b2) the hit's
+ * attributes are interpolated with.  The first word is 0xffffffff where the id of mi_pt_read_first_hit is 0 or 0xffffffff, and on pixels another rank
+ * owns.  MI_PT_ERR_STATE while vertex motion is not in force or before the first such batch after it came into force. */
+MI_PT_API int mi_pt_read_first_hit_triangle(MiPt* pt, uint32_t* hostPrimTriB1B2);
+/* The previous-pose positions of a deforming render primitive (vertexCount x 3 floats).  MI_PT_ERR_STATE while vertex motion is not in force,
+ * MI_PT_ERR_ARGUMENT for a render primitive the deformation tables do not deform. */
+MI_PT_API int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions);
 
 /* device address of the last denoise result (NULL before the first), valid until the next denoise / resize */
 MI_PT_API const void* mi_pt_denoised_device_ptr(MiPt* pt);
@@ -458,7 +483,8 @@ MI_PT_API const char* mi_pt_version(void);
  * 7: MiPtDeformPrimitive / MiPtDeformDesc and the deformation entry points (skins and morph targets on the device).
  * 8: MiPtAccelInfo and the refit entry points (mi_pt_set_accel_update, mi_pt_get_accel_info).
  * 9: MiPtTemporalParams and the motion / temporal entry points (mi_pt_read_first_hit, mi_pt_set_temporal, mi_pt_read_motion, mi_pt_denoise_temporal,
- *    mi_pt_reset_history). */
+ *    mi_pt_reset_history).  (Still 9: mi_pt_set_vertex_motion, mi_pt_read_first_hit_triangle, mi_pt_read_previous_positions -- new entry points, no
+ *    struct a caller allocates changed.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

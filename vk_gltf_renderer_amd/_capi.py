@@ -293,6 +293,9 @@ PT_SYMBOLS = {
     "mi_pt_default_temporal": (None, [P(MiPtTemporalParams)]),
     "mi_pt_denoise_temporal": (i32, [VP, P(MiPtTemporalParams), P(f32), VP]),
     "mi_pt_reset_history": (i32, [VP]),
+    "mi_pt_set_vertex_motion": (i32, [VP, i32]),
+    "mi_pt_read_first_hit_triangle": (i32, [VP, P(u32)]),
+    "mi_pt_read_previous_positions": (i32, [VP, i32, P(f32)]),
 }
 
 

@@ -721,7 +721,7 @@ void GltfRenderer::saveHeadlessOutputImage()
       m_pathTracer.denoiseOneShot();
     const int source = (m_pathTracer.isDenoiserEnabled() && m_pathTracer.hasValidDenoisedOutput()) ? 1 : 0;
     if(source)
-      printf("DENOISER passes=%d final_image=denoised%s\n", m_pathTracer.denoiseCount(), m_pathTracer.isTemporal() ? " temporal" : "");
+      printf("DENOISER passes=%d final_image=denoised%s\n", m_pathTracer.denoiseCount(), m_pathTracer.isVertexMotion() ? " temporal vertex-motion" : (m_pathTracer.isTemporal() ? " temporal" : ""));
     // a debug view is shown as it is, without the tonemapper; clay is shaded and keeps it (reference: src/renderer.cpp:1040-1046)
     MiTonemapperData tm  = m_resources.tonemapperData;
     const int        viz = m_resources.settings.visualization;

@@ -54,6 +54,8 @@ void PathTracer::registerParameters(ParameterRegistry* r)
   r->add("accelUpdate", "Acceleration structure on animated frames [rebuild:0, refit:1, auto:2]", &m_accelUpdate);
   // (our own) motion vectors and temporal reprojection for scenes and cameras that move: mi_pt_set_temporal right after mi_pt_create
   r->add("temporal", "Denoiser: temporal reprojection across poses (animated clips, camera moves); implies the denoiser", &m_temporal);
+  // (our own) skinned and morphed vertices in the motion vectors: mi_pt_set_vertex_motion; effective only with --temporal 1
+  r->add("vertexMotion", "Denoiser: motion vectors follow skinned / morphed vertices (with --temporal 1)", &m_vertexMotion);
   r->add("accelRebuildRatio", "auto: rebuild once the refitted tree's SAH cost exceeds this x the cost after the last build", &m_accelRebuildRatio);
 }
 
@@ -98,6 +100,11 @@ void PathTracer::onSceneInvalidated(Resources& res)
     {
       m_error = mi_pt_last_error();
       fprintf(stderr, "PathTracer: mi_pt_set_temporal failed: %s\n", m_error.c_str());
+    }
+    if(m_vertexMotion && mi_pt_set_vertex_motion(m_pt, 1) != MI_PT_OK)  // (in force once the scene's deformation tables are set)
+    {
+      m_error = mi_pt_last_error();
+      fprintf(stderr, "PathTracer: mi_pt_set_vertex_motion failed: %s\n", m_error.c_str());
     }
   }
   if(res.hdrIbl)

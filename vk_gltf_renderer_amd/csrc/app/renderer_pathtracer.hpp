@@ -48,6 +48,7 @@ public:
   int  denoiseCount() const { return m_denoiseCount; }
   bool denoisedIsCurrent() const { return m_hasDenoisedOutput && m_denoisedAtSamples == m_totalSamplesAccumulated; }
   bool isTemporal() const { return m_temporal; }
+  bool isVertexMotion() const { return m_temporal && m_vertexMotion; }
 
   // frames the next onRender traces in one go (1 = the reference's behaviour); what it actually did (1 whenever the adaptive
   // controller or the denoiser cadence need every frame's boundary)
@@ -79,6 +80,7 @@ private:
   // --temporal (our own): motion vectors + temporal reprojection (mi_pt_set_temporal); the denoiser is then the temporal pass, run ONCE per
   // pose -- when the next pose starts or the image is saved -- instead of on the auto-denoise cadence
   bool        m_temporal{false};
+  bool        m_vertexMotion{false};       // --vertexMotion (our own): mi_pt_set_vertex_motion, effective only with --temporal
   bool        m_poseOpen{false};           // the current pose has frames the temporal pass has not seen
   bool        m_havePoseViewProj{false};
   float       m_poseViewProj[16]{};        // viewProjMatrix of the current pose: the next pose's prevMVP

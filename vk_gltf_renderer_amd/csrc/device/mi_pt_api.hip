@@ -288,6 +288,16 @@ struct MiPt
   DevBuf<float4>          motion, history;       // history: 2 sets x 3 records x pixels
   DevBuf<float>           prevObjectToWorld;     // 16 floats per render node: the matrices of the pose rendered before
   std::vector<uint32_t>   ownedTilesHost;        // host copy of ownedTiles (mi_pt_read_first_hit)
+  // vertex motion (mi_pt_set_vertex_motion): in force while temporal and deformSet are too (vertexMotionActive); everything below exists only then
+  bool                    vertexMotion = false;  // as requested
+  bool                    haveFirstHitTri = false;  // a first-frame batch wrote firstHitTri
+  bool                    vmPoseDirty = false;   // mi_pt_update_deformation ran since the last snapshot of the positions
+  DevBuf<uint4>           firstHitTri;           // PathSoA::firstHitTri: per PIXEL slot
+  DevBuf<uint8_t>         vmPrevPositions;       // previous-pose positions of the deforming primitives: 12 B per vertex, each primitive padded to 16 B
+  DevBuf<pt::VertexMotionPrim> vmPrims;          // one record per render primitive
+  DevBuf<uint32_t>        vmDeformIDs;           // the deforming render primitives (k_snapshot_positions)
+  std::vector<size_t>     vmPrevOffset;          // per render primitive: byte offset into vmPrevPositions, SIZE_MAX = does not deform
+  uint32_t                vmMaxVertices = 0;
   DevBuf<uint32_t>        tonemapped, tmHistogram;
   DevBuf<float>           tmAutoState;
   float4*                 accum = nullptr;  // accumOwn.ptr or caller-bound memory
@@ -338,6 +348,67 @@ namespace {
 
 size_t align16(size_t v) { return (v + 15u) & ~size_t(15); }
 
+bool vertexMotionActive(const MiPt* pt) { return pt->vertexMotion && pt->temporal && pt->deformSet; }
+
+// The first-hit triangle records of vertex motion, at the current number of pixel slots; none while the feature is not in force.
+int allocFirstHitTri(MiPt* pt)
+{
+  pt->firstHitTri.release();
+  pt->paths.firstHitTri = nullptr;
+  pt->haveFirstHitTri   = false;
+  if(!vertexMotionActive(pt))
+    return MI_PT_OK;
+  const size_t n = std::max(size_t(std::max(pt->numSlots, 0)), size_t(1));
+  HIP_TRY(pt->firstHitTri.alloc(n));
+  HIP_TRY(hipMemset(pt->firstHitTri.ptr, 0xff, n * sizeof(uint4)));  // (no primitive: a record nobody wrote takes the rigid path)
+  pt->paths.firstHitTri = pt->firstHitTri.ptr;
+  return MI_PT_OK;
+}
+
+// Everything vertex motion owns, (re)made for the current switches, deformation tables and size: the triangle records, and the previous-pose
+// positions initialised to the resident ones.  The caller has synchronised the device.
+int allocVertexMotion(MiPt* pt)
+{
+  pt->vmPrevPositions.release();
+  pt->vmPrims.release();
+  pt->vmDeformIDs.release();
+  pt->vmPrevOffset.clear();
+  pt->vmMaxVertices = 0;
+  pt->vmPoseDirty   = false;
+  if(int rc = allocFirstHitTri(pt))
+    return rc;
+  if(!vertexMotionActive(pt))
+    return MI_PT_OK;
+  const size_t numPrims = pt->hostPrims.size();
+  pt->vmPrevOffset.assign(numPrims, SIZE_MAX);
+  size_t                bytes = 0;
+  std::vector<uint32_t> ids;
+  for(int id : pt->deformPrimIDs)
+  {
+    pt->vmPrevOffset[size_t(id)] = bytes;
+    bytes += align16(size_t(pt->primVertices[size_t(id)]) * 12);
+    pt->vmMaxVertices = std::max(pt->vmMaxVertices, pt->primVertices[size_t(id)]);
+    ids.push_back(uint32_t(id));
+  }
+  HIP_TRY(pt->vmPrevPositions.alloc(std::max<size_t>(bytes, 16)));
+  std::vector<pt::VertexMotionPrim> table(numPrims);
+  for(size_t i = 0; i < numPrims; ++i)
+  {
+    pt::VertexMotionPrim& v = table[i];
+    v.prevPositions = pt->vmPrevOffset[i] != SIZE_MAX ? reinterpret_cast<const float*>(pt->vmPrevPositions.ptr + pt->vmPrevOffset[i]) : nullptr;
+    v.positions     = pt->hostPrims[i].positions;
+    v.indices       = pt->hostPrims[i].indices;
+    v.numTriangles  = i < pt->primTriangles.size() ? pt->primTriangles[i] : 0u;
+    v.vertexCount   = pt->primVertices[i];
+  }
+  HIP_TRY(pt->vmPrims.upload(table.data(), table.size()));
+  HIP_TRY(pt->vmDeformIDs.upload(ids.data(), ids.size()));
+  pt::launchSnapshotPositions(pt->vmPrims.ptr, pt->vmDeformIDs.ptr, uint32_t(ids.size()), pt->vmMaxVertices, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return MI_PT_OK;
+}
+
 // Path state and ray queues for `frames` frames in flight (path slots are micro-tile major: pt::pathSlot).
 int allocPathResources(MiPt* pt, int frames)
 {
@@ -355,6 +426,8 @@ int allocPathResources(MiPt* pt, int frames)
   P              = pt::PathSoA{};
   P.radiance     = pt->pathArrays.ptr;
   P.firstHit     = pt->firstHit.ptr;
+  if(int rc = allocFirstHitTri(pt))
+    return rc;
   // sub-queue capacity: ceil(numChunks / NSUB) chunks (+1 of slack), see pt_scene.h
   const size_t numChunks = (n + pt::QCHUNK - 1) / pt::QCHUNK;
   const size_t subCap    = ((numChunks + pt::NSUB - 1) / pt::NSUB + 1) * pt::QCHUNK;
@@ -468,7 +541,7 @@ int allocTemporal(MiPt* pt)
   pt->history.release();
   pt->prevObjectToWorld.release();
   if(!pt->temporal)
-    return MI_PT_OK;
+    return allocVertexMotion(pt);
   const size_t px = size_t(std::max(pt->width, 0)) * size_t(std::max(pt->height, 0));
   HIP_TRY(pt->motion.alloc(px));
   HIP_TRY(pt->history.alloc(6 * px));
@@ -478,7 +551,7 @@ int allocTemporal(MiPt* pt)
   pt::launchSnapshotTransforms(pt->nodes.ptr, pt->prevObjectToWorld.ptr, int(pt->nodes.count), nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  return MI_PT_OK;
+  return allocVertexMotion(pt);
 }
 
 int allocFrameResources(MiPt* pt)
@@ -1434,7 +1507,7 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
   if(!desc)
   {
     releaseDeformation(pt);
-    return MI_PT_OK;
+    return allocVertexMotion(pt);
   }
   const int numPrims = int(pt->primVertices.size());
   if(desc->numPrims < 0 || desc->numJointMatrices < 0 || desc->numMorphWeights < 0 || (desc->numPrims > 0 && !desc->prims))
@@ -1480,7 +1553,7 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_deformation: too many vertices");
   releaseDeformation(pt);
   if(desc->numPrims == 0)
-    return MI_PT_OK;
+    return allocVertexMotion(pt);
   // ---- static upload: base poses (in the layout of DevPrim::verts, from the resident record: uv0 and the stream values that are not
   // deformed keep theirs), influences, deltas
   HIP_TRY(pt->deformPool.alloc(std::max<size_t>(poolBytes, 16)));
@@ -1559,7 +1632,7 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
   pt->deformSet         = true;
   for(int k = 0; k < desc->numPrims; ++k)
     pt->deformPrimIDs.push_back(desc->prims[k].renderPrimID);
-  return MI_PT_OK;
+  return allocVertexMotion(pt);  // (new tables: the previous-pose positions of vertex motion start from the resident ones again)
 }
 
 int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* morphWeights, int flags)
@@ -1604,6 +1677,7 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
   HIP_TRY(hipDeviceSynchronize());
   if(buildTiming)
     fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "deform", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  pt->vmPoseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
   for(int id : pt->deformPrimIDs)  // (what the next acceleration update refits; sized by a build that kept refit data)
     if(size_t(id) < pt->primDirty.size())
       pt->primDirty[size_t(id)] = pt->primDeformed[size_t(id)] = 1;
@@ -2138,9 +2212,17 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     pt->haveFirstHit = true;
     if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
     {
-      pt::launchMotionVectors(pt->firstHit.ptr, pt->ownedTiles.ptr, uint32_t(pt->numSlots), c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr,
-                              pt->prevObjectToWorld.ptr, int(pt->nodes.count), pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->motion.ptr, stream);
+      pt::launchMotionVectors(pt->firstHit.ptr, pt->firstHitTri.ptr, pt->vmPrims.ptr, int(pt->vmPrims.count), pt->ownedTiles.ptr, uint32_t(pt->numSlots),
+                              c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr, pt->prevObjectToWorld.ptr, int(pt->nodes.count),
+                              pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->motion.ptr, stream);
       pt->haveMotion = true;
+      if(pt->firstHitTri.ptr)  // vertex motion: the rendered pose's positions become the next pose's previous ones, when an update changed them
+      {
+        pt->haveFirstHitTri = true;
+        if(pt->vmPoseDirty)
+          pt::launchSnapshotPositions(pt->vmPrims.ptr, pt->vmDeformIDs.ptr, uint32_t(pt->vmDeformIDs.count), pt->vmMaxVertices, stream);
+        pt->vmPoseDirty = false;
+      }
     }
   }
   HIP_TRY(hipGetLastError());
@@ -2400,6 +2482,68 @@ int mi_pt_reset_history(MiPt* pt)
   return MI_PT_OK;
 }
 
+int mi_pt_set_vertex_motion(MiPt* pt, int enable)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_vertex_motion: null instance");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  pt->vertexMotion = enable != 0;
+  pt->haveHistory  = false;  // (the motion the history was reprojected along changes its meaning)
+  return allocVertexMotion(pt);
+}
+
+int mi_pt_read_first_hit_triangle(MiPt* pt, uint32_t* host)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !host || pt->width <= 0)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_first_hit_triangle: bad arguments");
+  if(!vertexMotionActive(pt) || !pt->haveFirstHitTri || !pt->haveFirstHit)
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_first_hit_triangle: needs vertex motion in force (mi_pt_set_vertex_motion, mi_pt_set_temporal, "
+                                 "mi_pt_set_deformation) and a MI_PT_FIRST_FRAME batch after it");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t        n = size_t(std::max(pt->numSlots, 0));
+  std::vector<float4> hits(n);
+  std::vector<uint4>  tris(n);
+  if(n)
+  {
+    HIP_TRY(hipMemcpy(hits.data(), pt->firstHit.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tris.data(), pt->firstHitTri.ptr, n * sizeof(uint4), hipMemcpyDeviceToHost));
+  }
+  memset(host, 0xff, size_t(pt->width) * size_t(pt->height) * sizeof(uint4));
+  int tileShift = 0;
+  while((1 << tileShift) < pt->tileSize)
+    ++tileShift;
+  for(uint32_t slot = 0; slot < uint32_t(n); ++slot)
+  {
+    int      px, py;
+    uint32_t id;
+    memcpy(&id, &hits[slot].w, sizeof(id));
+    if(id != 0u && id != pt::TEMPORAL_ID_INVALID && pt::pixelOfSlot(pt->ownedTilesHost.data(), tileShift, pt->width, pt->height, slot, px, py))
+      memcpy(host + 4 * (size_t(py) * size_t(pt->width) + size_t(px)), &tris[slot], sizeof(uint4));
+  }
+  return MI_PT_OK;
+}
+
+int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !positions)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: bad arguments");
+  if(!vertexMotionActive(pt))
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_previous_positions: vertex motion is not in force (mi_pt_set_vertex_motion, mi_pt_set_temporal, mi_pt_set_deformation)");
+  if(renderPrimID < 0 || size_t(renderPrimID) >= pt->vmPrevOffset.size() || pt->vmPrevOffset[size_t(renderPrimID)] == SIZE_MAX)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: render primitive " + std::to_string(renderPrimID) + " does not deform");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nv = pt->primVertices[size_t(renderPrimID)];
+  if(nv)
+    HIP_TRY(hipMemcpy(positions, pt->vmPrevPositions.ptr + pt->vmPrevOffset[size_t(renderPrimID)], nv * 12, hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+
 void mi_pt_default_tonemapper(MiTonemapperData* tm, int autoExposure)
 {
   if(!tm)
@@ -2470,7 +2614,8 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   uint64_t scene = bytes(pt->materials) + bytes(pt->texInfos) + bytes(pt->nodes) + bytes(pt->prims) + bytes(pt->lights) + bytes(pt->textures) + bytes(pt->texels) + bytes(pt->texQuads)
                    + bytes(pt->geometry) + bytes(pt->instFlags) + bytes(pt->srgbLut) + bytes(pt->envPixels) + bytes(pt->envAccel) + bytes(pt->alphaTris)
                    + bytes(pt->shadeTris) + bytes(pt->texRefs) + bytes(pt->coreTex) + bytes(pt->bvh8Planes) + bytes(pt->deformPool) + bytes(pt->deformTasks)
-                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights) + refitBytes(pt);
+                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights) + refitBytes(pt) + bytes(pt->vmPrevPositions) + bytes(pt->vmPrims)
+                   + bytes(pt->vmDeformIDs);
   // the acceleration structure is raw allocations: 64-B BVH2 nodes or 80-B BVH8 nodes + 48-B triangle records
   scene += uint64_t(pt->staticStats.bvhNodeCount) * pt->staticStats.bvhNodeBytes + uint64_t(sc.numTris) * sizeof(pt::DevTri);
   const uint64_t pathState = bytes(pt->pathArrays) + bytes(pt->optThroughput) + bytes(pt->optMisc) + bytes(pt->optMedium) + bytes(pt->optPixelSum) + bytes(pt->optGuides)
@@ -2478,7 +2623,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   const uint64_t renderer = pathState + bytes(pt->firstHit) + bytes(pt->accumOwn)
                             + bytes(pt->albedo) + bytes(pt->normal) + bytes(pt->denoiseA) + bytes(pt->denoiseB) + bytes(pt->tonemapped) + bytes(pt->depth)
                             + bytes(pt->selection) + bytes(pt->ownedTiles) + bytes(pt->sceneDev) + bytes(pt->fcRing) + bytes(pt->stats)
-                            + bytes(pt->motion) + bytes(pt->history) + bytes(pt->prevObjectToWorld);
+                            + bytes(pt->motion) + bytes(pt->history) + bytes(pt->prevObjectToWorld) + bytes(pt->firstHitTri);
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
   out->sceneBytes       = scene;

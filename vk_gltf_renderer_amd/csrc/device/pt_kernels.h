@@ -61,11 +61,15 @@ const float4* launchSvgfFilter(float4* in, float4* other, const float4* color, c
                                int height, int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, hipStream_t s);
 
 // motion vectors and temporal reprojection (temporal.hip, pt_temporal.h).  launchMotionVectors: the motion image of a first-frame batch from its
-// first-hit records (by pixel slot), then the snapshot of the render nodes' matrices as the next pose's "previous" ones
-void launchMotionVectors(const float4* firstHit, const uint32_t* ownedTiles, uint32_t numSlots, int tileShift, int width, int height,
-                         const MiGltfRenderNode* nodes, float* prevObjectToWorld, int numNodes, const float* viewProj, const float* prevMVP, float4* motion,
-                         hipStream_t s);
+// first-hit records (by pixel slot), then the snapshot of the render nodes' matrices as the next pose's "previous" ones.  firstHitTri (with
+// vmPrims, one record per render primitive) non-NULL: vertex motion -- hits on deforming primitives move with their previous-pose vertices
+void launchMotionVectors(const float4* firstHit, const uint4* firstHitTri, const VertexMotionPrim* vmPrims, int numPrims, const uint32_t* ownedTiles,
+                         uint32_t numSlots, int tileShift, int width, int height, const MiGltfRenderNode* nodes, float* prevObjectToWorld, int numNodes,
+                         const float* viewProj, const float* prevMVP, float4* motion, hipStream_t s);
 void launchSnapshotTransforms(const MiGltfRenderNode* nodes, float* prevObjectToWorld, int numNodes, hipStream_t s);
+// current resident positions -> previous-pose positions of the deforming primitives `ids` (indices into vmPrims), all in one launch;
+// maxVertexCount: the largest vertexCount among them
+void launchSnapshotPositions(const VertexMotionPrim* vmPrims, const uint32_t* ids, uint32_t numIds, uint32_t maxVertexCount, hipStream_t s);
 void launchSvgfReproject(const float4* color, const float4* albedo, const float4* normal, const float* depth, const float4* motion, const TemporalHistory& in,
                          const TemporalHistory& out, float4* illum, int width, int height, const TemporalConsts& tc, bool haveHistory, hipStream_t s);
 

@@ -334,6 +334,8 @@ struct PathSoA
   float4*   pixelSum;     // sum over the frame's samples of the clamped radiance rgba.  Multi-sample frames; else null
   float4*   guideAlbedo;  // optional (denoiser guides): sum over samples
   float4*   guideNormal;
+  uint4*    firstHitTri;  // optional (vertex motion, pt_temporal.h): render primitive, triangle inside it, bits of the barycentrics b1, b2 of the mesh hit
+                          // `firstHit` records.  Per PIXEL slot like firstHit
 };
 
 // Work queues.  Every logical queue is split into NSUB sub-queues so that appends hit 16 different counter words instead

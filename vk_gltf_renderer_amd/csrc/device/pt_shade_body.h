@@ -259,6 +259,11 @@
         }
         hit = getHitState(&gat(sc.geomPool, S.v0), &gat(sc.geomPool, S.v1), &gat(sc.geomPool, S.v2), S.attrs, &rp, ti,
                           mk3(1.0f - hit4.z - hit4.w, hit4.z, hit4.w), rn.worldToObject, rn.objectToWorld, rayDir, VIZ ? &frontFace : nullptr);
+        // The triangle of the first-hit record (vertex motion), written here where the record and the barycentrics are at hand and nothing has to
+        // stay alive for it: a first ray's mesh hit that needs the first hit either gets the mesh-hit `firstHit` store below from this same lane, or lies
+        // behind the infinite plane, whose id 0 makes every reader ignore this record.
+        if(P.firstHitTri && firstRay && needFirstHit)
+          P.firstHitTri[pathSlotPixel(fc, slot)] = make_uint4(uint32_t(S.renderPrimID), S.prim, __float_as_uint(hit4.z), __float_as_uint(hit4.w));
         if constexpr(VIZ)
         {
           rprimID = S.renderPrimID;

@@ -6,9 +6,11 @@
 //   motion record: xy = (prevNDC - currNDC) * 0.5 * resolution in pixels (the reference's calculateMotionVector, dlss_util.h:63-96: surfaces
 //   are points (w = 1) carried by their node's previous objectToWorld, gltf_pathtrace.slang:228-241; id 0 are points at infinity (w = 0), so
 //   that a camera translation cancels); z = the NDC depth the point had under prevMVP (1 for id 0); w = the id bits.
+//   With vertex motion on (motionRecordDeformed, below) a hit on skinned or morphed geometry is carried by its triangle's previous-pose vertices.
 #pragma once
 #include "mi_pt_shaderio.h"
 #include "pt_math.h"
+#include "pt_scene.h"
 
 namespace pt {
 
@@ -102,6 +104,15 @@ PT_DEV f4 mulChain(const float* M, float x, float y, float z, float w)
   return r;
 }
 
+// Projects the current point (the first-hit record's xyz) and the point `pp` it was in the previous pose; w = 1 for a surface point, 0 for a direction.
+PT_DEV float4 motionOfPoints(const float4 fh, const f3 pp, uint32_t id, const float* viewProj, const float* prevMVP, float width, float height)
+{
+  const float w   = id != 0u ? 1.0f : 0.0f;
+  const f4    cur = mulChain(viewProj, fh.x, fh.y, fh.z, w), prv = mulChain(prevMVP, pp.x, pp.y, pp.z, w);
+  const float cx = divExact(cur.x, cur.w), cy = divExact(cur.y, cur.w), qx = divExact(prv.x, prv.w), qy = divExact(prv.y, prv.w);
+  return make_float4((qx - cx) * 0.5f * width, (qy - cy) * 0.5f * height, id != 0u ? divExact(prv.z, prv.w) : 1.0f, fh.w);
+}
+
 // The motion record of a first-hit record.  prevObjectToWorld: 16 floats per render node, the matrices of the pose rendered before.
 PT_DEV float4 motionRecord(const float4 fh, const MiGltfRenderNode* __restrict__ nodes, const float* __restrict__ prevObjectToWorld, int numNodes,
                            const float* viewProj, const float* prevMVP, float width, float height)
@@ -109,8 +120,7 @@ PT_DEV float4 motionRecord(const float4 fh, const MiGltfRenderNode* __restrict__
   const uint32_t id = __float_as_uint(fh.w);
   if(id == TEMPORAL_ID_INVALID || id > uint32_t(numNodes))
     return make_float4(0.0f, 0.0f, 1.0f, __uint_as_float(TEMPORAL_ID_INVALID));
-  const float w  = id != 0u ? 1.0f : 0.0f;
-  f3          pp = mk3(fh.x, fh.y, fh.z);  // where the point was in the previous pose
+  f3 pp = mk3(fh.x, fh.y, fh.z);  // where the point was in the previous pose
   if(id != 0u)
   {
     const MiGltfRenderNode& rn   = nodes[id - 1u];
@@ -124,9 +134,62 @@ PT_DEV float4 motionRecord(const float4 fh, const MiGltfRenderNode* __restrict__
       pp           = xyz(mulChain(prev, obj.x, obj.y, obj.z, 1.0f));
     }
   }
-  const f4    cur = mulChain(viewProj, fh.x, fh.y, fh.z, w), prv = mulChain(prevMVP, pp.x, pp.y, pp.z, w);
-  const float cx = divExact(cur.x, cur.w), cy = divExact(cur.y, cur.w), qx = divExact(prv.x, prv.w), qy = divExact(prv.y, prv.w);
-  return make_float4((qx - cx) * 0.5f * width, (qy - cy) * 0.5f * height, id != 0u ? divExact(prv.z, prv.w) : 1.0f, fh.w);
+  return motionOfPoints(fh, pp, id, viewProj, prevMVP, width, height);
+}
+
+// ---- vertex motion (mi_pt_set_vertex_motion): skinned and morphed vertices carried in the motion record -------------------------------
+// first-hit triangle record (PathSoA::firstHitTri, next to the first-hit record): x = render primitive, y = triangle index inside it (the whole
+// source triangle, also where the tree holds pre-split references), z, w = the BITS of the barycentrics b1, b2 the shade interpolates the
+// attributes with (b0 = 1 - b1 - b2).  Written for mesh hits only: it means something where the first-hit id names a render node.
+
+// What the motion kernel needs of a render primitive, indexed by render primitive.  prevPositions: the object-space positions of the pose
+// rendered before (3 floats per vertex), NULL for a primitive that does not deform.
+struct VertexMotionPrim
+{
+  const float*    prevPositions;
+  const float*    positions;  // the resident stream (DevPrim::positions): the pose being rendered
+  const uint32_t* indices;    // DevPrim::indices
+  uint32_t        numTriangles, vertexCount;
+};
+
+// The motion record of a first hit on deforming geometry: the material point's previous position is the barycentric interpolation of its
+// triangle's previous-pose vertices, carried by the node's previous objectToWorld.  A triangle whose nine previous floats equal its nine
+// current ones bit for bit (a still character, the first pose, an update with unchanged tables) takes motionRecord's path -- and so does a
+// record that names no deforming primitive -- so that zero motion stays exactly zero.
+PT_DEV float4 motionRecordDeformed(const float4 fh, const uint4 tri, const VertexMotionPrim* __restrict__ prims, int numPrims,
+                                   const MiGltfRenderNode* __restrict__ nodes, const float* __restrict__ prevObjectToWorld, int numNodes,
+                                   const float* viewProj, const float* prevMVP, float width, float height)
+{
+  const uint32_t id = __float_as_uint(fh.w);
+  if(id != 0u && id != TEMPORAL_ID_INVALID && id <= uint32_t(numNodes) && tri.x < uint32_t(numPrims))
+  {
+    const VertexMotionPrim& vp = prims[tri.x];
+    if(vp.prevPositions && tri.y < vp.numTriangles)
+    {
+      // (the record's pointers are generic to the compiler; gat() reads them as the global memory they are, pt_scene.h)
+      const uint32_t* ix = &gat(vp.indices, 3u * size_t(tri.y));
+      const uint32_t  i0 = ix[0], i1 = ix[1], i2 = ix[2];
+      if(i0 < vp.vertexCount && i1 < vp.vertexCount && i2 < vp.vertexCount)
+      {
+        const float *p0 = &gat(vp.prevPositions, 3u * size_t(i0)), *p1 = &gat(vp.prevPositions, 3u * size_t(i1)), *p2 = &gat(vp.prevPositions, 3u * size_t(i2));
+        const float *c0 = &gat(vp.positions, 3u * size_t(i0)), *c1 = &gat(vp.positions, 3u * size_t(i1)), *c2 = &gat(vp.positions, 3u * size_t(i2));
+        bool         deformed = false;
+        for(int k = 0; k < 3; ++k)
+          deformed = deformed || __float_as_uint(p0[k]) != __float_as_uint(c0[k]) || __float_as_uint(p1[k]) != __float_as_uint(c1[k])
+                     || __float_as_uint(p2[k]) != __float_as_uint(c2[k]);
+        if(deformed)
+        {
+          const float b1 = __uint_as_float(tri.z), b2 = __uint_as_float(tri.w), b0 = 1.0f - b1 - b2;
+          const float ox = __builtin_fmaf(b2, p2[0], __builtin_fmaf(b1, p1[0], b0 * p0[0]));
+          const float oy = __builtin_fmaf(b2, p2[1], __builtin_fmaf(b1, p1[1], b0 * p0[1]));
+          const float oz = __builtin_fmaf(b2, p2[2], __builtin_fmaf(b1, p1[2], b0 * p0[2]));
+          const f3    pp = xyz(mulChain(prevObjectToWorld + size_t(id - 1u) * 16u, ox, oy, oz, 1.0f));
+          return motionOfPoints(fh, pp, id, viewProj, prevMVP, width, height);
+        }
+      }
+    }
+  }
+  return motionRecord(fh, nodes, prevObjectToWorld, numNodes, viewProj, prevMVP, width, height);
 }
 
 // One pixel of the temporal stage: reprojects the history along the motion record, blends this pose's demodulated colour and luminance

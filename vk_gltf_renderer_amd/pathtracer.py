@@ -352,6 +352,25 @@ class PathTracer:
         _check_pt(self._l.mi_pt_read_motion(self._p, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def set_vertex_motion(self, enable=True):
+        """Skinned and morphed vertices carried in the motion image (mi_pt_set_vertex_motion): in force once set_temporal and set_deformation
+        are too, in any order.  Records the first hit's triangle and keeps the deforming primitives' previous-pose positions.  Drops the history."""
+        _check_pt(self._l.mi_pt_set_vertex_motion(self._p, 1 if enable else 0))
+
+    def read_first_hit_triangle(self):
+        """(H, W, 4) uint32 of the last first-frame batch: render primitive, triangle index inside it, the bits of the barycentrics b1, b2
+        (view as float32; b0 = 1 - b1 - b2).  The first word is 0xffffffff where read_first_hit's id is 0 or 0xffffffff."""
+        out = np.empty((self.height, self.width, 4), dtype=np.uint32)
+        _check_pt(self._l.mi_pt_read_first_hit_triangle(self._p, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def read_previous_positions(self, prim):
+        """(V, 3) float32: the positions render primitive `prim` had in the pose rendered before (mi_pt_read_previous_positions)."""
+        n = int(self._scene.desc.contents.renderPrimitives[prim].vertexCount)
+        out = np.zeros((n, 3), np.float32)
+        _check_pt(self._l.mi_pt_read_previous_positions(self._p, int(prim), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def default_temporal(self, **fields):
         """MiPtTemporalParams with the library's defaults (mi_pt_default_temporal), fields overridden by name."""
         tp = capi.MiPtTemporalParams()
