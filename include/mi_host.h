@@ -62,6 +62,20 @@ MI_PT_API int                  mi_mikktspace(const float* positions, const float
  * only, and mi_pt_update_materials refuses an alpha change on cut geometry -- so the loader's own animations never meet that refusal. */
 MI_PT_API int64_t              mi_scene_cut_alpha(MiScene* scene, int subdivisions);
 
+/* KHR_materials_variants at run time (reference: Scene::setCurrentVariant, src/gltf_scene.cpp:2038-2072; the load resolves variant 0).
+ * mi_scene_set_variant rewrites the materialID of the render-node table of mi_scene_desc() in place -- same pointers, same counts -- ready for
+ * mi_pt_update_render_nodes(), like the matrices after an animation step.  Per primitive: the material of the first mapping whose `variants`
+ * list holds the variant, else max(0, primitive.material), never beyond the material table; every render node made from the primitive gets
+ * it, EXT_mesh_gpu_instancing instances included.  Returns the number of render nodes whose material changed (0 is a valid result), or
+ * MI_PT_ERR_ARGUMENT with nothing changed: a variant outside [0, mi_scene_num_variants), or a switch that would give a primitive cut by
+ * mi_scene_cut_alpha (opaqueTriangleCount > 0) a material with another alpha state (alphaMode, alphaCutoff, base / diffuse alpha factor or
+ * texture) -- the cut classified its triangles under the old one and is applied once per loaded scene: load again, switch, then cut.
+ * mi_scene_variant_name: MI_PT_ERR_ARGUMENT for an index out of range; the name is truncated to nameCapacity - 1 characters. */
+MI_PT_API int                  mi_scene_num_variants(const MiScene* scene);
+MI_PT_API int                  mi_scene_variant_name(const MiScene* scene, int index, char* name, int nameCapacity);
+MI_PT_API int                  mi_scene_current_variant(const MiScene* scene);
+MI_PT_API int                  mi_scene_set_variant(MiScene* scene, int variant);
+
 /* Keyframe animation of node transforms (reference: nvvkgltf::AnimationSystem, src/gltf_scene_animation.hpp:93-122; AnimationInfo
  * src/gltf_scene.hpp:159-189; driven per frame by GltfRenderer::updateAnimation, src/renderer.cpp:2065-2170).  Translation /
  * rotation / scale channels and morph-target `weights` channels with LINEAR, STEP and CUBICSPLINE samplers.

@@ -284,6 +284,37 @@ typedef struct MiPtAccelInfo
   uint64_t refitBytes;        /* device memory of the refit data (counted in MiPtMemory::sceneBytes) */
 } MiPtAccelInfo;
 MI_PT_API int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* info);
+/* Resident mode: visibility and material-id changes of mi_pt_update_render_nodes without a build (reference: a hidden instance keeps its
+ * TLAS entry with blasAddress = 0, a material change is an instance-flag update, both through the TLAS update path;
+ * src/gltf_scene_rtx.cpp:317-334).  Off by default; while it is off every update does what it did before.  In force when enabled AND the
+ * structure holds refit data (mode REFIT or AUTO, 8-wide walk, no MI_PT_HOST_COLLAPSE): enabling under REBUILD is accepted and stays inert
+ * until mi_pt_set_accel_update allows refits -- either order of the two calls ends in the same state.  In force,
+ *  - the tree is built over EVERY render node that owns triangles, hidden ones included, as if all were visible; hidden nodes are then
+ *    hidden by a refit: their triangle slots become degenerate records with empty boxes, children with nothing visible below them get the
+ *    inverted boxes of empty slots, so the walks skip them.  The slots stay resident: a hidden triangle costs ~130 B of device memory (record,
+ *    shade record, two refit boxes; 48 B more in a scene with alpha records), counts towards the 2^26-slot limit of the 8-wide walk and is
+ *    counted by mi_pt_get_memory and MiPtStats::bvhTriangleCount.  sahCostAtBuild is the all-visible cost, which AUTO compares with;
+ *  - a visibility change is a refit (a node that comes back takes its current matrices and pose; one that stays hidden costs nothing), a
+ *    materialID change is a patch of the flag words, alpha records and shade records of that node's slots (the kernel of
+ *    mi_pt_update_materials) that follows the scene-wide summaries like mi_pt_update_materials does; one update may carry matrices, visibility
+ *    and material ids at once.  The next frames render bit for bit what a fresh instance of the same tables and visibility renders;
+ *  - still a build (counted): a renderPrimID change; a material-id change that flips the transmissive bit of a node while the tree holds
+ *    pre-split references; AUTO's cost bound.  A build in resident mode builds the resident tree;
+ *  - MI_PT_ERR_ARGUMENT, with NOTHING changed: a material-id change that alters the alpha state of geometry mi_scene_cut_alpha cut at load
+ *    (opaqueTriangleCount > 0), as in mi_pt_update_materials.
+ * Enabling rebuilds once inside the call when it comes into force (a build, like the switch to REFIT); disabling rebuilds once over the
+ * visible nodes.  Synchronises like an update. */
+MI_PT_API int mi_pt_set_accel_resident(MiPt* pt, int enable);
+typedef struct MiPtAccelResidentInfo
+{
+  int32_t  enabled;            /* as requested */
+  int32_t  inForce;            /* the resident tree exists and updates use it */
+  uint64_t residentTriangles;  /* triangle slots of the resident tree, hidden ones included (0 while not in force) */
+  uint64_t hiddenTriangles;    /* triangles of the hidden render nodes among them (a pre-split triangle holds several slots and counts once) */
+  uint64_t visibilityRefits;   /* updates whose visibility change was served by a refit */
+  uint64_t materialPatches;    /* updates whose material-id change was served by a patch */
+} MiPtAccelResidentInfo;
+MI_PT_API int mi_pt_get_accel_resident_info(MiPt* pt, MiPtAccelResidentInfo* info);
 /* Reads back the resident streams of a render primitive (vertexCount x 3 / 3 / 4 floats); any pointer may be NULL, and a stream the
  * primitive does not have is left untouched. */
 MI_PT_API int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* normals, float* tangents);

@@ -149,6 +149,11 @@ class MiPtAccelInfo(C.Structure):
                 ("sahCostAtBuild", C.c_double), ("sahCost", C.c_double), ("trianglesMoved", C.c_uint64), ("refitBytes", C.c_uint64)]
 
 
+class MiPtAccelResidentInfo(C.Structure):
+    _fields_ = [("enabled", i32), ("inForce", i32), ("residentTriangles", C.c_uint64), ("hiddenTriangles", C.c_uint64),
+                ("visibilityRefits", C.c_uint64), ("materialPatches", C.c_uint64)]
+
+
 class MiPtTemporalParams(C.Structure):
     _fields_ = [("iterations", i32), ("sigmaLuminance", f32), ("sigmaNormal", f32), ("sigmaDepth", f32), ("alpha", f32), ("momentsAlpha", f32),
                 ("maxHistory", f32), ("normalCos", f32), ("depthTolerance", f32)]
@@ -165,6 +170,7 @@ assert C.sizeof(MiGltfTextureInfo) == 32
 assert C.sizeof(MiGltfShadeMaterial) == 288
 assert C.sizeof(MiSceneFrameInfo) == 396
 assert C.sizeof(MiPtAccelInfo) == 64
+assert C.sizeof(MiPtAccelResidentInfo) == 40
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
@@ -230,6 +236,10 @@ HOST_SYMBOLS = {
     "mi_scene_recompute_tangents": (i32, [VP, i32, i32]),
     "mi_mikktspace": (i32, [P(f32), P(f32), P(f32), u32, P(u32), u32, P(f32)]),
     "mi_scene_cut_alpha": (C.c_int64, [VP, i32]),
+    "mi_scene_num_variants": (i32, [VP]),
+    "mi_scene_variant_name": (i32, [VP, i32, C.c_char_p, i32]),
+    "mi_scene_current_variant": (i32, [VP]),
+    "mi_scene_set_variant": (i32, [VP, i32]),
     "mi_scene_num_animations": (i32, [VP]),
     "mi_scene_animation_info": (i32, [VP, i32, P(f32), P(f32), C.c_char_p, i32]),
     "mi_scene_update_animation": (i32, [VP, i32, f32]),
@@ -287,6 +297,8 @@ PT_SYMBOLS = {
     "mi_pt_read_vertices": (i32, [VP, i32, P(f32), P(f32), P(f32)]),
     "mi_pt_set_accel_update": (i32, [VP, i32, f32]),
     "mi_pt_get_accel_info": (i32, [VP, P(MiPtAccelInfo)]),
+    "mi_pt_set_accel_resident": (i32, [VP, i32]),
+    "mi_pt_get_accel_resident_info": (i32, [VP, P(MiPtAccelResidentInfo)]),
     "mi_pt_read_first_hit": (i32, [VP, P(f32)]),
     "mi_pt_set_temporal": (i32, [VP, i32]),
     "mi_pt_read_motion": (i32, [VP, P(f32)]),

@@ -43,6 +43,8 @@ void GltfRenderer::registerParameters(ParameterRegistry* r)
   // the reference consumes baked opacity micro-maps (EXT_mesh_opacity_micromap) when --useOpacityMicromap is on (src/main.cpp:114-115);
   // the counterpart here is baked at load time from the alpha texture (mi_scene_cut_alpha)
   r->add("useOpacityMicromap", "Bake alpha-MASK geometry at load time (see --alphaCut)", &m_useOpacityMicromap);
+  // the reference switches variants from the UI (Scene::setCurrentVariant, src/gltf_scene.cpp:2038-2072); here a start-up option
+  r->add("variant", "KHR_materials_variants: index of the material variant applied after loading", &m_variant);
   r->add("alphaCut", "Alpha bake: subdivisions per triangle edge [2..16], 0 = off", &m_alphaCut);
   // animation playback (the reference drives AnimationControl from its UI strip only; these switches are this port's headless handle)
   AnimationControl& ac = m_resources.animationControl;
@@ -209,6 +211,16 @@ bool GltfRenderer::createScene(const std::string& sceneFile)
   mi_scene_camera(m_resources.scene, 0, &m_resources.camera);
   resetFrame();
   m_pathTracer.onSceneInvalidated(m_resources);
+  // --variant: the scene loads under variant 0; the switch goes through the update path of the renderer just created (a patch under
+  // --accelResident, a rebuild otherwise), as a switch during a session would
+  if(m_variant != 0)
+  {
+    const MiPtSceneDesc* d = mi_scene_desc(m_resources.scene);
+    if(mi_scene_set_variant(m_resources.scene, m_variant) < 0)
+      fprintf(stderr, "variant: %s\n", mi_host_last_error());
+    else if(m_pathTracer.handle() && mi_pt_update_render_nodes(m_pathTracer.handle(), d->renderNodes, d->numRenderNodes, d->renderNodeVisible) != MI_PT_OK)
+      fprintf(stderr, "variant: %s\n", mi_pt_last_error());
+  }
   return m_pathTracer.handle() != nullptr;
 }
 

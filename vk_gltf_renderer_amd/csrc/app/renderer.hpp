@@ -53,6 +53,7 @@ private:
   int                 m_recomputeTangents{0};
   bool                m_useOpacityMicromap{true};
   int                 m_alphaCut{4};
+  int                 m_variant{0};  // --variant (our own): KHR_materials_variants index applied after the load (mi_scene_set_variant)
   int                 m_animClip{-1};
   float               m_animTime{0.0f};
   MiPt*               m_deformSetFor{nullptr};  // the path-tracer instance the scene's skin / morph tables were uploaded to

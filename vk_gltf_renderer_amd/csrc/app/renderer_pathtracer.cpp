@@ -56,6 +56,8 @@ void PathTracer::registerParameters(ParameterRegistry* r)
   r->add("temporal", "Denoiser: temporal reprojection across poses (animated clips, camera moves); implies the denoiser", &m_temporal);
   // (our own) skinned and morphed vertices in the motion vectors: mi_pt_set_vertex_motion; effective only with --temporal 1
   r->add("vertexMotion", "Denoiser: motion vectors follow skinned / morphed vertices (with --temporal 1)", &m_vertexMotion);
+  // (our own) resident mode: hidden render nodes stay in the tree, so that visibility and material variants need no build (mi_pt_set_accel_resident, right after --accelUpdate)
+  r->add("accelResident", "Keep hidden render nodes in the tree: visibility and material changes refit / patch instead of rebuilding (with --accelUpdate 1 | 2)", &m_accelResident);
   r->add("accelRebuildRatio", "auto: rebuild once the refitted tree's SAH cost exceeds this x the cost after the last build", &m_accelRebuildRatio);
 }
 
@@ -88,6 +90,14 @@ void PathTracer::onSceneInvalidated(Resources& res)
   {
     m_error = mi_pt_last_error();
     fprintf(stderr, "PathTracer: mi_pt_set_accel_update failed: %s\n", m_error.c_str());
+    mi_pt_destroy(m_pt);
+    m_pt = nullptr;
+    return;
+  }
+  if(m_accelResident && mi_pt_set_accel_resident(m_pt, 1) != MI_PT_OK)
+  {
+    m_error = mi_pt_last_error();
+    fprintf(stderr, "PathTracer: mi_pt_set_accel_resident failed: %s\n", m_error.c_str());
     mi_pt_destroy(m_pt);
     m_pt = nullptr;
     return;

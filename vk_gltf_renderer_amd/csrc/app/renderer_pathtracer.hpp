@@ -76,6 +76,7 @@ private:
   int         m_performanceTarget{1};      // Balanced
   bool        m_collectCounters{false};    // --ptCounters (our own): MiPtCreateOptions::collectCounters
   int         m_accelUpdate{0};            // --accelUpdate (our own): MI_PT_ACCEL_REBUILD / REFIT / AUTO
+  bool        m_accelResident{false};      // --accelResident (our own): mi_pt_set_accel_resident
   float       m_accelRebuildRatio{1.5f};   // --accelRebuildRatio: AUTO's bound (mi_pt_set_accel_update)
   // --temporal (our own): motion vectors + temporal reprojection (mi_pt_set_temporal); the denoiser is then the temporal pass, run ONCE per
   // pose -- when the next pose starts or the image is saved -- instead of on the auto-denoise cadence

@@ -136,6 +136,17 @@ PT_DEV float refitBoxArea(const float lo[3], const float hi[3])
   const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
   return __fmaf_rn(ez, ex, __fmaf_rn(ey, ez, ex * ey));
 }
+// An EMPTY box -- nothing visible below it (resident mode: the slots of hidden render nodes) -- is the neutral element of the union,
+// lo = FLT_MAX, hi = -FLT_MAX: fminf / fmaxf pass the other operand through, so a union needs no test for it.  What must not see
+// +-FLT_MAX is the arithmetic: an empty box has area 0 and no place in a node's frame.
+PT_DEV bool refitBoxEmpty(const float lo[3], const float hi[3])
+{
+  return lo[0] > hi[0];
+}
+PT_DEV float refitBoxAreaOrZero(const float lo[3], const float hi[3])
+{
+  return refitBoxEmpty(lo, hi) ? 0.0f : refitBoxArea(lo, hi);
+}
 
 // What a triangle slot's render node did since the last update (the dirty byte table of k_refit_tris)
 enum : uint8_t
@@ -144,6 +155,9 @@ enum : uint8_t
   REFIT_MOVED = 1,  // moved or deformed: record and box from the current pose; a pre-split reference gets its whole triangle's box
   REFIT_HOME  = 2,  // changed, and back at the matrices of the last build with a primitive not deformed since: record from the current
                     // pose, box = the one the build filed (a deformed primitive is never HOME until the next build: its vertices are not compared)
+  REFIT_HIDDEN = 3,  // became invisible (resident mode): a degenerate record -- a point at the origin, like a non-finite triangle -- that keeps
+                     // its render node, triangle index and flag word, and an empty box.  A node that STAYS hidden is CLEAN; one that comes
+                     // back is HOME or MOVED
 };
 
 // k_refit_tris, one triangle slot `s`: rewrites the record and the slot box of a slot whose render node is not clean.  The record's
@@ -156,6 +170,16 @@ PT_DEV void refitTriSlot(const MiGltfRenderNode* nodes, const DevPrim* prims, co
   const uint8_t  state = dirty[rnode];
   if(state == REFIT_CLEAN)
     return;
+  if(state == REFIT_HIDDEN)
+  {
+    tris[s].a = make_float4(0.0f, 0.0f, 0.0f, a.w);
+    tris[s].b = make_float4(0.0f, 0.0f, 0.0f, tris[s].b.w);
+    tris[s].c = make_float4(0.0f, 0.0f, 0.0f, tris[s].c.w);
+    RefitBox empty;
+    for(int k = 0; k < 3; ++k) { empty.lo[k] = FLT_MAX; empty.hi[k] = -FLT_MAX; }
+    slotBox[s] = empty;
+    return;
+  }
   const uint32_t          t  = uint32_t(__float_as_int(tris[s].b.w));
   const MiGltfRenderNode& rn = nodes[rnode];
   const DevPrim&          rp = prims[rn.renderPrimID];
@@ -172,6 +196,11 @@ PT_DEV void refitTriSlot(const MiGltfRenderNode* nodes, const DevPrim* prims, co
 // k_refit_level, one node: takes the union of each child's boxes -- leaf children from the slot boxes at triBase, inner children from the
 // node boxes at childBase --, requantises the node (slot assignment, childBase, triBase, valid and imask stay) and returns its box in `own`
 // and its SAH term: area(node) + C_TRI x the summed area x triangles of its leaf children.
+// Emptiness (refitBoxEmpty): an empty slot box drops out of its leaf child's union by itself; a child whose box is empty -- every triangle
+// of a leaf child hidden, or an inner child with nothing visible below it -- is left out of `used` and so gets the inverted bytes 255 / 0 of
+// an empty slot, which every walk's slab test misses, while valid, imask, childBase and triBase stay (the tree keeps its topology); it adds
+// 0 to the SAH term.  A node with no child left reports an empty box upwards and keeps its p: the walks compute (p - org) * idir from it,
+// so p is never +-FLT_MAX or non-finite.
 PT_DEV float refitNode8(Node8& N, const RefitBox* slotBox, const RefitBox* nodeBox, RefitBox& own)
 {
   float    clo[3][8], chi[3][8], lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}, leafTerm = 0.0f;
@@ -194,20 +223,26 @@ PT_DEV float refitNode8(Node8& N, const RefitBox* slotBox, const RefitBox* nodeB
         for(int a = 0; a < 3; ++a) { b.lo[a] = fminf(b.lo[a], c.lo[a]); b.hi[a] = fmaxf(b.hi[a], c.hi[a]); }
       }
       tri += count;
-      leafTerm = __fmaf_rn(refitBoxArea(b.lo, b.hi), float(count), leafTerm);
+      leafTerm = __fmaf_rn(refitBoxAreaOrZero(b.lo, b.hi), float(count), leafTerm);
     }
     else
       for(int a = 0; a < 3; ++a) { b.lo[a] = 0.0f; b.hi[a] = 0.0f; }
     for(int a = 0; a < 3; ++a) { clo[a][sl] = b.lo[a]; chi[a][sl] = b.hi[a]; }
-    if(inner || v)
+    if((inner || v) && !refitBoxEmpty(b.lo, b.hi))
     {
       used |= 1u << sl;
       for(int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], b.lo[a]); hi[a] = fmaxf(hi[a], b.hi[a]); }
     }
   }
-  quantiseNode8(N, lo, hi, clo, chi, used);
+  if(used)
+    quantiseNode8(N, lo, hi, clo, chi, used);
+  else
+  {
+    const float keep[3] = {N.p[0], N.p[1], N.p[2]};  // (a frame of no extent at the previous origin: every slot inverted)
+    quantiseNode8(N, keep, keep, clo, chi, 0u);
+  }
   for(int a = 0; a < 3; ++a) { own.lo[a] = lo[a]; own.hi[a] = hi[a]; }
-  return __fmaf_rn(float(MI_PT_DP_C_TRI), leafTerm, refitBoxArea(lo, hi));
+  return __fmaf_rn(float(MI_PT_DP_C_TRI), leafTerm, refitBoxAreaOrZero(lo, hi));
 }
 
 }  // namespace pt

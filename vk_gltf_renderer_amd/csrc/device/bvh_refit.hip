@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) k_sah_final(uint32_t numPartials, const R
   if(threadIdx.x == 0)
   {
     const RefitBox root = nodeBox[0];
-    const float    area = refitBoxArea(root.lo, root.hi);
+    const float    area = refitBoxAreaOrZero(root.lo, root.hi);  // (resident mode: every render node hidden)
     partial[REFIT_SAH_PARTIALS] = area > 0.0f ? sum[0] / double(area) : 0.0;
   }
 }

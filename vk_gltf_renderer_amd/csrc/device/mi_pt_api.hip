@@ -247,6 +247,11 @@ struct MiPt
   std::vector<MiGltfRenderNode> builtNodes;       // the node table of the last full build
   std::vector<uint8_t>          primDirty;        // per render primitive: deformed since the last acceleration update ...
   std::vector<uint8_t>          primDeformed;     // ... since the last full build
+  // resident mode (mi_pt_set_accel_resident): the tree holds the hidden render nodes too, so that visibility is a refit and a material id a patch
+  bool                          accelResident = false;  // as requested
+  bool                          residentTree  = false;  // the resident structure was built over every render node that owns triangles
+  uint64_t                      hiddenTris = 0;         // triangles of the hidden render nodes in it
+  uint64_t                      visibilityRefits = 0, materialPatches = 0;
   // frame state
   int                     width = 0, height = 0;
   int                     tileRank = 0, tileWorld = 1, tileSize = 64;
@@ -697,9 +702,27 @@ int readSahCost(MiPt* pt, double& cost)
   return MI_PT_OK;
 }
 
+// Resident mode is wanted of a build when it is enabled and the build can keep refit data (residentInForce: it then did)
+bool residentWanted(const MiPt* pt)
+{
+  return pt->accelResident && pt->accelMode != MI_PT_ACCEL_REBUILD && (pt->bvhBuilder & 1) == 0 && !pt->sw.hostCollapse;
+}
+bool residentInForce(const MiPt* pt)
+{
+  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refitLevels.empty() && pt->bvh8Nodes && pt->wide;
+}
+int buildAccelerationOver(MiPt* pt, bool resident);
 int buildAccelerationUnguarded(MiPt* pt)
 {
+  return buildAccelerationOver(pt, residentWanted(pt));
+}
+// `resident`: over every render node that owns triangles, as if all were visible; the hidden ones are then hidden by one refit pass
+int buildAccelerationOver(MiPt* pt, bool resident)
+{
   releaseRefitData(pt);
+  pt->residentTree = false;
+  pt->hiddenTris   = 0;
+  uint64_t  hiddenTris = 0;
   const int numNodes = int(pt->hostNodes.size()), numPrims = int(pt->primTriangles.size());
   std::vector<uint8_t>  flags = instanceFlags(pt);
   std::vector<uint32_t> triOffset;
@@ -709,10 +732,13 @@ int buildAccelerationUnguarded(MiPt* pt)
   for(int n = 0; n < numNodes; ++n)
   {
     const MiGltfRenderNode& rn = pt->hostNodes[size_t(n)];
-    if(!pt->hostVisible.empty() && !pt->hostVisible[size_t(n)])
+    const bool hidden = !pt->hostVisible.empty() && !pt->hostVisible[size_t(n)];
+    if(hidden && !resident)
       continue;  // invisible nodes get no geometry (reference: src/gltf_scene_rtx.cpp:319-323)
     if(rn.renderPrimID < 0 || rn.renderPrimID >= numPrims || pt->primTriangles[size_t(rn.renderPrimID)] == 0)
       continue;
+    if(hidden)
+      hiddenTris += pt->primTriangles[size_t(rn.renderPrimID)];
     totalTris += pt->primTriangles[size_t(rn.renderPrimID)];
     if(totalTris > 0x7fffffffull)
       return fail(MI_PT_ERR_ARGUMENT, "more than 2^31 flattened triangles");
@@ -820,6 +846,8 @@ int buildAccelerationUnguarded(MiPt* pt)
         pt->builtNodes  = pt->hostNodes;
         pt->primDirty.assign(pt->primTriangles.size(), 0);
         pt->primDeformed.assign(pt->primTriangles.size(), 0);
+        pt->residentTree = resident;
+        pt->hiddenTris   = resident ? hiddenTris : 0;
       }
       else
       {
@@ -827,6 +855,11 @@ int buildAccelerationUnguarded(MiPt* pt)
         pt->refitNodeBox.release();
       }
     }
+  }
+  if(resident && !pt->residentTree && hiddenTris > 0)  // no refit data came of it (a one-reference scene: bvh8.hip), so nothing could hide them
+  {
+    --pt->accelBuilds;
+    return buildAccelerationOver(pt, false);
   }
   pt::DevScene& S = pt->scene;
   S.bvhNodes = pt->bvhNodes; S.bvh8Nodes = pt->bvh8Nodes; S.tris = pt->bvhTris;
@@ -849,6 +882,24 @@ int buildAccelerationUnguarded(MiPt* pt)
     HIP_TRY(hipDeviceSynchronize());
     S.alphaTris = pt->alphaTris.ptr;
   }
+  if(pt->residentTree && pt->hiddenTris > 0)
+  {
+    // the hide pass: the records above were made from the all-visible tree (they hold no geometry); sahAtBuild stays the all-visible cost
+    std::vector<uint8_t> dirty(std::max<size_t>(pt->hostNodes.size(), 1), pt::REFIT_CLEAN);
+    for(size_t n = 0; n < pt->hostNodes.size(); ++n)
+      if(!pt->hostVisible[n])
+        dirty[n] = pt::REFIT_HIDDEN;
+    HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris, pt->refitSlotBox.ptr,
+                        uint32_t(S.numTris), nullptr);
+    pt::launchRefitLevels(pt->bvh8Nodes, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+    if(pt->bvh8Planes.ptr)
+      pt::launchBvh8Planes(pt->bvh8Nodes, uint32_t(S.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    if(int rc = readSahCost(pt, pt->sahNow))
+      return rc;
+    HIP_TRY(hipDeviceSynchronize());
+  }
   pt->sceneDevDirty = true;
   return MI_PT_OK;
 }
@@ -858,18 +909,38 @@ int buildAccelerationUnguarded(MiPt* pt)
 // primitive deformed since that build: deformed vertices are not compared with the built ones, so its pre-split references keep their
 // whole triangles' boxes until the next build, conservative and the same image), every node
 // level by level, the packet walk's planes, the SAH cost.  AUTO rebuilds when that cost exceeds the ratio x the cost at the last build.
-int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved)
+// `visWas`, resident mode only (else NULL): per render node, whether it was visible before this update.  A node that became hidden is
+// REFIT_HIDDEN, one that stays hidden is clean whatever its matrices do, one that came back is HOME or MOVED by the same comparison.
+int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::vector<uint8_t>* visWas = nullptr)
 {
   static const bool    buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
   const auto           t0          = std::chrono::steady_clock::now();
   const size_t         numNodes = pt->hostNodes.size(), numPrims = pt->primTriangles.size();
   std::vector<uint8_t> dirty(std::max<size_t>(numNodes, 1), pt::REFIT_CLEAN);
+  std::vector<uint8_t> visKept;
+  if(!visWas && pt->residentTree && !pt->hostVisible.empty())  // (a deformation update: what is hidden in the resident tree stays hidden)
+  {
+    visKept = pt->hostVisible;
+    visWas  = &visKept;
+  }
   uint64_t             movedTris = 0;
   for(size_t n = 0; n < numNodes; ++n)
   {
     const MiGltfRenderNode& rn       = pt->hostNodes[n];
     const bool              ownsPrim = rn.renderPrimID >= 0 && size_t(rn.renderPrimID) < numPrims;
-    if(!moved[n] && !(ownsPrim && pt->primDirty[size_t(rn.renderPrimID)]))
+    bool                    shown    = false;
+    if(visWas)
+    {
+      const bool visNow = pt->hostVisible.empty() || pt->hostVisible[n];
+      if(!visNow)
+      {
+        if((*visWas)[n])
+          dirty[n] = pt::REFIT_HIDDEN;
+        continue;
+      }
+      shown = !(*visWas)[n];
+    }
+    if(!shown && !moved[n] && !(ownsPrim && pt->primDirty[size_t(rn.renderPrimID)]))
       continue;
     const bool home = memcmp(rn.objectToWorld, pt->builtNodes[n].objectToWorld, sizeof(float) * 32) == 0 && !(ownsPrim && pt->primDeformed[size_t(rn.renderPrimID)]);
     dirty[n]        = home ? pt::REFIT_HOME : pt::REFIT_MOVED;
@@ -903,6 +974,16 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved)
     fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "refit", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   if(pt->accelMode == MI_PT_ACCEL_AUTO && pt->sahNow > double(pt->accelRatio) * pt->sahAtBuild)
     return buildAcceleration(pt);
+  if(visWas)
+  {
+    pt->hiddenTris = 0;
+    for(size_t n = 0; n < numNodes; ++n)
+    {
+      const int prim = pt->hostNodes[n].renderPrimID;
+      if(!pt->hostVisible.empty() && !pt->hostVisible[n] && prim >= 0 && size_t(prim) < numPrims)
+        pt->hiddenTris += pt->primTriangles[size_t(prim)];
+    }
+  }
   ++pt->accelRefits;
   pt->lastUpdate     = MI_PT_ACCEL_LAST_REFIT;
   pt->trianglesMoved = movedTris;
@@ -916,6 +997,33 @@ int updateAcceleration(MiPt* pt, bool sameTopology, const std::vector<uint8_t>& 
   if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refitLevels.empty() && pt->bvh8Nodes && pt->wide)
     return refitAcceleration(pt, moved);
   return buildAcceleration(pt);
+}
+
+// What makeAlphaRecord (pt_shading.h) reads of a material and its base / diffuse texture info, as it reads it: two materials with equal
+// keys give equal alpha records for the same triangle.  (An OPAQUE material's record is the default one whatever else it holds.)
+struct AlphaKey
+{
+  int32_t  alphaMode = MI_ALPHA_OPAQUE;
+  float    cutoff = 0.0f, factorAlpha = 0.0f;
+  uint32_t slot = 0;
+  int32_t  index = 0, texCoord = 0;
+};
+AlphaKey alphaKey(const MiGltfShadeMaterial& mat, const MiGltfTextureInfo* infos)
+{
+  AlphaKey k;
+  if(mat.alphaMode == MI_ALPHA_OPAQUE)
+    return k;
+  const bool sg = mat.pbrModel == MI_PBR_SPECULAR_GLOSSINESS;
+  k.alphaMode   = mat.alphaMode;
+  k.cutoff      = mat.alphaCutoff;
+  k.factorAlpha = sg ? mat.pbrDiffuseFactor[3] : mat.pbrBaseColorFactor[3];
+  k.slot        = sg ? mat.pbrDiffuseTexture : mat.pbrBaseColorTexture;
+  if(k.slot > 0)
+  {
+    k.index    = infos[k.slot].index;
+    k.texCoord = infos[k.slot].texCoord;
+  }
+  return k;
 }
 
 uint64_t refitBytes(const MiPt* pt)
@@ -1010,6 +1118,145 @@ void deriveTextureRecords(const MiPt* pt, const MiGltfShadeMaterial* materials, 
                 | (uint32_t(r.numLevels) << pt::CT_LEVELS_SHIFT);
     }
   }
+}
+
+// The scene-wide material summaries (instanceFlags sets them) select kernels and optional buffers: what an update that changed them -- the
+// material tables (mi_pt_update_materials) or the render nodes' material ids (resident mode) -- owes the next render.  `hadTransmissive`,
+// `wasSimple`: the summaries before the update.
+int followSummaries(MiPt* pt, bool hadTransmissive, bool wasSimple)
+{
+  if(pt->simpleMaterials != wasSimple)  // the medium array comes back zeroed, on demand, when the generic shade kernel needs it (ensureOptionalPathArrays)
+  {
+    pt->optMedium.release();
+    pt->paths.medium = nullptr;
+  }
+  if(pt->hasTransmissive != hadTransmissive)  // the candidate pool and lists are part of the path resources
+  {
+    pt->candPool.release();
+    pt->candLists.release();
+    if(pt->width > 0)
+      return allocPathResources(pt, pt->framesCap);
+  }
+  return MI_PT_OK;
+}
+
+// The per-triangle data a build bakes of the materials, brought in place to what a build over the current tables writes: the instance flags
+// `flags` (instanceFlags(pt), which also set pt->hasAlpha), the alpha-record buffer appearing or going with pt->hasAlpha, and one launch of
+// k_patch_materials over the slots of the render nodes whose byte in `dirty` (pt::MATERIAL_PATCH_*, as wanted) is set -- none when no byte is.
+// The alpha bit is dropped where there are no records to patch: none needed, or all of them made below as a build makes them.
+int patchTriangleData(MiPt* pt, const std::vector<uint8_t>& flags, std::vector<uint8_t>& dirty)
+{
+  HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
+  pt::DevScene& S          = pt->scene;
+  const bool    hadRecords = pt->alphaTris.ptr != nullptr;
+  if(!pt->hasAlpha)
+  {
+    pt->alphaTris.release();
+    S.alphaTris = nullptr;
+  }
+  else if(!hadRecords)
+    HIP_TRY(pt->alphaTris.alloc(size_t(S.numTris)));
+  bool anyDirty = false;
+  for(uint8_t& d : dirty)
+  {
+    if(!(pt->hasAlpha && hadRecords))
+      d &= uint8_t(~pt::MATERIAL_PATCH_ALPHA);
+    anyDirty |= d != 0;
+  }
+  if(anyDirty)
+  {
+    if(pt->matDirty.count != dirty.size())
+      HIP_TRY(pt->matDirty.alloc(dirty.size()));
+    HIP_TRY(hipMemcpy(pt->matDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+    pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris, hadRecords ? pt->alphaTris.ptr : nullptr, pt->shadeTris.ptr,
+                             uint32_t(S.numTris), nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  if(pt->hasAlpha && !hadRecords)  // the scene had no alpha records: all of them, as a build makes them
+  {
+    pt::launchBuildAlphaRecords(S, uint32_t(S.numTris), pt->alphaTris.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    S.alphaTris = pt->alphaTris.ptr;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  pt->sceneDevDirty = true;
+  return MI_PT_OK;
+}
+
+// mi_pt_update_render_nodes in resident mode: matrices, visibility and material ids in one k_refit_tris pass, one level sweep and at most one
+// patch launch; a build only for what the resident tree cannot take (a renderPrimID change, a transmissive bit under pre-split references,
+// AUTO's cost bound).  The caller checked the arguments.
+int updateRenderNodesResident(MiPt* pt, const MiGltfRenderNode* renderNodes, int numRenderNodes, const uint8_t* renderNodeVisible)
+{
+  const int            numMaterials = int(pt->matInstFlags.size()), numPrims = int(pt->hostPrims.size());
+  const size_t         nn = size_t(numRenderNodes);
+  std::vector<uint8_t> moved(nn, 0), visWas(nn, 1), matDirty(std::max<size_t>(nn, 1), 0);
+  bool                 primChanged = false, visChanged = false, matChanged = false, anyMoved = false, transmissiveChanged = false;
+  auto                 materialOf = [&](const MiGltfRenderNode& rn) { return size_t(std::max(0, std::min(rn.materialID, numMaterials - 1))); };
+  for(size_t n = 0; n < nn; ++n)
+  {
+    const MiGltfRenderNode &was = pt->hostNodes[n], &now = renderNodes[n];
+    visWas[n]         = pt->hostVisible.empty() || pt->hostVisible[n];
+    const bool visNow = !renderNodeVisible || renderNodeVisible[n];
+    visChanged |= (visWas[n] != 0) != visNow;
+    primChanged |= was.renderPrimID != now.renderPrimID;
+    moved[n] = memcmp(was.objectToWorld, now.objectToWorld, sizeof(float) * 32) != 0;
+    anyMoved |= moved[n] != 0;
+    if(was.materialID == now.materialID)
+      continue;
+    matChanged           = true;
+    const size_t   mWas  = materialOf(was), mNow = materialOf(now);
+    const AlphaKey kWas  = alphaKey(pt->hostMaterials[mWas], pt->hostTexInfos.data()), kNow = alphaKey(pt->hostMaterials[mNow], pt->hostTexInfos.data());
+    const bool     alpha = memcmp(&kWas, &kNow, sizeof(AlphaKey)) != 0;
+    const int      prim  = now.renderPrimID;
+    // the OPAQUE class of the load-time alpha cut was found under the old alpha state (as in mi_pt_update_materials)
+    if(alpha && prim >= 0 && prim < numPrims && pt->hostPrims[size_t(prim)].opaqueTriangles > 0)
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_render_nodes: material with another alpha state for geometry that was cut at load: re-cut and re-create (render node "
+                                          + std::to_string(n) + ", material " + std::to_string(mNow) + ")");
+    if(((pt->matInstFlags[mWas] ^ pt->matInstFlags[mNow]) & pt::INST_TRANSMISSIVE) != 0)
+      transmissiveChanged = true;
+    matDirty[n] = uint8_t(pt::MATERIAL_PATCH_SHADE | (alpha ? pt::MATERIAL_PATCH_ALPHA : 0));
+  }
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still walk the old structure
+  const bool                 hadTransmissive = pt->hasTransmissive, wasSimple = pt->simpleMaterials;
+  const std::vector<uint8_t> flagsWas = matChanged ? instanceFlags(pt) : std::vector<uint8_t>();
+  pt->hostNodes.assign(renderNodes, renderNodes + numRenderNodes);
+  if(renderNodeVisible)
+    pt->hostVisible.assign(renderNodeVisible, renderNodeVisible + numRenderNodes);
+  else
+    pt->hostVisible.clear();
+  if(primChanged || (transmissiveChanged && pt->splitRefs))
+  {
+    if(int rc = buildAcceleration(pt))
+      return rc;
+    return followSummaries(pt, hadTransmissive, wasSimple);
+  }
+  bool anyPrimDirty = false;
+  for(uint8_t d : pt->primDirty)
+    anyPrimDirty |= d != 0;
+  if(visChanged || anyMoved || anyPrimDirty || !matChanged)  // (an update that changes nothing refits, as it does outside resident mode)
+  {
+    if(int rc = refitAcceleration(pt, moved, &visWas))
+      return rc;
+    if(pt->lastUpdate == MI_PT_ACCEL_LAST_BUILD)  // AUTO's bound: the build baked the materials
+      return followSummaries(pt, hadTransmissive, wasSimple);
+    if(visChanged)
+      ++pt->visibilityRefits;
+  }
+  if(!matChanged)
+    return MI_PT_OK;
+  const std::vector<uint8_t> flags = instanceFlags(pt);
+  for(size_t n = 0; n < nn; ++n)
+    if(matDirty[n] && flags[n] != flagsWas[n])
+      matDirty[n] |= pt::MATERIAL_PATCH_FLAGS;
+  // (the refit uploaded the node table; an update of material ids alone has not)
+  HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * nn, hipMemcpyHostToDevice));
+  if(int rc = patchTriangleData(pt, flags, matDirty))
+    return rc;
+  ++pt->materialPatches;
+  pt->lastUpdate = MI_PT_ACCEL_LAST_REFIT;
+  return followSummaries(pt, hadTransmissive, wasSimple);
 }
 
 }  // namespace
@@ -1287,6 +1534,8 @@ int mi_pt_update_render_nodes(MiPt* pt, const MiGltfRenderNode* renderNodes, int
   for(int n = 0; n < numRenderNodes; ++n)
     if(renderNodes[n].materialID >= int(pt->matInstFlags.size()))
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_render_nodes: render node references a material beyond the table");
+  if(residentInForce(pt))
+    return updateRenderNodesResident(pt, renderNodes, numRenderNodes, renderNodeVisible);
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still walk the old structure
   // what changed: matrices only (a refit may follow), or primitives, materials or visibility (a rebuild)
@@ -1319,33 +1568,6 @@ int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLights)
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still sample the old table
   HIP_TRY(hipMemcpy(pt->lights.ptr, lights, sizeof(MiGltfLight) * size_t(numLights), hipMemcpyHostToDevice));
   return MI_PT_OK;
-}
-
-// What makeAlphaRecord (pt_shading.h) reads of a material and its base / diffuse texture info, as it reads it: two materials with equal
-// keys give equal alpha records for the same triangle.  (An OPAQUE material's record is the default one whatever else it holds.)
-struct AlphaKey
-{
-  int32_t  alphaMode = MI_ALPHA_OPAQUE;
-  float    cutoff = 0.0f, factorAlpha = 0.0f;
-  uint32_t slot = 0;
-  int32_t  index = 0, texCoord = 0;
-};
-static AlphaKey alphaKey(const MiGltfShadeMaterial& mat, const MiGltfTextureInfo* infos)
-{
-  AlphaKey k;
-  if(mat.alphaMode == MI_ALPHA_OPAQUE)
-    return k;
-  const bool sg = mat.pbrModel == MI_PBR_SPECULAR_GLOSSINESS;
-  k.alphaMode   = mat.alphaMode;
-  k.cutoff      = mat.alphaCutoff;
-  k.factorAlpha = sg ? mat.pbrDiffuseFactor[3] : mat.pbrBaseColorFactor[3];
-  k.slot        = sg ? mat.pbrDiffuseTexture : mat.pbrBaseColorTexture;
-  if(k.slot > 0)
-  {
-    k.index    = infos[k.slot].index;
-    k.texCoord = infos[k.slot].texCoord;
-  }
-  return k;
 }
 
 int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int numMaterials, const MiGltfTextureInfo* textureInfos, int numTextureInfos)
@@ -1421,67 +1643,27 @@ int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int n
   // ---- the scene-wide summaries, and the buffers they call for at the next render
   const bool hadTransmissive = pt->hasTransmissive, wasSimple = pt->simpleMaterials;
   const std::vector<uint8_t> flags = instanceFlags(pt);
-  auto followSummaries = [&]() -> int {
-    if(pt->simpleMaterials != wasSimple)  // the medium array comes back zeroed, on demand, when the generic shade kernel needs it (ensureOptionalPathArrays)
-    {
-      pt->optMedium.release();
-      pt->paths.medium = nullptr;
-    }
-    if(pt->hasTransmissive != hadTransmissive)  // the candidate pool and lists are part of the path resources
-    {
-      pt->candPool.release();
-      pt->candLists.release();
-      if(pt->width > 0)
-        return allocPathResources(pt, pt->framesCap);
-    }
-    return MI_PT_OK;
-  };
   // ---- what the resident structure cannot take in place is rebuilt: the BVH2 walk (no patch path), and a transmissive bit that changes
   // while the tree holds pre-split references (triangles of transmissive instances keep ONE reference: bvh_build.hip, k_split_refs)
   if((anyAlpha || anyFlags) && pt->scene.numTris > 0 && (!pt->wide || (transmissiveChanged && pt->splitRefs)))
   {
     if(int rc = buildAcceleration(pt))
       return rc;
-    return followSummaries();
+    return followSummaries(pt, hadTransmissive, wasSimple);
   }
   if(pt->scene.numTris > 0)
   {
-    HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
-    pt::DevScene& S          = pt->scene;
-    const bool    hadRecords = pt->alphaTris.ptr != nullptr;
-    if(!pt->hasAlpha)
-    {
-      pt->alphaTris.release();
-      S.alphaTris = nullptr;
-    }
-    else if(!hadRecords)
-      HIP_TRY(pt->alphaTris.alloc(size_t(S.numTris)));
     // the dirty byte of every render node, from its material's classes; no launch when no byte is set (factor-only and UV-transform updates)
     std::vector<uint8_t> dirty(size_t(std::max(numNodes, 1)), 0);
-    bool                 anyDirty = false;
     for(int n = 0; n < numNodes; ++n)
     {
       const size_t m = materialOf(n);
-      dirty[size_t(n)] = uint8_t((flagsChanged[m] ? pt::MATERIAL_PATCH_FLAGS : 0) | (alphaChanged[m] && pt->hasAlpha && hadRecords ? pt::MATERIAL_PATCH_ALPHA : 0));
-      anyDirty |= dirty[size_t(n)] != 0;
+      dirty[size_t(n)] = uint8_t((flagsChanged[m] ? pt::MATERIAL_PATCH_FLAGS : 0) | (alphaChanged[m] ? pt::MATERIAL_PATCH_ALPHA : 0));
     }
-    if(anyDirty)
-    {
-      if(pt->matDirty.count != dirty.size())
-        HIP_TRY(pt->matDirty.alloc(dirty.size()));
-      HIP_TRY(hipMemcpy(pt->matDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-      pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris, hadRecords ? pt->alphaTris.ptr : nullptr, uint32_t(S.numTris), nullptr);
-      HIP_TRY(hipGetLastError());
-    }
-    if(pt->hasAlpha && !hadRecords)  // the scene had no alpha records: all of them, as a build makes them
-    {
-      pt::launchBuildAlphaRecords(S, uint32_t(S.numTris), pt->alphaTris.ptr, nullptr);
-      HIP_TRY(hipGetLastError());
-      S.alphaTris = pt->alphaTris.ptr;
-    }
-    HIP_TRY(hipDeviceSynchronize());
+    if(int rc = patchTriangleData(pt, flags, dirty))
+      return rc;
   }
-  return followSummaries();
+  return followSummaries(pt, hadTransmissive, wasSimple);
 }
 
 static void releaseDeformation(MiPt* pt)
@@ -1726,6 +1908,39 @@ int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* out)
   out->sahCost          = pt->sahNow;
   out->trianglesMoved   = pt->trianglesMoved;
   out->refitBytes       = refitBytes(pt);
+  return MI_PT_OK;
+}
+
+int mi_pt_set_accel_resident(MiPt* pt, int enable)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_resident: null instance");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still walk the structure
+  pt->accelResident = enable != 0;
+  // the tree the updates then refit: built once, here, when the request comes into force or leaves it (inert under REBUILD, the BVH2 walk
+  // and the host collapse: their updates build anyway)
+  if(residentWanted(pt) == pt->residentTree || pt->accelMode == MI_PT_ACCEL_REBUILD || (pt->bvhBuilder & 1) != 0 || pt->sw.hostCollapse)
+    return MI_PT_OK;
+  pt->switchBuild = true;
+  const int rc    = buildAcceleration(pt);
+  pt->switchBuild = false;
+  return rc;
+}
+
+int mi_pt_get_accel_resident_info(MiPt* pt, MiPtAccelResidentInfo* out)
+{
+  if(!pt || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_accel_resident_info: null argument");
+  memset(out, 0, sizeof(*out));
+  const bool inForce     = residentInForce(pt);
+  out->enabled           = pt->accelResident ? 1 : 0;
+  out->inForce           = inForce ? 1 : 0;
+  out->residentTriangles = inForce ? uint64_t(std::max(pt->scene.numTris, 0)) : 0;
+  out->hiddenTriangles   = inForce ? pt->hiddenTris : 0;
+  out->visibilityRefits  = pt->visibilityRefits;
+  out->materialPatches   = pt->materialPatches;
   return MI_PT_OK;
 }
 

@@ -32,9 +32,10 @@ struct LaunchCtx
 void launchBuildShadeRecords(const DevScene& scene, uint32_t numTris, DevShadeTri* out, hipStream_t s);
 void launchBuildAlphaRecords(const DevScene& scene, uint32_t numTris, DevAlphaTri* out, hipStream_t s);
 // material_update.hip: the flag word of the triangle records and the alpha records of the slots whose render node's byte in `dirty` is set
-// (material_patch.h: MATERIAL_PATCH_*); `tris` is scene.tris, writable; alphaTris may be NULL
-void launchPatchMaterials(const DevScene& scene, const uint8_t* instFlags, const uint8_t* dirty, DevTri* tris, DevAlphaTri* alphaTris, uint32_t numTris,
-                          hipStream_t s);
+// (material_patch.h: MATERIAL_PATCH_*); `tris` is scene.tris, writable; alphaTris may be NULL, and so may shadeTris (the material ids of the shade
+// records: MATERIAL_PATCH_SHADE)
+void launchPatchMaterials(const DevScene& scene, const uint8_t* instFlags, const uint8_t* dirty, DevTri* tris, DevAlphaTri* alphaTris, DevShadeTri* shadeTris,
+                          uint32_t numTris, hipStream_t s);
 void dumpTraceProfile();  // prints the -DTRACE_PROFILE section timers (no-op in the product build)
 void launchBvh8Planes(const uint4* nodes, uint32_t numNodes, float* planes, hipStream_t s);
 void launchTextureQuads(const uchar4* texels, uint4* quads, uint32_t offset, int width, int height, int wrapS, int wrapT, hipStream_t s);

@@ -742,6 +742,11 @@ PT_DEV float getOpacityFast(const DevScene& sc, int triIndex, f3 bary)
     return alpha >= rec.b.w ? 1.0f : 0.0f;
   return alpha;
 }
+// The material id a shade record carries for its render node (one text for the build and the material patch, material_patch.h)
+PT_DEV int32_t shadeRecordMaterial(const MiGltfRenderNode& rn)
+{
+  return max(0, rn.materialID);
+}
 PT_DEV DevShadeTri makeShadeRecord(const DevScene& sc, const DevTri& T)
 {
   DevShadeTri             r;
@@ -753,7 +758,7 @@ PT_DEV DevShadeTri makeShadeRecord(const DevScene& sc, const DevTri& T)
   r.v0 = base + 3u * ti.x; r.v1 = base + 3u * ti.y; r.v2 = base + 3u * ti.z;
   r.rnode        = rnode;
   r.renderPrimID = rn.renderPrimID;
-  r.materialID   = max(0, rn.materialID);
+  r.materialID   = shadeRecordMaterial(rn);
   r.prim         = prim;
   r.attrs        = (rp.normals ? SHADE_HAS_NORMALS : 0u) | (rp.texCoords0 ? SHADE_HAS_UV0 : 0u) | (rp.tangents ? SHADE_HAS_TANGENTS : 0u)
             | (rp.texCoords1 ? SHADE_HAS_UV1 : 0u) | (rp.colors ? SHADE_HAS_COLORS : 0u);

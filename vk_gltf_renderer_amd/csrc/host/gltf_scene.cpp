@@ -1316,24 +1316,8 @@ void GltfScene::traverse(int nodeID, const mx::mat4& parent, bool parentVisible,
       if(it == primMap.end())
         continue;
       int rprimID = it->second;
-      // material: KHR_materials_variants mapping for variant 0, else max(0, material)
-      // (reference: src/gltf_scene.cpp:2749-2769)
-      int          materialID = std::max(0, getInt(prim, "material", -1));
-      const Value& variants   = ext(prim, "KHR_materials_variants");
-      if(variants.isObject())
-      {
-        const Value& mappings = variants["mappings"];
-        bool         found    = false;
-        for(size_t m = 0; m < mappings.size() && !found; ++m)
-          for(size_t v = 0; v < mappings[m]["variants"].size(); ++v)
-            if(mappings[m]["variants"][v].integer(-1) == 0)
-            {
-              materialID = mappings[m]["material"].integer(0);
-              found      = true;
-              break;
-            }
-      }
-      materialID = std::min(materialID, int(m_materials.size()) - 1);
+      // material: KHR_materials_variants mapping for variant 0 (setVariant switches later), else max(0, material)
+      const int materialID = variantMaterial(prim, 0);
       auto addNode = [&](const mx::mat4& w, int instance) {
         MiGltfRenderNode rn{};
         memcpy(rn.objectToWorld, w.m, sizeof(rn.objectToWorld));
@@ -1344,6 +1328,7 @@ void GltfScene::traverse(int nodeID, const mx::mat4& parent, bool parentVisible,
         m_renderNodes.push_back(rn);
         m_renderNodeVisible.push_back(visible ? 1 : 0);
         m_renderNodeSource.push_back({nodeID, instance, m_curPath});
+        m_renderNodePrimitive.push_back({meshID, int(p)});
         m_numTriangles += m_primData[size_t(rprimID)].indices.size() / 3;
       };
       if(instances)
@@ -1359,6 +1344,106 @@ void GltfScene::traverse(int nodeID, const mx::mat4& parent, bool parentVisible,
     traverse(children[c].integer(-1), world, visible, primMap);
   m_onPath[size_t(nodeID)] = 0;
   m_curPath.pop_back();
+}
+
+// The material of a primitive under variant `variant` of KHR_materials_variants (reference: getMaterialVariantIndex,
+// src/gltf_scene.cpp:2749-2769): the first mapping whose `variants` list holds it, else max(0, primitive.material); never beyond the table.
+int GltfScene::variantMaterial(const Value& prim, int variant) const
+{
+  int          materialID = std::max(0, getInt(prim, "material", -1));
+  const Value& variants   = ext(prim, "KHR_materials_variants");
+  if(variants.isObject())
+  {
+    const Value& mappings = variants["mappings"];
+    bool         found    = false;
+    for(size_t m = 0; m < mappings.size() && !found; ++m)
+      for(size_t v = 0; v < mappings[m]["variants"].size(); ++v)
+        if(mappings[m]["variants"][v].integer(-1) == variant)
+        {
+          materialID = mappings[m]["material"].integer(0);
+          found      = true;
+          break;
+        }
+  }
+  return std::min(materialID, int(m_materials.size()) - 1);
+}
+
+int GltfScene::numVariants() const
+{
+  return int(ext(m_doc, "KHR_materials_variants")["variants"].size());
+}
+std::string GltfScene::variantName(int index) const
+{
+  return ext(m_doc, "KHR_materials_variants")["variants"][size_t(index)]["name"].string("");
+}
+
+namespace {
+// What the alpha test reads of a material (the alpha key of mi_pt_update_materials: alphaMode, cutoff, the base / diffuse alpha factor, and the
+// image and TEXCOORD set of the base / diffuse texture).  An OPAQUE material's state is the default whatever else it holds.
+struct AlphaState
+{
+  int32_t  alphaMode = MI_ALPHA_OPAQUE;
+  float    cutoff = 0.0f, factorAlpha = 0.0f;
+  uint32_t slot = 0;
+  int32_t  index = 0, texCoord = 0;
+  bool operator==(const AlphaState& o) const
+  {
+    return alphaMode == o.alphaMode && cutoff == o.cutoff && factorAlpha == o.factorAlpha && slot == o.slot && index == o.index && texCoord == o.texCoord;
+  }
+};
+AlphaState alphaState(const MiGltfShadeMaterial& mat, const std::vector<MiGltfTextureInfo>& infos)
+{
+  AlphaState k;
+  if(mat.alphaMode == MI_ALPHA_OPAQUE)
+    return k;
+  const bool sg = mat.pbrModel == MI_PBR_SPECULAR_GLOSSINESS;
+  k.alphaMode   = mat.alphaMode;
+  k.cutoff      = mat.alphaCutoff;
+  k.factorAlpha = sg ? mat.pbrDiffuseFactor[3] : mat.pbrBaseColorFactor[3];
+  k.slot        = sg ? mat.pbrDiffuseTexture : mat.pbrBaseColorTexture;
+  if(k.slot > 0 && k.slot < infos.size())
+  {
+    k.index    = infos[k.slot].index;
+    k.texCoord = infos[k.slot].texCoord;
+  }
+  return k;
+}
+}  // namespace
+
+// Rewrites the materialID of every render node in place (same table, same count) and returns how many changed; -1 with error() set and
+// nothing changed for a variant out of range, or when a primitive the alpha cut classified (opaqueTriangles > 0) would get a material
+// with another alpha state: the cut is applied once per loaded scene, under the alpha state it found.
+int GltfScene::setVariant(int variant)
+{
+  if(variant < 0 || variant >= numVariants())
+  {
+    m_error = "no such material variant: " + std::to_string(variant) + " of " + std::to_string(numVariants());
+    return -1;
+  }
+  std::vector<int> ids(m_renderNodes.size());
+  for(size_t n = 0; n < m_renderNodes.size(); ++n)
+  {
+    const MiGltfRenderNode& rn = m_renderNodes[n];
+    const auto&             mp = m_renderNodePrimitive[n];
+    ids[n]                     = variantMaterial(m_doc["meshes"][size_t(mp.first)]["primitives"][size_t(mp.second)], variant);
+    if(ids[n] == rn.materialID || rn.renderPrimID < 0 || size_t(rn.renderPrimID) >= m_primData.size() || m_primData[size_t(rn.renderPrimID)].opaqueTriangles == 0)
+      continue;
+    const size_t was = size_t(std::max(0, rn.materialID)), now = size_t(std::max(0, ids[n]));
+    if(was < m_materials.size() && now < m_materials.size() && !(alphaState(m_materials[was], m_textureInfos) == alphaState(m_materials[now], m_textureInfos)))
+    {
+      m_error = "material variant " + std::to_string(variant) + " changes the alpha state of geometry the alpha cut classified (render node " + std::to_string(n)
+                + "): load the scene again, switch, then cut";
+      return -1;
+    }
+  }
+  int changed = 0;
+  for(size_t n = 0; n < m_renderNodes.size(); ++n)
+  {
+    changed += ids[n] != m_renderNodes[n].materialID;
+    m_renderNodes[n].materialID = ids[n];
+  }
+  m_currentVariant = variant;
+  return changed;
 }
 
 mx::mat4 GltfScene::localMatrix(int nodeID) const
@@ -1497,6 +1582,8 @@ bool GltfScene::parse(const std::string& baseDir)  // reference: src/gltf_scene.
   m_cameras.clear();
   m_gpuInstanceLocalMatrices.clear();
   m_renderNodeSource.clear();
+  m_renderNodePrimitive.clear();
+  m_currentVariant = 0;
   m_lightNode.clear();
   m_lightIndex.clear();
   m_cameraIndex.clear();

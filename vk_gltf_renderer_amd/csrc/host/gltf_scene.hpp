@@ -6,7 +6,7 @@
 // Keyframe animation of node transforms (gltf_scene_animation.cpp here; reference: src/gltf_scene_animation.cpp:355-700) feeds
 // mi_pt_update_render_nodes / mi_pt_update_lights; skins and morph targets (same file; reference: src/gltf_scene_animation.cpp:196-320)
 // feed mi_pt_update_deformation; KHR_animation_pointer channels (same file; reference: src/gltf_animation_pointer.cpp) rewrite the material, light,
-// camera and visibility tables and feed mi_pt_update_materials.  Editing, saving, merging and the variants UI are out of scope.
+// camera and visibility tables and feed mi_pt_update_materials.  KHR_materials_variants are switched at run time (setVariant).  Editing, saving and merging are out of scope.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -94,6 +94,14 @@ public:
   const MiPtDeformDesc* deformation() const { return m_deform.empty() ? nullptr : &m_deformDesc; }
   int                   deformOnHost();
   const std::vector<uint8_t>& renderNodeVisible() const { return m_renderNodeVisible; }
+  // KHR_materials_variants at run time (reference: Scene::setCurrentVariant, src/gltf_scene.cpp:2038-2072).  The load resolves variant 0;
+  // setVariant rewrites the materialID of renderNodes() IN PLACE (every render node made from a primitive, EXT_mesh_gpu_instancing instances
+  // included) and returns the number of render nodes whose material changed, or -1 (error() set, nothing changed): no such variant, or the
+  // switch would give geometry the alpha cut classified a material with another alpha state.
+  int         numVariants() const;
+  std::string variantName(int index) const;
+  int         currentVariant() const { return m_currentVariant; }
+  int         setVariant(int variant);
   // Load-time bake for alpha-MASK geometry (alpha_cut.cpp; the counterpart of the reference's opacity micro-map bake,
   // src/gltf_scene_omm.cpp): triangles are cut into subdivisions x subdivisions sub-triangles and those on which the alpha test
   // cannot pass are dropped.  Returns the number of (sub-)triangles dropped; desc() is rebuilt (its pointers change).
@@ -122,6 +130,7 @@ private:
   void     lightProperties(const mijson::Value& light, MiGltfLight& info) const;
   void     cameraIntrinsics(const mijson::Value& camera, RenderCamera& cam) const;
   mx::mat4 localMatrix(int nodeID) const;
+  int      variantMaterial(const mijson::Value& prim, int variant) const;
   void     parseAnimations();
   void     parseDeformation();
   void     finalizeDeformation();  // (re)takes the base copies from the streams and rebuilds m_deformDesc
@@ -168,6 +177,8 @@ private:
   std::vector<Animation>        m_animations;
   std::vector<NodePose>         m_nodePose;
   std::vector<RenderNodeSource> m_renderNodeSource;
+  std::vector<std::pair<int, int>> m_renderNodePrimitive;  // per render node: the glTF mesh and the index of the primitive in it (setVariant)
+  int                           m_currentVariant = 0;
   std::vector<int>              m_lightNode, m_roots;
   std::vector<int>              m_lightIndex, m_cameraIndex;  // per light / camera of the tables: its index in the document (-1: the default camera)
   std::vector<uint32_t>         m_materialFirstInfo;          // per material (+ the end): its first texture info; they are contiguous

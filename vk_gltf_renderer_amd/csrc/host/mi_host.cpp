@@ -92,6 +92,43 @@ int64_t mi_scene_cut_alpha(MiScene* scene, int subdivisions)
     return MI_PT_ERR_IO;
   }
 }
+int mi_scene_num_variants(const MiScene* scene)
+{
+  return scene ? scene->scene.numVariants() : 0;
+}
+int mi_scene_variant_name(const MiScene* scene, int index, char* name, int nameCapacity)
+{
+  if(!scene || index < 0 || index >= scene->scene.numVariants())
+  {
+    g_hostError = "mi_scene_variant_name: no such variant";
+    return MI_PT_ERR_ARGUMENT;
+  }
+  if(name && nameCapacity > 0)
+  {
+    strncpy(name, scene->scene.variantName(index).c_str(), size_t(nameCapacity) - 1);
+    name[nameCapacity - 1] = 0;
+  }
+  return MI_PT_OK;
+}
+int mi_scene_current_variant(const MiScene* scene)
+{
+  return scene ? scene->scene.currentVariant() : 0;
+}
+int mi_scene_set_variant(MiScene* scene, int variant)
+{
+  if(!scene)
+  {
+    g_hostError = "mi_scene_set_variant: null scene";
+    return MI_PT_ERR_ARGUMENT;
+  }
+  const int changed = scene->scene.setVariant(variant);
+  if(changed < 0)
+  {
+    g_hostError = "mi_scene_set_variant: " + scene->scene.error();
+    return MI_PT_ERR_ARGUMENT;
+  }
+  return changed;
+}
 int mi_scene_num_animations(const MiScene* scene)
 {
   return scene ? const_cast<MiScene*>(scene)->scene.numAnimations() : 0;

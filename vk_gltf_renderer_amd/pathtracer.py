@@ -69,6 +69,29 @@ class Scene:
         return int(n)
 
     @property
+    def variants(self):
+        """The names of the KHR_materials_variants of the file, in order ([] without the extension)."""
+        out = []
+        for i in range(int(self._h.mi_scene_num_variants(self._p))):
+            name = C.create_string_buffer(256)
+            _check_host(self._h.mi_scene_variant_name(self._p, i, name, 256))
+            out.append(name.value.decode())
+        return out
+
+    @property
+    def current_variant(self):
+        return int(self._h.mi_scene_current_variant(self._p))
+
+    def set_variant(self, variant):
+        """Switches the material variant (mi_scene_set_variant): the material ids of the render-node table of `desc` change in place.  Returns
+        the number of render nodes whose material changed; follow with PathTracer.update_render_nodes (a patch in resident mode, a
+        rebuild otherwise).  Raises MiError, with nothing changed, for a variant out of range or an alpha change on cut geometry."""
+        n = self._h.mi_scene_set_variant(self._p, int(variant))
+        if n < 0:
+            _check_host(n)
+        return int(n)
+
+    @property
     def num_animations(self):
         return int(self._h.mi_scene_num_animations(self._p))
 
@@ -188,7 +211,8 @@ class PathTracer:
         self.temporal = False
 
     def update_render_nodes(self, render_nodes, count, visible=None):
-        """New transforms / materials / visibility for the instances: rebuilds the acceleration structure on the device."""
+        """New transforms / materials / visibility for the instances: rebuilds the acceleration structure on the device (or refits and
+        patches it: set_accel_update, set_accel_resident)."""
         _check_pt(self._l.mi_pt_update_render_nodes(self._p, render_nodes, count, visible))
 
     def update_lights(self, lights, count):
@@ -230,6 +254,17 @@ class PathTracer:
         a = capi.MiPtAccelInfo()
         _check_pt(self._l.mi_pt_get_accel_info(self._p, C.byref(a)))
         return {n: getattr(a, n) for n, _ in a._fields_ if n != "reserved"}
+
+    def set_accel_resident(self, enable=True):
+        """Resident mode (mi_pt_set_accel_resident): with refits allowed (set_accel_update "refit" / "auto"), hidden render nodes stay in
+        the tree, so that a visibility change is a refit and a material-id change a patch instead of a build.  ~130 B per hidden triangle."""
+        _check_pt(self._l.mi_pt_set_accel_resident(self._p, 1 if enable else 0))
+
+    def accel_resident_info(self):
+        """mi_pt_get_accel_resident_info as a dict: enabled, inForce, residentTriangles, hiddenTriangles, visibilityRefits, materialPatches."""
+        a = capi.MiPtAccelResidentInfo()
+        _check_pt(self._l.mi_pt_get_accel_resident_info(self._p, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in a._fields_}
 
     def read_vertices(self, prim):
         """The resident streams of render primitive `prim`: (positions (V, 3), normals (V, 3) or None, tangents (V, 4) or None)."""

@@ -1312,3 +1312,62 @@ def scene_skinned(path, seed=11, tess=12):
 def scene_skinned_large(path, seed=11):
     """scene_skinned with ~1.6 M deformed vertices (the timing variant)."""
     return scene_skinned(path, seed=seed, tess=240)
+
+
+def scene_variants(path, seed=31, tess=12, tex_size=32):
+    """A small stage for KHR_materials_variants: three spheres, a brick under EXT_mesh_gpu_instancing (three instances) and a floor nothing
+    maps.  Variants "base" (0), "cutout" (1), "glass" (2):
+      sphere A  primitive.material plain red; one mapping, cutout -> the alpha-MASK material (a tex_size^2 alpha texture, half of it solid):
+                OPAQUE -> MASK -> OPAQUE over the cycle, and "base" maps nothing for it;
+      sphere B  two mappings, [glass] -> the transmissive material, then [cutout, glass] -> blue metal: the FIRST mapping that holds a
+                variant wins, so glass is transmissive although the second mapping lists it too;
+      sphere C  primitive.material blue metal, one mapping [base] -> red: variant 0 is resolved at load, against primitive.material;
+      brick     one mapping [cutout] -> gold: all three instances switch together.
+    scene_variants.LAYOUT names the material indices."""
+    rng = np.random.default_rng(seed)
+    b = GlbBuilder()
+    L = scene_variants.LAYOUT
+    a = np.clip(value_noise(rng, tex_size, 3, 1)[..., 0] * 1.3, 0, 1)
+    a[:, :tex_size // 2] = 1.0  # (a solid half: the alpha cut finds triangles that cannot fail the test)
+    card = np.concatenate([np.clip(value_noise(rng, tex_size, 3, 3), 0, 1), a[..., None]], -1)
+    card_tex = b.texture(b.image((card * 255 + 0.5).astype(np.uint8)), b.sampler())
+    mats = [None] * 7
+    mats[L["red"]] = lambert_material((0.8, 0.25, 0.2))
+    mats[L["green"]] = lambert_material((0.3, 0.7, 0.35))
+    mats[L["metal"]] = {"pbrMetallicRoughness": {"baseColorFactor": [0.2, 0.3, 0.8, 1], "metallicFactor": 0.7, "roughnessFactor": 0.3}}
+    mats[L["mask"]] = {"pbrMetallicRoughness": {"baseColorTexture": {"index": card_tex}, "metallicFactor": 0.0, "roughnessFactor": 0.8}, "alphaMode": "MASK",
+                       "alphaCutoff": 0.5, "doubleSided": True}
+    mats[L["glass"]] = {"pbrMetallicRoughness": {"baseColorFactor": [0.9, 0.95, 1.0, 1], "metallicFactor": 0.0, "roughnessFactor": 0.05},
+                        "extensions": {"KHR_materials_transmission": {"transmissionFactor": 0.9}, "KHR_materials_ior": {"ior": 1.45}}}
+    mats[L["grey"]] = lambert_material((0.6, 0.6, 0.6))
+    mats[L["gold"]] = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 0.77, 0.34, 1], "metallicFactor": 1.0, "roughnessFactor": 0.25}}
+    for m in mats:
+        b.material(m)
+    b.doc.setdefault("extensions", {})["KHR_materials_variants"] = {"variants": [{"name": "base"}, {"name": "cutout"}, {"name": "glass"}]}
+    b.ext_used.update(("KHR_materials_variants", "EXT_mesh_gpu_instancing"))
+
+    def mapped(prim, mappings):
+        prim["extensions"] = {"KHR_materials_variants": {"mappings": [{"material": m, "variants": list(v)} for m, v in mappings]}}
+        return prim
+    sp, sn, suv, si = uv_sphere(tess * 2, tess, 0.45)
+    bp, bn, _, bi = box((0.5, 0.3, 0.4))
+    fp, fn, _, fi = grid(4, 4, (8, 8))
+    ball_a = b.mesh([mapped(b.primitive(sp, si, sn, suv, material=L["red"]), [(L["mask"], [1])])])
+    ball_b = b.mesh([mapped(b.primitive(sp, si, sn, suv, material=L["green"]), [(L["glass"], [2]), (L["metal"], [1, 2])])])
+    ball_c = b.mesh([mapped(b.primitive(sp, si, sn, suv, material=L["metal"]), [(L["red"], [0])])])
+    brick = b.mesh([mapped(b.primitive(bp, bi, normals=bn, material=L["grey"]), [(L["gold"], [1])])])
+    floor = b.mesh([b.primitive(fp, fi, normals=fn, material=L["grey"])])
+    b.node(mesh=floor, translation=[0, -0.5, 0])
+    b.node(mesh=ball_a, translation=[-1.3, 0.0, 0.2])
+    b.node(mesh=ball_b, translation=[0.0, 0.0, 0.6])
+    b.node(mesh=ball_c, translation=[1.3, 0.0, 0.1], scale=[1.0, 1.2, 1.0])
+    inst_t = b.accessor(np.asarray([[0, 0, 0], [1.1, 0.0, 0.1], [-1.1, 0.1, 0.0]], np.float32))
+    inst_s = b.accessor(np.asarray([[1, 1, 1], [0.6, 0.6, 0.6], [0.8, 0.5, 0.8]], np.float32))
+    b.node(mesh=brick, translation=[0, -0.3, -1.2], extensions={"EXT_mesh_gpu_instancing": {"attributes": {"TRANSLATION": inst_t, "SCALE": inst_s}}})
+    b.light({"type": "point", "intensity": 50.0, "color": [1, 0.95, 0.9], "extras": {"radius": 0.1}})
+    b.node(extensions={"KHR_lights_punctual": {"light": 0}}, translation=[0.5, 3.0, 2.5])
+    b.camera_node((0.0, 1.6, 4.6), (0, 0.0, 0), yfov=0.7)
+    return b.save(path)
+
+
+scene_variants.LAYOUT = {"red": 0, "green": 1, "metal": 2, "mask": 3, "glass": 4, "grey": 5, "gold": 6}
