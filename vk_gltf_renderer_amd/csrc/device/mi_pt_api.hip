@@ -111,6 +111,10 @@ struct RunSwitches
   bool   collapseBad    = false;
   bool   hostCollapse   = false;   // MI_PT_HOST_COLLAPSE    collapse on the host (the greedy reference of the device collapse)
   bool   coreTex        = true;    // MI_PT_CORE_TEX=0: A/B switch -- the per-material slot records (pt_scene.h: DevCoreTex) send every fetch the general way
+  bool   shadowDeposit  = true;    // MI_PT_SHADOW_DEPOSIT=0: A/B switch -- every shadow ray of the opaque / alpha-tested any-hit walks (k_trace_shadow MODE 0 / 1) leaves its
+                                   //                        outcome in its queue entry and k_shadow_resolve adds the terms as a pass of its own, as in rounds 5-6.  Default: the walk
+                                   //                        adds an unoccluded ray's term where the ray ends (three float atomics nobody waits for, pt_scene.h: shadowDepositAdd) and
+                                   //                        the pass runs for catcher probes only.  Same image bit for bit (tests/test_gpu_shadow_deposit.py)
   int    maxItersDiag   = 0;       // MI_PT_DIAG_MAX_ITERS=N test hook: the bounce loop stops after N iterations whatever is still alive (the truncation a
                                    //                        volume-scatter scene meets at maxDepth * 66 + 512)
   int    failBuildAt    = 0;       // MI_PT_DIAG_FAIL_BUILD=N  test hook: the N-th acceleration REbuild of the instance fails after the old structure is gone
@@ -147,6 +151,7 @@ struct RunSwitches
     hostCollapse   = flag("MI_PT_HOST_COLLAPSE");
     maxItersDiag   = num("MI_PT_DIAG_MAX_ITERS", 0);
     coreTex        = num("MI_PT_CORE_TEX", 1) != 0;
+    shadowDeposit  = num("MI_PT_SHADOW_DEPOSIT", 1) != 0;
     failBuildAt    = num("MI_PT_DIAG_FAIL_BUILD", 0);
     if(const char* e = getenv("MI_PT_DIAG_CAND_POOL"))
     {
@@ -2228,6 +2233,7 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   c.simpleMaterials  = pt->simpleMaterials;
   c.wide             = pt->wide;
   c.collectCounters  = pt->collectCounters;
+  c.shadowDeposit    = pt->sw.shadowDeposit;
   {
     // Per-bounce sort of the shade kernel (k_shade): grouping the hits by material pays where the materials take different ways
     // through the BSDF (glass workload: generic shade kernel -11 %); where every material runs the same code (the SIMPLE

@@ -25,6 +25,7 @@ struct LaunchCtx
   bool            simpleMaterials;  // no material needs the transmission / clearcoat / sheen / iridescence / anisotropy paths
   bool            wide;  // traverse the 8-wide compressed BVH (scene.bvh8Nodes) instead of the BVH2
   bool            collectCounters;
+  bool            shadowDeposit;  // k_trace_shadow MODE 0 / 1 add an unoccluded ray's term where the ray ends; k_shadow_resolve<false> runs for catcher probes only (MI_PT_SHADOW_DEPOSIT)
   int             sortMode;  // per-bounce sort of the generic shade kernel: 0 off, 1 surface hits / others / dead, 2 hits grouped by material too
   bool            visualization;  // fc.frameInfo.visualization is a debug view (1 .. MI_VIZ_COUNT - 1): launchShade runs k_shade_viz
 };

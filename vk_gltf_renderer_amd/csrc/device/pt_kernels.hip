@@ -1615,7 +1615,7 @@ PT_DEV void shadowDeposit(const PathSoA& P, const Queues& Q, int nxt, uint32_t s
     if(!occ)
     {
       // `slot` is the entry's target (pt_scene.h: SHADOW_TARGET_QUEUE): the living path's record in the next active queue, or its slot
-      float4* const target = (slot & SHADOW_TARGET_QUEUE) ? &Q.active[nxt].rad[slot & ~SHADOW_TARGET_QUEUE] : &P.radiance[slot];
+      float4* const target = shadowTarget(P, Q, nxt, slot);
       float4        rad    = *target;
       rad.x += contrib.x * total.x;
       rad.y += contrib.y * total.y;
@@ -1645,13 +1645,20 @@ PT_DEV void shadowDeposit(const PathSoA& P, const Queues& Q, int nxt, uint32_t s
 }
 
 template <bool WIDE, int MODE, bool COUNT>
-__global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_trace_shadow(DevScene sc, const DevScene* __restrict__ scp, PathSoA P, Queues Q, int nxt, float catcherDarken, StatCounters* stats, int overflowOnly)
+__global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_trace_shadow(DevScene sc, const DevScene* __restrict__ scp, PathSoA P, Queues Q, int nxt, float catcherDarken, StatCounters* stats, int overflowOnly,
+                                                                                          int walkDeposit)
 {
   // `sc` (kernel argument, SGPRs) serves the inlined walk; the non-inlined material helpers of the transmissive path get the
   // device-resident copy `*scp` so that the argument's address never escapes (no scratch copy, cf. k_shade)
   constexpr int  SBLOCK    = ShadowCfg<MODE>::BLOCK;
   constexpr bool HAS_ALPHA = MODE >= 1, HAS_TRANS = MODE == 2, REC = MODE == 3;
   constexpr bool DEFER = MODE == 1 || MODE == 3;  // candidates of non-opaque instances go through alpha rounds
+  // MODE 0 / 1 with `walkDeposit` (MI_PT_SHADOW_DEPOSIT, wave-uniform): a ray that is not a catcher probe is settled where it ends -- see `finished` below
+  const bool inWalk = !HAS_TRANS && !REC && walkDeposit != 0;
+  // The alpha-tested walk on the 8-wide BVH sits at its 128 VGPRs with nothing spilled, and its prefetch keeps one word of the entry's `aux` (the seed):
+  // three more words waiting with every prefetched ray sent the prefetch itself to scratch, with a full wait behind its loads.  That instantiation
+  // asks for the contribution again when the ray STARTS -- the line has just arrived for the seed, nothing waits for the load before the ray ends.
+  constexpr bool LATE_CONTRIB = WIDE && MODE == 1;
   static_assert(!REC || WIDE, "the recording walk exists for the 8-wide BVH only");
   __shared__ int      s_stack[BVH_STACK_LDS * SBLOCK];
   __shared__ uint32_t s_prefix[NSUB + 1];
@@ -1700,13 +1707,15 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
   unsigned nodes = 0, tris = 0, rays = 0;
   // prefetched next shadow ray
   bool     pValid = false;
-  uint32_t pSlot = QUEUE_DEAD, pQPos = 0, qpos = 0;
+  uint32_t pSlot = QUEUE_DEAD, pQPos = 0;
+  uint32_t posOrTarget = 0;  // the ray's position in the shadow queue -- or, for a ray the walk settles itself (`inWalk && !catcherRay`), its TARGET (the entry's slot word)
   float4   pO = make_float4(0, 0, 0, 0), pD = make_float4(0, 0, 0, 0), pC = make_float4(0, 0, 0, 0);
   bool     catcherRay = false;
   uint32_t pBase = 0, pMask = 0, qBase = 0, qMask = 0;  // parked leaf hits of the 8-wide walk (see k_trace_closest)
   uint32_t aCount   = 0;                                // deferred alpha tests of this wave / some of them this lane's (MODE 1, 3)
   bool     aPending = false;
   bool     toOverflow = false;                          // MODE 3: this lane's ray just ended with candidates that did not fit the pool
+  bool     lateContrib = false;                         // LATE_CONTRIB: this lane's ray has just started and will deposit its own term
 #ifdef TRACE_PROFILE
   unsigned long long sp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long spStart = PROF_T();
@@ -1720,7 +1729,7 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
   CandRec  rec{Q.candPool, Q.candNext, &Q.counters[QC_CAND_POOL], Q.candCap, s_head + (REC ? (threadIdx.x & ~63u) : 0u), s_ovf + (REC ? (threadIdx.x & ~63u) : 0u), 0u, 0u};
   (void)rec;
 
-  auto deposit = [&](bool occ) { shadowDeposit(P, Q, nxt, slot, qpos, catcherRay, contrib, total, occ, catcherDarken); };
+  auto deposit = [&](bool occ) { shadowDeposit(P, Q, nxt, slot, posOrTarget, catcherRay, contrib, total, occ, catcherDarken); };
 
   // Transmissive candidates met by the any-hit walk, kept so that the common case (a few glass surfaces on the way to the
   // light) is settled by ordering this list instead of one search walk per candidate.  Separate local arrays: scratch, only
@@ -1810,13 +1819,17 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
       pValid = false;
       if(pSlot != QUEUE_DEAD)
       {
+        catcherRay = (__float_as_uint(pD.w) & 2u) != 0u;
         slot     = pSlot;
-        qpos     = pQPos;
+        // a ray the walk settles itself needs its target and never its queue position, every other ray the position alone: one register
+        // (the kernel sits at its 128 VGPRs; MODE 2's deposit is the only reader of both, and there it is always the position).  Every use
+        // below that indexes the queue is on the other side of `inWalk && !catcherRay`, or in a mode that never deposits in the walk.
+        posOrTarget     = (inWalk && !catcherRay) ? pSlot : pQPos;
         r        = makeRaySetup(xyz(pO), xyz(pD));
         tMax     = pO.w;
         isInside = (__float_as_uint(pD.w) & 1u) != 0u;
-        catcherRay = (__float_as_uint(pD.w) & 2u) != 0u;
-        contrib  = xyz(pC);
+        if(!LATE_CONTRIB)
+          contrib = xyz(pC);
         seed0    = __float_as_uint(pC.w);
         phase    = 0;
         nTrans   = 0;
@@ -1837,13 +1850,34 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
         if(COUNT) ++rays;
         if(sc.bvhRoot == BVH_EMPTY)  // nothing to hit: unoccluded
         {
-          if(HAS_TRANS)
-            deposit(false);
+          if(!HAS_TRANS && inWalk && !catcherRay)
+          {
+            // an empty walk: the ray ends below like any other unoccluded one (the deposit has ONE place in this kernel)
+            G    = NodeGroup{0, 0};
+            node = BVH_EMPTY;
+          }
           else
-            reinterpret_cast<uint32_t*>(&Q.shadow.org[qpos])[3] = CAND_NIL;
-          active = false;
+          {
+            if(HAS_TRANS)
+              deposit(false);
+            else
+              reinterpret_cast<uint32_t*>(&Q.shadow.org[posOrTarget])[3] = CAND_NIL;
+            active = false;
+          }
         }
+        lateContrib = LATE_CONTRIB && inWalk && active && !catcherRay;
       }
+    }
+    // In a block of its own BEHIND the ray's start: that block ends with the wait for the prefetched words (they move into the ray's registers
+    // there), and these loads must not stand in front of it.  Three loads of one word each, which the compiler does not merge: a three-word load
+    // wants consecutive registers, and the copies out of them brought a wait for the load to this place.
+    if(lateContrib)
+    {
+      lateContrib = false;
+      const float* const a = reinterpret_cast<const float*>(&in.aux[pQPos]);
+      contrib.x = __hip_atomic_load(a + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      contrib.y = __hip_atomic_load(a + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      contrib.z = __hip_atomic_load(a + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     if(!feed.exhausted)
     {
@@ -2029,12 +2063,21 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
           {
             if(HAS_TRANS)
               deposit(occluded);  // the ordered-search kernel settles its rays itself
+            else if(inWalk && !catcherRay)
+            {
+              // An occluded ray leaves nothing behind.  An unoccluded one adds its term to the path's radiance record here, as three
+              // float atomics without a returned value (shadowDepositAdd, pt_scene.h): the record is not loaded and the wave does not
+              // wait for the adds.  What used to sit here in rounds 1-4, a load / add / store of the record in the middle of a
+              // persistent wave, stalled the whole wave for a memory round trip whenever one of its rays ended (a quarter of this
+              // kernel's time on the glass workload), which is why the recording walk below still hands its rays to a pass of their own.
+              if(!occluded)  // (here posOrTarget is the target)
+                shadowDepositAdd(shadowTarget(P, Q, nxt, posOrTarget), contrib);
+            }
             else
             {
-              // The outcome goes into the ray's queue entry (org.w, the walk is done with tmax): k_shadow_resolve adds the
-              // contributions as one streaming pass.  Doing it here -- a dependent read-modify-write of the path's radiance in
-              // the middle of a persistent wave -- stalled the whole wave for a memory round trip whenever one of its rays
-              // ended: a quarter of this kernel's time on the glass workload.
+              // The outcome goes into the ray's queue entry (org.w, the walk is done with tmax) and k_shadow_resolve settles the ray:
+              // catcher probes (their deposit reads aux2 and may end the path's continuation entry), every ray of the recording walk
+              // (MODE 3: the recorded candidates are evaluated in order there), and every ray when MI_PT_SHADOW_DEPOSIT=0.
               uint32_t code = occluded ? SHADOW_OCCLUDED : CAND_NIL;
               if(REC && !occluded)
               {
@@ -2042,9 +2085,9 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
                 toOverflow = s_ovf[threadIdx.x] != 0u;
               }
               if(toOverflow)  // the entry keeps its tmax for the ordered-search kernel and is flagged in dir.w (bit 2)
-                reinterpret_cast<uint32_t*>(&Q.shadow.dir[qpos])[3] |= SHADOW_DIR_OVERFLOW;
+                reinterpret_cast<uint32_t*>(&Q.shadow.dir[posOrTarget])[3] |= SHADOW_DIR_OVERFLOW;
               else
-                reinterpret_cast<uint32_t*>(&Q.shadow.org[qpos])[3] = code;
+                reinterpret_cast<uint32_t*>(&Q.shadow.org[posOrTarget])[3] = code;
             }
             active = false;
           }
@@ -2062,7 +2105,7 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
             base = atomicAdd(&Q.counters[QC_OVERFLOW], uint32_t(__popcll(mO)));
           base = uint32_t(__builtin_amdgcn_readlane(int(base), first));
           if(toOverflow)
-            Q.overflow[base + laneCountBelow(mO)] = qpos;
+            Q.overflow[base + laneCountBelow(mO)] = posOrTarget;
         }
         toOverflow = false;
       }
@@ -2092,11 +2135,14 @@ __global__ void __launch_bounds__(ShadowCfg<MODE>::BLOCK, TRACE_MIN_WAVES) k_tra
 }
 
 //================================================================================================================================
-// k_shadow_resolve: the end of every shadow ray -- `radiance += contribution * transmission` (gltf_pathtrace.slang:462-471) -- and
-// the ordered half of TraceShadow for rays that met transmissive candidates (raytracer_interface.h.slang:160-178)
+// k_shadow_resolve: the end of the shadow rays the any-hit walk does not settle itself -- `radiance += contribution * transmission`
+// (gltf_pathtrace.slang:462-471), the two outcomes of a shadow-catcher probe -- and the ordered half of TraceShadow for rays that met
+// transmissive candidates (raytracer_interface.h.slang:160-178)
 //================================================================================================================================
-// One streaming pass over the shadow queue, one thread per entry, reading the outcome k_trace_shadow left in org.w.  Occluded rays
-// cost one word.  A ray with recorded candidates (a chain in Q.candPool, typically two to four: the shells of the glass between a
+// One streaming pass over the shadow queue, one thread per entry, reading the outcome k_trace_shadow left in org.w.  Which rays it
+// finds there: <true>, behind the recording walk (MODE 3), all of them; <false>, behind MODE 0 / 1, the catcher probes alone
+// (`catcherOnly`: the walk has added every other ray's term, the launch is left out on frames without a catcher plane) -- or all of
+// them with MI_PT_SHADOW_DEPOSIT=0.  Occluded rays cost one word.  A ray with recorded candidates (a chain in Q.candPool, typically two to four: the shells of the glass between a
 // point and the light) takes them in increasing (t, renderNode, primitive) order by repeated selection over the chain -- no
 // per-thread array, the chain is L2 resident -- and each accepted one multiplies the transmission by getShadowTransmission() over
 // the segment since the previous accepted one, until the product drops to MIN_TRANSMISSION.  Nothing here walks the BVH.
@@ -2177,7 +2223,7 @@ PT_DEV void resolveChain(const DevScene& sc, const PathSoA& P, const Queues& Q, 
 // r06_glass_pmc_summary.json): they are listed in LDS while the block streams through its entries -- rays without a chain are settled on the spot -- and the block
 // works the list off 256 rays at a time, every lane on a chain (-DRESOLVE_INLINE_CHAINS: rounds 2-5, each ray's chain where the ray is met).
 template <bool REC>
-__global__ void __launch_bounds__(256) k_shadow_resolve(const DevScene* __restrict__ scp, PathSoA P, Queues Q, int nxt, float catcherDarken)
+__global__ void __launch_bounds__(256) k_shadow_resolve(const DevScene* __restrict__ scp, PathSoA P, Queues Q, int nxt, float catcherDarken, int catcherOnly)
 {
   __shared__ uint32_t s_prefix[NSUB + 1];
 #ifndef RESOLVE_INLINE_CHAINS
@@ -2186,15 +2232,21 @@ __global__ void __launch_bounds__(256) k_shadow_resolve(const DevScene* __restri
   constexpr bool LIST = false;
 #endif
   __shared__ uint32_t s_chain[LIST ? 512 : 1];
-  __shared__ uint32_t s_chainCount;
+  __shared__ uint32_t s_chainCount, s_chainSeen;  // entries listed; the count the block decides on (workOff)
   if(threadIdx.x == 0)
     s_chainCount = 0;
   queuePrefix(&Q.counters[(nxt ? QC_PAIR1 : QC_PAIR0) + 1], s_prefix);
   const uint32_t  count = s_prefix[NSUB];
   const DevScene& sc    = uniformConst(*scp);
   auto workOff = [&](bool all) {  // whole block; contains barriers
+    // the decision is the block's: thread 0 copies the count into a word nobody else writes, so that a thread that is late to read
+    // it cannot see the count a faster one -- which left early and went on to the next round's atomicAdd -- has already raised (and
+    // enter the barriers below while that one is elsewhere)
     __syncthreads();
-    const uint32_t n = s_chainCount;
+    if(threadIdx.x == 0)
+      s_chainSeen = s_chainCount;
+    __syncthreads();
+    const uint32_t n = s_chainSeen;
     if(n == 0u || (!all && n < 256u))
       return;
     const uint32_t take = min(n, 256u), base = n - take;
@@ -2227,7 +2279,7 @@ __global__ void __launch_bounds__(256) k_shadow_resolve(const DevScene* __restri
         const uint32_t code       = reinterpret_cast<const uint32_t*>(&Q.shadow.org[qpos])[3];
         const bool     catcherRay = (__float_as_uint(d4.w) & 2u) != 0u;
         const bool     occluded   = code == SHADOW_OCCLUDED;
-        if(!occluded || catcherRay)
+        if((!occluded || catcherRay) && (REC || catcherRay || catcherOnly == 0))
         {
           if(REC && !occluded && code != CAND_NIL)
           {
@@ -2578,9 +2630,13 @@ void launchTraceShadowT(const LaunchCtx& c, int nxt)
   const unsigned bs  = mode == 2 ? unsigned(ShadowCfg<2>::BLOCK) : unsigned(ShadowCfg<0>::BLOCK);
   dim3 grid(c.persistentBlocks * 256u / bs), block(bs);
 #define MI_LAUNCH_SHADOW(M, C, OVF) \
-  hipLaunchKernelGGL((k_trace_shadow<WIDE, M, C>), grid, block, 0, c.stream, c.scene, c.sceneDev, c.paths, c.queues, nxt, darken, c.stats, OVF)
-  // the walk leaves every ray's outcome in its queue entry; k_shadow_resolve adds the contributions (and, after the recording
-  // walk, evaluates the recorded transmissive candidates in order) as one streaming pass
+  hipLaunchKernelGGL((k_trace_shadow<WIDE, M, C>), grid, block, 0, c.stream, c.scene, c.sceneDev, c.paths, c.queues, nxt, darken, c.stats, OVF, deposit)
+  // MODE 0 / 1 add an unoccluded ray's term where the ray ends (LaunchCtx::shadowDeposit); only catcher probes leave their outcome in the
+  // queue entry, and k_shadow_resolve<false> runs for them alone -- on frames with a catcher plane.  With the switch off, and behind the
+  // recording walk (MODE 3), every ray's outcome goes into its entry and k_shadow_resolve settles them as one streaming pass (<true>: it
+  // also evaluates the recorded transmissive candidates in order).
+  const int  deposit     = (c.shadowDeposit && (mode == 0 || mode == 1)) ? 1 : 0;
+  const bool catcherRays = (c.fc.frameInfo.flags & MI_SCENE_USE_INFINITE_PLANE) && (c.fc.frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER);
   const dim3 rgrid(c.persistentBlocks), rblock(256);
   if(mode == 0)      { if(c.collectCounters) MI_LAUNCH_SHADOW(0, true, 0); else MI_LAUNCH_SHADOW(0, false, 0); }
   else if(mode == 1) { if(c.collectCounters) MI_LAUNCH_SHADOW(1, true, 0); else MI_LAUNCH_SHADOW(1, false, 0); }
@@ -2594,7 +2650,7 @@ void launchTraceShadowT(const LaunchCtx& c, int nxt)
   }
   if(mode == 3)
   {
-    hipLaunchKernelGGL(k_shadow_resolve<true>, rgrid, rblock, 0, c.stream, c.sceneDev, c.paths, c.queues, nxt, darken);
+    hipLaunchKernelGGL(k_shadow_resolve<true>, rgrid, rblock, 0, c.stream, c.sceneDev, c.paths, c.queues, nxt, darken, 0);
     if constexpr(WIDE)
     {
       // normally on an empty list: the rays whose candidates did not fit the pool, by ordered search
@@ -2603,8 +2659,8 @@ void launchTraceShadowT(const LaunchCtx& c, int nxt)
       if(c.collectCounters) MI_LAUNCH_SHADOW(2, true, 1); else MI_LAUNCH_SHADOW(2, false, 1);
     }
   }
-  else if(mode != 2)
-    hipLaunchKernelGGL(k_shadow_resolve<false>, rgrid, rblock, 0, c.stream, c.sceneDev, c.paths, c.queues, nxt, darken);
+  else if(mode != 2 && (!deposit || catcherRays))
+    hipLaunchKernelGGL(k_shadow_resolve<false>, rgrid, rblock, 0, c.stream, c.sceneDev, c.paths, c.queues, nxt, darken, deposit);
 #undef MI_LAUNCH_SHADOW
 }
 }  // namespace

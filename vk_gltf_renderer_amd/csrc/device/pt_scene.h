@@ -362,9 +362,9 @@ struct RayQueue
   // the surviving paths are sparse in slot space: three 16-byte gathers by slot touched up to three cache lines per path (and three
   // scattered stores), where the entry's records now arrive in the order the wave processes them.
   float4*   misc;  // maxRoughness.y, flags (uint bits), seed (uint bits), cone.width
-  float4*   rad;   // radiance so far .rgb, maxRoughness.x | RADW_NOT_SOLID -- k_shadow_resolve adds a shadow ray's term HERE while the path lives
+  float4*   rad;   // radiance so far .rgb, maxRoughness.x | RADW_NOT_SOLID -- the shadow stage (k_trace_shadow, k_shadow_resolve) adds a shadow ray's term HERE while the path lives
 };
-// slot field of a SHADOW queue entry when the path's state is in the queue: where k_shadow_resolve adds the ray's term -- bit 31 set:
+// slot field of a SHADOW queue entry when the path's state is in the queue: where the shadow stage adds the ray's term -- bit 31 set:
 // entry (slot & 0x7fffffff) of the NEXT active queue's `rad` (the path goes on); clear: PathSoA::radiance[slot] (the path ended with
 // this bounce, its radiance already lies where k_finish_sample reads it)
 constexpr uint32_t SHADOW_TARGET_QUEUE = 0x80000000u;
@@ -388,6 +388,24 @@ struct Queues
 constexpr uint32_t CAND_NIL        = 0xffffffffu;  // unoccluded, nothing recorded
 constexpr uint32_t SHADOW_OCCLUDED = 0xfffffffeu;
 constexpr uint32_t SHADOW_DIR_OVERFLOW = 4u;  // dir.w bit 2: candidates did not fit the pool, the ordered-search kernel re-traces the ray (org.w keeps tmax)
+#ifdef __HIPCC__  // (scoped atomics: device compilations only -- the host-side harnesses of these headers do not deposit)
+// The term of an unoccluded, non-catcher shadow ray, added where the any-hit walk ends the ray (k_trace_shadow MODE 0 / 1, RunSwitches::shadowDeposit):
+// rgb of a radiance record += c as three float atomics whose result nobody asks for -- no load of the record, nothing for the wave to wait for.  A
+// bounce has at most one shadow ray per path and the record is the path's own, so each component receives ONE add per kernel: the sum is the rounded
+// sum a load / add / store gives, in any order (tests/device_kat/kat_atomic_deposit.hip pins the instruction's arithmetic).  `.w` is not touched.
+PT_DEV void shadowDepositAdd(float4* target, f3 c)
+{
+  float* const p = reinterpret_cast<float*>(target);
+  (void)__hip_atomic_fetch_add(p + 0, c.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (global_atomic_add_f32 without a returned value:
+  (void)__hip_atomic_fetch_add(p + 1, c.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  //  tests/test_shadow_deposit_isa.py)
+  (void)__hip_atomic_fetch_add(p + 2, c.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// where a shadow-queue entry's term goes: `slot` is the entry's target (SHADOW_TARGET_QUEUE)
+PT_DEV float4* shadowTarget(const PathSoA& P, const Queues& Q, int nxt, uint32_t slot)
+{
+  return (slot & SHADOW_TARGET_QUEUE) ? &Q.active[nxt].rad[slot & ~SHADOW_TARGET_QUEUE] : &P.radiance[slot];
+}
+#endif
 enum : int
 {
   // Queue tails.  PAIR q holds, per sub-queue s, two adjacent words: [2s] = entries appended to active queue q, [2s+1] =

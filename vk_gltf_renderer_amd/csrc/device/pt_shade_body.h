@@ -641,7 +641,7 @@
     }
     if(pushShadow)
     {
-      // where k_shadow_resolve adds this ray's term: the path's next queue entry while it lives, PathSoA::radiance once it has ended
+      // where the shadow stage (k_trace_shadow, or k_shadow_resolve) adds this ray's term: the path's next queue entry while it lives, PathSoA::radiance once it has ended
       Q.shadow.slot[posShadow] = (stateInQueue && alive) ? (posNext | SHADOW_TARGET_QUEUE) : slot;
       Q.shadow.org[posShadow]  = shOrg;
       Q.shadow.dir[posShadow]  = shDir;
