@@ -53,3 +53,31 @@ static inline unsigned long long atomicMax(unsigned long long* p, unsigned long 
   while(old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
   return old;
 }
+
+// ---- for dev_buf.h (tests/host_shim/dev_buf_on_host.cpp): malloc-backed device memory that counts its calls; the failAt-th hipMalloc from
+// now (1 = the next one) returns hipErrorOutOfMemory and allocates nothing
+#include <cstdlib>
+enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
+enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
+struct HipShimCounts { long mallocs = 0, frees = 0, memcpys = 0, failAt = 0; };
+inline HipShimCounts g_hipShim;
+static inline hipError_t hipMalloc(void** p, size_t bytes)
+{
+  if(g_hipShim.failAt > 0 && --g_hipShim.failAt == 0)
+    return hipErrorOutOfMemory;
+  *p = bytes ? std::malloc(bytes) : nullptr;  // (hipMalloc of 0 bytes: null and success)
+  g_hipShim.mallocs += *p ? 1 : 0;
+  return *p || !bytes ? hipSuccess : hipErrorOutOfMemory;
+}
+static inline hipError_t hipFree(void* p)
+{
+  g_hipShim.frees += p ? 1 : 0;
+  std::free(p);
+  return hipSuccess;
+}
+static inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind)
+{
+  ++g_hipShim.memcpys;
+  std::memcpy(dst, src, bytes);
+  return hipSuccess;
+}

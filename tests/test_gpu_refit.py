@@ -344,3 +344,69 @@ def test_one_refit_per_animated_frame(skinned):
     def count(what):
         return sum(1 for line in animated.splitlines() if line.startswith("[mi_pt build]") and line.split()[2] == what)
     assert count("deform") == 3 and count("refit") == 3 and count("rebuild") == 0, animated
+
+
+def test_scene_bytes_follow_the_owned_acceleration_arrays(tmp_path):
+    """sceneBytes is summed from the buffers the instance owns, the acceleration structure's included: rebuilds of one node table leave it
+    where the creation put it, and a failed rebuild (MI_PT_DIAG_FAIL_BUILD, armed at creation) takes off exactly the node, triangle,
+    shade-record and plane arrays of the structure it released -- an array kept or dropped by mistake shows up as a difference.
+    The instances are created with MI_PT_REINSERT=0: by default the creation (and the build of a switch to REFIT) runs 16 reinsertion
+    passes that a rebuild does not (RunSwitches::reinsertUpdate), so its tree has another node count than the rebuilds' -- on this scene
+    14 nodes fewer, sceneBytes 292180 at creation against 295988 after every rebuild, 14 x (80 + 192) apart."""
+    b = scenegen.GlbBuilder()
+    floor = b.material(scenegen.lambert_material((0.5, 0.5, 0.5)))
+    pos, nrm, uv, idx = scenegen.grid(4, 4, (10, 10), "y")
+    b.node(mesh=b.mesh([b.primitive(pos, idx, nrm, uv, material=floor)]))
+    sp = scenegen.uv_sphere(24, 12, 0.6)
+    for k, c in enumerate(((0.8, 0.3, 0.2), (0.2, 0.7, 0.3), (0.3, 0.3, 0.8))):
+        b.node(mesh=b.mesh([b.primitive(sp[0], sp[3], sp[1], sp[2], material=b.material(scenegen.lambert_material(c)))]), translation=[-1.5 + 1.5 * k, 0.61, 0.0])
+    b.camera_node((0.0, 2.5, 5.0), (0, 0.5, 0), yfov=0.7)
+    st = pu.Setup(b.save(str(tmp_path / "spheres.glb")), 160, 120, max_depth=4)
+    nodes, n = _nodes(st.scene)
+    shade_record, alpha_record = 32, 0  # DevShadeTri; every material is opaque, so the scene has no alpha records (DevAlphaTri, 48 B)
+
+    def create(fail_build_at=None, **kw):  # (run-time switches are read once, at mi_pt_create)
+        switches = dict({"MI_PT_REINSERT": "0"}, **({"MI_PT_DIAG_FAIL_BUILD": str(fail_build_at)} if fail_build_at else {}))
+        os.environ.update(switches)
+        try:
+            return _tracer(st, **kw)
+        finally:
+            for k in switches:
+                del os.environ[k]
+
+    for bvh, plane_bytes in ((0, 192), (1, 0)):  # the 8-wide BVH with its 48 float planes per node; the BVH2 walk has none
+        tr = create(fail_build_at=3, bvh=bvh)
+        seen = [tr.memory()["sceneBytes"]]
+        for _ in range(2):
+            tr.update_render_nodes(nodes, n, None)
+            seen.append(tr.memory()["sceneBytes"])
+        s = tr.stats()
+        assert s["bvhTriangleCount"] > 1700 and s["bvhNodeCount"] > 0 and s["bvhTriangleBytes"] == 48 and s["bvhNodeBytes"] == (64 if bvh else 80), s
+        with pytest.raises(ptmod.MiError):
+            tr.update_render_nodes(nodes, n, None)
+        failed = tr.memory()["sceneBytes"]
+        tr.update_render_nodes(nodes, n, None)
+        seen.append(tr.memory()["sceneBytes"])
+        released = s["bvhNodeCount"] * (s["bvhNodeBytes"] + plane_bytes) + s["bvhTriangleCount"] * (s["bvhTriangleBytes"] + shade_record + alpha_record)
+        print("bvh", bvh, "sceneBytes", seen, "after the failed rebuild", failed, "released", released, s["bvhNodeCount"], s["bvhTriangleCount"])
+        assert seen == [seen[0]] * 4, seen
+        assert seen[0] - failed == released, (seen[0], failed, released)
+        tr.close()
+
+    # REFIT mode: the refit data on top, through refits of the same table and through rebuilds (a visibility change and its return)
+    tr = create()
+    rebuild_bytes = tr.memory()["sceneBytes"]
+    tr.set_accel_update("refit")
+    refit_bytes = tr.accel_info()["refitBytes"]
+    with_refit = tr.memory()["sceneBytes"]
+    assert refit_bytes > 0 and with_refit == rebuild_bytes + refit_bytes
+    for vis, kind in ((None, capi.MI_PT_ACCEL_LAST_REFIT), ((C.c_uint8 * n)(*([1] * (n - 1) + [0])), capi.MI_PT_ACCEL_LAST_BUILD), (None, capi.MI_PT_ACCEL_LAST_BUILD),
+                      (None, capi.MI_PT_ACCEL_LAST_REFIT)):
+        tr.update_render_nodes(nodes, n, vis)
+        info = tr.accel_info()
+        assert info["lastUpdate"] == kind, info
+        if vis is None:
+            assert tr.memory()["sceneBytes"] == with_refit and info["refitBytes"] == refit_bytes, (tr.memory(), info, with_refit, refit_bytes)
+        else:
+            assert tr.memory()["sceneBytes"] < with_refit
+    tr.close()

@@ -472,123 +472,108 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
     }
     return true;
   };
+  Bvh8Output     r;  // becomes `out` once the collapse has succeeded: a failure leaves `out` empty
   const uint32_t numInner = b2.numNodes;
   const bool hostCollapse = opt.hostCollapse;
   const int  leafTrisOpt  = 2;  // (see the note above Cand)
   if(numInner > 0 && !hostCollapse)
   {
     // ---- device collapse, one level at a time (see the header comment) -------------------------------------------------------
-    Node8*              dNodes = nullptr;
-    int *               itemsA = nullptr, *itemsB = nullptr;
-    uint32_t*           dPerm  = nullptr;
-    unsigned long long *counts = nullptr, *offsets = nullptr, *totals = nullptr;
-    void*               scanTemp  = nullptr;
-    size_t              scanBytes = 0;
-    bool                ok        = true;
-    uint32_t            numNodes8 = 0, trisPlaced = 0;
-    DpTables            dp{nullptr, nullptr};
-    int *               dpParent = nullptr, *dpLeafParent = nullptr;
-    unsigned*           dpArrive = nullptr;
-    do
+    DevBuf<Node8>              dNodes;
+    DevBuf<int>                itemsA, itemsB;
+    DevBuf<uint32_t>           dPerm;
+    DevBuf<unsigned long long> counts, offsets, totals;
+    DevBuf<uint8_t>            scanTemp;
+    size_t                     scanBytes = 0;
+    uint32_t                   trisPlaced = 0;
+    DpTables                   dp{nullptr, nullptr};
+    DevBuf<float>              dpCost;
+    DevBuf<int8_t>             dpSplit;
+    DevBuf<int>                dpParent, dpLeafParent;
+    DevBuf<unsigned>           dpArrive;
+    // every 8-wide node is rooted at a distinct BVH2 inner node: numInner bounds their number and the length of any level
+    if(!check(dNodes.alloc(numInner), "alloc BVH8 nodes (worst case)")) return false;
+    if(!check(itemsA.alloc(numInner), "alloc level items")) return false;
+    if(!check(itemsB.alloc(numInner), "alloc level items")) return false;
+    if(!check(dPerm.alloc(n), "alloc perm")) return false;
+    if(opt.keepRefit)  // the refit data (bvh_refit.hip): the box each triangle slot was filed under
+      if(!check(r.slotBox.alloc(n), "alloc refit slot boxes")) return false;
+    if(!check(counts.alloc(numInner), "alloc counts")) return false;
+    if(!check(offsets.alloc(numInner), "alloc offsets")) return false;
+    if(!check(totals.alloc(1), "alloc totals")) return false;
+    if(!check(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, counts.ptr, offsets.ptr, int(numInner), stream), "scan size")) return false;
+    if(!check(scanTemp.alloc(scanBytes), "alloc scan")) return false;
+    const int root = b2.root;
+    if(!check(hipMemcpyAsync(itemsA.ptr, &root, sizeof(int), hipMemcpyHostToDevice, stream), "seed level 0")) return false;
+    uint32_t levelStart = 0, levelCount = 1;
+    uint32_t   maxLeaf = uint32_t(leafTrisOpt);
+    // which BVH2 subtrees become the children of an 8-wide node (Bvh8Options; the images do not depend on it)
+    const bool sahDp   = opt.sahCollapse;
+    if(sahDp)
     {
-      // every 8-wide node is rooted at a distinct BVH2 inner node: numInner bounds their number and the length of any level
-      if(!(ok = check(hipMalloc(&dNodes, sizeof(Node8) * size_t(numInner)), "alloc BVH8 nodes (worst case)"))) break;
-      if(!(ok = check(hipMalloc(&itemsA, sizeof(int) * size_t(numInner)), "alloc level items"))) break;
-      if(!(ok = check(hipMalloc(&itemsB, sizeof(int) * size_t(numInner)), "alloc level items"))) break;
-      if(!(ok = check(hipMalloc(&dPerm, sizeof(uint32_t) * size_t(n)), "alloc perm"))) break;
-      if(opt.keepRefit)  // the refit data (bvh_refit.hip): the box each triangle slot was filed under
-        if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.slotBox), sizeof(RefitBox) * size_t(n)), "alloc refit slot boxes"))) break;
-      if(!(ok = check(hipMalloc(&counts, sizeof(unsigned long long) * size_t(numInner)), "alloc counts"))) break;
-      if(!(ok = check(hipMalloc(&offsets, sizeof(unsigned long long) * size_t(numInner)), "alloc offsets"))) break;
-      if(!(ok = check(hipMalloc(&totals, sizeof(unsigned long long)), "alloc totals"))) break;
-      if(!(ok = check(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, counts, offsets, int(numInner), stream), "scan size"))) break;
-      if(!(ok = check(hipMalloc(&scanTemp, scanBytes), "alloc scan"))) break;
-      const int root = b2.root;
-      if(!(ok = check(hipMemcpyAsync(itemsA, &root, sizeof(int), hipMemcpyHostToDevice, stream), "seed level 0"))) break;
-      uint32_t levelStart = 0, levelCount = 1;
-      uint32_t   maxLeaf = uint32_t(leafTrisOpt);
-      // which BVH2 subtrees become the children of an 8-wide node (Bvh8Options; the images do not depend on it)
-      const bool sahDp   = opt.sahCollapse;
-      if(sahDp)
-      {
-        maxLeaf = std::min(maxLeaf, 3u);
-        if(!(ok = check(hipMalloc(&dp.cost, sizeof(float) * 8 * size_t(numInner)), "alloc DP cost"))) break;
-        if(!(ok = check(hipMalloc(&dp.split, 8 * size_t(numInner)), "alloc DP split"))) break;
-        if(!(ok = check(hipMalloc(&dpParent, sizeof(int) * size_t(numInner)), "alloc DP parents"))) break;
-        if(!(ok = check(hipMalloc(&dpLeafParent, sizeof(int) * size_t(n)), "alloc DP leaf parents"))) break;
-        if(!(ok = check(hipMalloc(&dpArrive, sizeof(unsigned) * size_t(numInner)), "alloc DP tickets"))) break;
-        if(!(ok = check(hipMemsetAsync(dpArrive, 0, sizeof(unsigned) * size_t(numInner), stream), "clear DP tickets"))) break;
-        hipLaunchKernelGGL(k_dp_parents, dim3((numInner + 255u) / 256u), dim3(256), 0, stream, int(numInner), b2.nodes, dpParent, dpLeafParent, root);
-        hipLaunchKernelGGL(k_dp_solve, dim3((n + 255u) / 256u), dim3(256), 0, stream, int(n), b2.nodes, dpParent, dpLeafParent, dpArrive, dp, maxLeaf);
-        if(!(ok = check(hipGetLastError(), "DP kernels"))) break;
-      }
-      while(levelCount > 0)
-      {
-        const unsigned g = (levelCount + 127u) / 128u;
-        hipLaunchKernelGGL(k_collapse_count, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA, b2.nodes, dp, maxLeaf, counts);
-        if(!(ok = check(hipcub::DeviceScan::ExclusiveSum(scanTemp, scanBytes, counts, offsets, int(levelCount), stream), "scan"))) break;
-        hipLaunchKernelGGL(k_collapse_emit, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA, b2.nodes, dp, maxLeaf, counts, offsets, levelStart,
-                           levelStart + levelCount, trisPlaced, dNodes, itemsB, dPerm, totals, out.slotBox);
-        out.levels.push_back(levelStart);
-        unsigned long long t = 0;
-        if(!(ok = check(hipGetLastError(), "collapse kernels"))) break;
-        if(!(ok = check(hipMemcpyAsync(&t, totals, sizeof(t), hipMemcpyDeviceToHost, stream), "read level totals"))) break;
-        if(!(ok = check(hipStreamSynchronize(stream), "sync level"))) break;
-        levelStart += levelCount;
-        levelCount = uint32_t(t);
-        trisPlaced += uint32_t(t >> 32);
-        if(levelStart + levelCount > numInner || trisPlaced > n)
-        {
-          err = "BVH8 collapse overran its bounds";
-          ok  = false;
-          break;
-        }
-        std::swap(itemsA, itemsB);
-      }
-      if(!ok)
-        break;
-      numNodes8 = levelStart;
-      if(trisPlaced != n)
-      {
-        err = "BVH8 collapse lost triangles";
-        ok  = false;
-        break;
-      }
-      if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.nodes), sizeof(Node8) * size_t(numNodes8)), "alloc BVH8 nodes"))) break;
-      if(!(ok = check(hipMemcpyAsync(out.nodes, dNodes, sizeof(Node8) * size_t(numNodes8), hipMemcpyDeviceToDevice, stream), "copy BVH8 nodes"))) break;
-      out.levels.push_back(numNodes8);
-      if(opt.keepRefit)  // (filled by the first pass of k_refit_level, which the caller runs over the new tree)
-        if(!(ok = check(hipMalloc(reinterpret_cast<void**>(&out.nodeBox), sizeof(RefitBox) * size_t(numNodes8)), "alloc refit node boxes"))) break;
-      if(!(ok = check(hipMalloc(&out.tris, sizeof(DevTri) * size_t(n)), "alloc BVH8 triangles"))) break;
-      hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm, b2.tris, out.tris);
-      ok = check(hipGetLastError(), "k_reorder_tris") && check(hipStreamSynchronize(stream), "sync");
-    } while(0);
-    (void)hipFree(dNodes); (void)hipFree(itemsA); (void)hipFree(itemsB); (void)hipFree(dPerm); (void)hipFree(counts); (void)hipFree(offsets);
-    (void)hipFree(totals); (void)hipFree(scanTemp);
-    (void)hipFree(dp.cost); (void)hipFree(dp.split); (void)hipFree(dpParent); (void)hipFree(dpLeafParent); (void)hipFree(dpArrive);
-    if(!ok)
+      maxLeaf = std::min(maxLeaf, 3u);
+      if(!check(dpCost.alloc(8 * size_t(numInner)), "alloc DP cost")) return false;
+      if(!check(dpSplit.alloc(8 * size_t(numInner)), "alloc DP split")) return false;
+      if(!check(dpParent.alloc(numInner), "alloc DP parents")) return false;
+      if(!check(dpLeafParent.alloc(n), "alloc DP leaf parents")) return false;
+      if(!check(dpArrive.alloc(numInner), "alloc DP tickets")) return false;
+      if(!check(hipMemsetAsync(dpArrive.ptr, 0, sizeof(unsigned) * size_t(numInner), stream), "clear DP tickets")) return false;
+      dp = DpTables{dpCost.ptr, dpSplit.ptr};
+      hipLaunchKernelGGL(k_dp_parents, dim3((numInner + 255u) / 256u), dim3(256), 0, stream, int(numInner), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, root);
+      hipLaunchKernelGGL(k_dp_solve, dim3((n + 255u) / 256u), dim3(256), 0, stream, int(n), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, dpArrive.ptr, dp, maxLeaf);
+      if(!check(hipGetLastError(), "DP kernels")) return false;
+    }
+    while(levelCount > 0)
     {
-      if(out.nodes) (void)hipFree(out.nodes);
-      if(out.tris) (void)hipFree(out.tris);
-      if(out.slotBox) (void)hipFree(out.slotBox);
-      if(out.nodeBox) (void)hipFree(out.nodeBox);
-      out = Bvh8Output();
+      const unsigned g = (levelCount + 127u) / 128u;
+      hipLaunchKernelGGL(k_collapse_count, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr);
+      if(!check(hipcub::DeviceScan::ExclusiveSum(scanTemp.ptr, scanBytes, counts.ptr, offsets.ptr, int(levelCount), stream), "scan")) return false;
+      hipLaunchKernelGGL(k_collapse_emit, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr, offsets.ptr, levelStart,
+                         levelStart + levelCount, trisPlaced, dNodes.ptr, itemsB.ptr, dPerm.ptr, totals.ptr, r.slotBox.ptr);
+      r.levels.push_back(levelStart);
+      unsigned long long t = 0;
+      if(!check(hipGetLastError(), "collapse kernels")) return false;
+      if(!check(hipMemcpyAsync(&t, totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream), "read level totals")) return false;
+      if(!check(hipStreamSynchronize(stream), "sync level")) return false;
+      levelStart += levelCount;
+      levelCount = uint32_t(t);
+      trisPlaced += uint32_t(t >> 32);
+      if(levelStart + levelCount > numInner || trisPlaced > n)
+      {
+        err = "BVH8 collapse overran its bounds";
+        return false;
+      }
+      std::swap(itemsA, itemsB);
+    }
+    const uint32_t numNodes8 = levelStart;
+    if(trisPlaced != n)
+    {
+      err = "BVH8 collapse lost triangles";
       return false;
     }
-    out.numNodes = numNodes8;
-    out.numTris  = n;
+    if(!check(r.nodes.alloc(5 * size_t(numNodes8)), "alloc BVH8 nodes")) return false;
+    if(!check(hipMemcpyAsync(r.nodes.ptr, dNodes.ptr, sizeof(Node8) * size_t(numNodes8), hipMemcpyDeviceToDevice, stream), "copy BVH8 nodes")) return false;
+    r.levels.push_back(numNodes8);
+    if(opt.keepRefit)  // (filled by the first pass of k_refit_level, which the caller runs over the new tree)
+      if(!check(r.nodeBox.alloc(numNodes8), "alloc refit node boxes")) return false;
+    if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
+    hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
+    if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
+    r.numNodes = numNodes8;
+    r.numTris  = n;
+    out        = std::move(r);
     return true;
   }
   // ---- host collapse (A/B reference, and the one-triangle scene): download the BVH2 -------------------------------------------
 
   std::vector<float4> nodes2(size_t(numInner) * 4);
-  if(numInner && !check(hipMemcpy(nodes2.data(), b2.nodes, nodes2.size() * sizeof(float4), hipMemcpyDeviceToHost), "download BVH2"))
+  if(numInner && !check(hipMemcpy(nodes2.data(), b2.nodes.ptr, nodes2.size() * sizeof(float4), hipMemcpyDeviceToHost), "download BVH2"))
     return false;
   std::vector<DevTri> tris2;
   if(numInner == 0)  // single triangle: need its bounds
   {
     tris2.resize(n);
-    if(!check(hipMemcpy(tris2.data(), b2.tris, sizeof(DevTri) * n, hipMemcpyDeviceToHost), "download triangles"))
+    if(!check(hipMemcpy(tris2.data(), b2.tris.ptr, sizeof(DevTri) * n, hipMemcpyDeviceToHost), "download triangles"))
       return false;
   }
   auto childRef = [&](int node, int which) {
@@ -856,27 +841,17 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
     return false;
   }
   // ---- upload ----------------------------------------------------------------------------------------------------------
-  uint32_t* dPerm = nullptr;
-  bool      ok    = check(hipMalloc(&out.nodes, nodes8.size() * sizeof(Node8)), "alloc BVH8 nodes")
-            && check(hipMemcpy(out.nodes, nodes8.data(), nodes8.size() * sizeof(Node8), hipMemcpyHostToDevice), "upload BVH8 nodes")
-            && check(hipMalloc(&out.tris, sizeof(DevTri) * n), "alloc BVH8 triangles") && check(hipMalloc(&dPerm, sizeof(uint32_t) * n), "alloc perm")
-            && check(hipMemcpy(dPerm, perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice), "upload perm");
-  if(ok)
-  {
-    hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm, b2.tris, out.tris);
-    ok = check(hipGetLastError(), "k_reorder_tris") && check(hipStreamSynchronize(stream), "sync");
-  }
-  if(dPerm)
-    (void)hipFree(dPerm);
-  if(!ok)
-  {
-    if(out.nodes) (void)hipFree(out.nodes);
-    if(out.tris) (void)hipFree(out.tris);
-    out = Bvh8Output();
-    return false;
-  }
-  out.numNodes = uint32_t(nodes8.size());
-  out.numTris  = n;
+  DevBuf<uint32_t> dPerm;
+  if(!check(r.nodes.alloc(5 * nodes8.size()), "alloc BVH8 nodes")) return false;
+  if(!check(hipMemcpy(r.nodes.ptr, nodes8.data(), nodes8.size() * sizeof(Node8), hipMemcpyHostToDevice), "upload BVH8 nodes")) return false;
+  if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
+  if(!check(dPerm.alloc(n), "alloc perm")) return false;
+  if(!check(hipMemcpy(dPerm.ptr, perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice), "upload perm")) return false;
+  hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
+  if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
+  r.numNodes = uint32_t(nodes8.size());
+  r.numTris  = n;
+  out        = std::move(r);
   return true;
 }
 

@@ -474,17 +474,14 @@ __global__ void k_re_refit(Bvh2Tree T, unsigned int* arrive)
     reinsertRefit(T, arrive, leaf);
 }
 
-// A failed call records the error and LEAVES THE ENCLOSING LOOP: the macro is a plain block (no do { } while(0) of its own, whose `break` would
-// only leave the macro), so its `break` belongs to the loop it is written in -- the do { } while(0) around a builder's body, or a pass / round
-// loop inside it, whose conditions test `ok` and which are followed by `if(!ok) break;` where more steps come after them.
+// A failed call records the error and returns false from the builder it is written in; the DevBuf locals free what was allocated.
 #define BUILD_CHECK(x)                                                                                                  \
   {                                                                                                                     \
     hipError_t e_ = (x);                                                                                                \
     if(e_ != hipSuccess)                                                                                                \
     {                                                                                                                   \
       err = std::string(#x) + ": " + hipGetErrorString(e_);                                                             \
-      ok  = false;                                                                                                      \
-      break;                                                                                                            \
+      return false;                                                                                                     \
     }                                                                                                                   \
   }
 
@@ -498,58 +495,53 @@ static bool reinsertBvh2(float4* nodes, int numInner, int root, int passes, int 
     *movesOut = 0;
   if(passes <= 0 || numInner < 3)
     return true;
-  static const bool   timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
-  const auto          t0     = std::chrono::steady_clock::now();
-  int                 passesRun = 0;
-  uint32_t            movesAll  = 0;
-  const int           ids = 2 * numInner + 1, B = 256;
-  int *               parent = nullptr, *leafParent = nullptr;
-  ReinsertMove*       moves  = nullptr;
-  unsigned long long* locks  = nullptr;
-  unsigned int *      arrive = nullptr, *carried = nullptr;
-  bool                ok     = true;
-  do
+  static const bool          timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  const auto                 t0     = std::chrono::steady_clock::now();
+  int                        passesRun = 0;
+  uint32_t                   movesAll  = 0;
+  const int                  ids = 2 * numInner + 1, B = 256;
+  DevBuf<int>                parent, leafParent;
+  DevBuf<ReinsertMove>       moves;
+  DevBuf<unsigned long long> locks;
+  DevBuf<unsigned int>       arrive, carried;
+  BUILD_CHECK(parent.alloc(numInner));
+  BUILD_CHECK(leafParent.alloc(numInner + 1));
+  BUILD_CHECK(moves.alloc(ids));
+  BUILD_CHECK(locks.alloc(ids));
+  BUILD_CHECK(arrive.alloc(numInner));
+  BUILD_CHECK(carried.alloc(1));
+  const Bvh2Tree T{nodes, parent.ptr, leafParent.ptr, numInner, root};
+  const dim3     gN((numInner + B - 1) / B), gI((ids + B - 1) / B), gL((numInner + 1 + B - 1) / B);
+  for(int pass = 0; pass < passes; ++pass)
   {
-    BUILD_CHECK(hipMalloc(&parent, sizeof(int) * numInner));
-    BUILD_CHECK(hipMalloc(&leafParent, sizeof(int) * (numInner + 1)));
-    BUILD_CHECK(hipMalloc(&moves, sizeof(ReinsertMove) * ids));
-    BUILD_CHECK(hipMalloc(&locks, sizeof(unsigned long long) * ids));
-    BUILD_CHECK(hipMalloc(&arrive, sizeof(unsigned int) * numInner));
-    BUILD_CHECK(hipMalloc(&carried, sizeof(unsigned int)));
-    const Bvh2Tree T{nodes, parent, leafParent, numInner, root};
-    const dim3     gN((numInner + B - 1) / B), gI((ids + B - 1) / B), gL((numInner + 1 + B - 1) / B);
-    for(int pass = 0; pass < passes && ok; ++pass)
+    hipLaunchKernelGGL(k_re_parents, gN, dim3(B), 0, stream, T);
+    hipLaunchKernelGGL(k_re_search, gI, dim3(B), 0, stream, T, ids, moves.ptr);
+    BUILD_CHECK(hipMemsetAsync(locks.ptr, 0, sizeof(unsigned long long) * ids, stream));
+    BUILD_CHECK(hipMemsetAsync(carried.ptr, 0, sizeof(unsigned int), stream));
+    for(int round = 0; round < rounds; ++round)
     {
-      hipLaunchKernelGGL(k_re_parents, gN, dim3(B), 0, stream, T);
-      hipLaunchKernelGGL(k_re_search, gI, dim3(B), 0, stream, T, ids, moves);
-      BUILD_CHECK(hipMemsetAsync(locks, 0, sizeof(unsigned long long) * ids, stream));
-      BUILD_CHECK(hipMemsetAsync(carried, 0, sizeof(unsigned int), stream));
-      for(int round = 0; round < rounds; ++round)
-      {
-        hipLaunchKernelGGL(k_re_lock, gI, dim3(B), 0, stream, T, ids, moves, locks);
-        hipLaunchKernelGGL(k_re_apply, gI, dim3(B), 0, stream, T, ids, moves, locks, carried);
-        hipLaunchKernelGGL(k_re_unlock, gI, dim3(B), 0, stream, ids, locks);
-      }
-      hipLaunchKernelGGL(k_re_parents, gN, dim3(B), 0, stream, T);
-      BUILD_CHECK(hipMemsetAsync(arrive, 0, sizeof(unsigned int) * numInner, stream));
-      hipLaunchKernelGGL(k_re_refit, gL, dim3(B), 0, stream, T, arrive);
-      BUILD_CHECK(hipGetLastError());
-      unsigned int done = 0;
-      BUILD_CHECK(hipMemcpyAsync(&done, carried, sizeof(done), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipStreamSynchronize(stream));
-      ++passesRun;
-      movesAll += done;
-      if(done < unsigned(numInner / 2000 + 1))
-        break;
+      hipLaunchKernelGGL(k_re_lock, gI, dim3(B), 0, stream, T, ids, moves.ptr, locks.ptr);
+      hipLaunchKernelGGL(k_re_apply, gI, dim3(B), 0, stream, T, ids, moves.ptr, locks.ptr, carried.ptr);
+      hipLaunchKernelGGL(k_re_unlock, gI, dim3(B), 0, stream, ids, locks.ptr);
     }
-  } while(0);
-  (void)hipFree(parent); (void)hipFree(leafParent); (void)hipFree(moves); (void)hipFree(locks); (void)hipFree(arrive); (void)hipFree(carried);
+    hipLaunchKernelGGL(k_re_parents, gN, dim3(B), 0, stream, T);
+    BUILD_CHECK(hipMemsetAsync(arrive.ptr, 0, sizeof(unsigned int) * numInner, stream));
+    hipLaunchKernelGGL(k_re_refit, gL, dim3(B), 0, stream, T, arrive.ptr);
+    BUILD_CHECK(hipGetLastError());
+    unsigned int done = 0;
+    BUILD_CHECK(hipMemcpyAsync(&done, carried.ptr, sizeof(done), hipMemcpyDeviceToHost, stream));
+    BUILD_CHECK(hipStreamSynchronize(stream));
+    ++passesRun;
+    movesAll += done;
+    if(done < unsigned(numInner / 2000 + 1))
+      break;
+  }
   if(movesOut)
     *movesOut = movesAll;
   if(timing)
     fprintf(stderr, "[mi_pt build] reinsertion: %d of %d passes x %d rounds over %d nodes and leaves, %u subtrees moved, %.2f ms\n", passesRun, passes, rounds, ids, movesAll,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  return ok;
+  return true;
 }
 
 bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, std::string& err)
@@ -561,66 +553,62 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
   out.root          = BVH_EMPTY;
   if(n == 0)
     return true;
-  DevTri*   trisTmp = nullptr;
-  float4 *  boxLo = nullptr, *boxHi = nullptr, *nodeLo = nullptr, *nodeHi = nullptr;
-  uint32_t *bounds = nullptr, *valsA = nullptr, *valsB = nullptr;
-  uint64_t *keysA = nullptr, *keysB = nullptr;
-  int2*     children = nullptr;
-  int *     parentInternal = nullptr, *parentLeaf = nullptr;
-  unsigned* arrive         = nullptr;
-  int*      nodeCnt        = nullptr;
-  void*     sortTemp       = nullptr;
-  size_t    sortBytes      = 0;
-  int *     cidA = nullptr, *cidB = nullptr, *nn = nullptr;
-  float4 *  cloA = nullptr, *chiA = nullptr, *cloB = nullptr, *chiB = nullptr;
-  unsigned long long *flags = nullptr, *pos = nullptr, *totals = nullptr;
-  void*     scanTemp  = nullptr;
-  size_t    scanBytes = 0;
-  const int B              = 256;
-  unsigned  gridT          = (n + B - 1) / B;
-  float *   splitArea = nullptr, *splitSum = nullptr;
-  uint32_t *splitCounts = nullptr, *splitOffsets = nullptr;
-  void*     splitTemp = nullptr;
+  // every temporary lives to the end of the build (a free on the way would synchronise the device); `nodes` and `tris` become the
+  // output's only once the build has succeeded
+  DevBuf<float4>   nodes;
+  DevBuf<DevTri>   tris, trisTmp;
+  DevBuf<float4>   boxLo, boxHi, nodeLo, nodeHi;
+  DevBuf<uint32_t> bounds, valsA, valsB;
+  DevBuf<uint64_t> keysA, keysB;
+  DevBuf<int2>     children;
+  DevBuf<int>      parentInternal, parentLeaf, nodeCnt;
+  DevBuf<unsigned> arrive;
+  DevBuf<uint8_t>  sortTemp, scanTemp, splitTemp;
+  size_t           sortBytes = 0, scanBytes = 0;
+  DevBuf<int>      cidA, cidB, nn;
+  DevBuf<float4>   cloA, chiA, cloB, chiB;
+  DevBuf<unsigned long long> flags, pos, totals;
+  const int        B     = 256;
+  unsigned         gridT = (n + B - 1) / B;
+  DevBuf<float>    splitArea, splitSum;
+  DevBuf<uint32_t> splitCounts, splitOffsets;
   BuildTables T{in.nodes, in.prims, in.instFlags, in.nodeTriOffset, in.entryNode, in.numEntries};
   const uint32_t initBounds[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-  bool           ok            = true;
   uint32_t       hb[6]         = {0, 0, 0, 0, 0, 0};
 
-  do
-  {
-  BUILD_CHECK(hipMalloc(&trisTmp, sizeof(DevTri) * n));
-  BUILD_CHECK(hipMalloc(&boxLo, sizeof(float4) * n));
-  BUILD_CHECK(hipMalloc(&boxHi, sizeof(float4) * n));
-  BUILD_CHECK(hipMalloc(&bounds, sizeof(initBounds)));
-  BUILD_CHECK(hipMemcpyAsync(bounds, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_tri_setup, dim3(gridT), dim3(B), 0, stream, T, n, trisTmp, boxLo, boxHi, bounds);
+  BUILD_CHECK(trisTmp.alloc(n));
+  BUILD_CHECK(boxLo.alloc(n));
+  BUILD_CHECK(boxHi.alloc(n));
+  BUILD_CHECK(bounds.alloc(6));
+  BUILD_CHECK(hipMemcpyAsync(bounds.ptr, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_tri_setup, dim3(gridT), dim3(B), 0, stream, T, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, bounds.ptr);
   BUILD_CHECK(hipGetLastError());
 
   // ---- pre-splitting: references instead of triangles from here on (bvh_split.h) ----
   if(in.splitFactor > 0.0f && n >= 2)
   {
     size_t tb1 = 0, tb2 = 0;
-    BUILD_CHECK(hipMalloc(&splitArea, sizeof(float) * n));
-    BUILD_CHECK(hipMalloc(&splitSum, sizeof(float)));
-    BUILD_CHECK(hipMalloc(&splitCounts, sizeof(uint32_t) * n));
-    BUILD_CHECK(hipMalloc(&splitOffsets, sizeof(uint32_t) * n));
-    BUILD_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb1, splitArea, splitSum, int(n), stream));
-    BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, splitCounts, splitOffsets, int(n), stream));
-    BUILD_CHECK(hipMalloc(&splitTemp, std::max(tb1, tb2)));
-    hipLaunchKernelGGL(k_split_area, dim3(gridT), dim3(B), 0, stream, n, boxLo, boxHi, splitArea);
-    BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp, tb1, splitArea, splitSum, int(n), stream));
+    BUILD_CHECK(splitArea.alloc(n));
+    BUILD_CHECK(splitSum.alloc(1));
+    BUILD_CHECK(splitCounts.alloc(n));
+    BUILD_CHECK(splitOffsets.alloc(n));
+    BUILD_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb1, splitArea.ptr, splitSum.ptr, int(n), stream));
+    BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, splitCounts.ptr, splitOffsets.ptr, int(n), stream));
+    BUILD_CHECK(splitTemp.alloc(std::max(tb1, tb2)));
+    hipLaunchKernelGGL(k_split_area, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, splitArea.ptr);
+    BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp.ptr, tb1, splitArea.ptr, splitSum.ptr, int(n), stream));
     // Splitting engages only where large triangles DOMINATE the scene's box area (the SAH is area weighted): the share of the summed box area held by
     // triangles above 64 x the mean is 0 / 0.05 on the evenly tessellated atrium / street stand-ins -- whose trees splitting only perturbs (-1 %) --
     // and 0.20 / 0.89 on their sliver versions (+6 % / +41 %).  The threshold is splitMinShare (default 0.1; 0 = always split).
     bool engage = true;
     if(in.splitMinShare > 0.0f)
     {
-      float* large = reinterpret_cast<float*>(splitCounts);  // (not yet in use)
+      float* large = reinterpret_cast<float*>(splitCounts.ptr);  // (not yet in use)
       float  sums[2] = {0.0f, 0.0f};
-      hipLaunchKernelGGL(k_split_large_area, dim3(gridT), dim3(B), 0, stream, n, splitArea, splitSum, 64.0f, large);
-      BUILD_CHECK(hipMemcpyAsync(&sums[0], splitSum, sizeof(float), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp, tb1, large, reinterpret_cast<float*>(splitOffsets), int(n), stream));
-      BUILD_CHECK(hipMemcpyAsync(&sums[1], splitOffsets, sizeof(float), hipMemcpyDeviceToHost, stream));
+      hipLaunchKernelGGL(k_split_large_area, dim3(gridT), dim3(B), 0, stream, n, splitArea.ptr, splitSum.ptr, 64.0f, large);
+      BUILD_CHECK(hipMemcpyAsync(&sums[0], splitSum.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
+      BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp.ptr, tb1, large, reinterpret_cast<float*>(splitOffsets.ptr), int(n), stream));
+      BUILD_CHECK(hipMemcpyAsync(&sums[1], splitOffsets.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
       BUILD_CHECK(hipStreamSynchronize(stream));
       engage = sums[0] > 0.0f && sums[1] >= in.splitMinShare * sums[0];
     }
@@ -630,117 +618,108 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
     uint32_t total  = n;
     for(int attempt = 0; engage && attempt < 5; ++attempt, factor *= 2.0f)
     {
-      hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp, boxLo, boxHi, splitSum, factor, in.splitMaxDepth, nullptr, splitCounts, nullptr, nullptr, nullptr);
+      hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, splitSum.ptr, factor, in.splitMaxDepth, nullptr, splitCounts.ptr, nullptr, nullptr, nullptr);
       BUILD_CHECK(hipGetLastError());
-      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(splitTemp, tb2, splitCounts, splitOffsets, int(n), stream));
+      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(splitTemp.ptr, tb2, splitCounts.ptr, splitOffsets.ptr, int(n), stream));
       uint32_t lastOff = 0, lastCnt = 0;
-      BUILD_CHECK(hipMemcpyAsync(&lastOff, splitOffsets + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipMemcpyAsync(&lastCnt, splitCounts + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      BUILD_CHECK(hipMemcpyAsync(&lastOff, splitOffsets.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      BUILD_CHECK(hipMemcpyAsync(&lastCnt, splitCounts.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
       BUILD_CHECK(hipStreamSynchronize(stream));
       total = lastOff + lastCnt;
       if(uint64_t(total) <= uint64_t(n) + uint64_t(n) / 2u + 4096u && total < (1u << 26))
         break;
       total = n;
     }
-    if(!ok)
-      break;
     if(total > n)
     {
       // (the reference arrays replace the triangle arrays only once all three exist and are filled; a failure on the way frees what was allocated)
-      DevTri* refTris = nullptr;
-      float4 *refLo = nullptr, *refHi = nullptr;
-      hipError_t e = hipMalloc(&refTris, sizeof(DevTri) * total);
-      if(e == hipSuccess) e = hipMalloc(&refLo, sizeof(float4) * total);
-      if(e == hipSuccess) e = hipMalloc(&refHi, sizeof(float4) * total);
+      DevBuf<DevTri> refTris;
+      DevBuf<float4> refLo, refHi;
+      hipError_t     e = refTris.alloc(total);
+      if(e == hipSuccess) e = refLo.alloc(total);
+      if(e == hipSuccess) e = refHi.alloc(total);
       if(e == hipSuccess)
       {
-        hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp, boxLo, boxHi, splitSum, factor, in.splitMaxDepth, splitOffsets, splitCounts, refTris, refLo, refHi);
+        hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, splitSum.ptr, factor, in.splitMaxDepth, splitOffsets.ptr, splitCounts.ptr, refTris.ptr, refLo.ptr, refHi.ptr);
         e = hipGetLastError();
       }
       if(e == hipSuccess) e = hipStreamSynchronize(stream);
       if(e != hipSuccess)
       {
-        (void)hipFree(refTris); (void)hipFree(refLo); (void)hipFree(refHi);
         err = std::string("triangle pre-splitting: ") + hipGetErrorString(e);
-        ok  = false;
-        break;
+        return false;
       }
-      (void)hipFree(trisTmp); (void)hipFree(boxLo); (void)hipFree(boxHi);
-      trisTmp = refTris; boxLo = refLo; boxHi = refHi;
+      trisTmp = std::move(refTris); boxLo = std::move(refLo); boxHi = std::move(refHi);
       n           = total;
       gridT       = (n + B - 1) / B;
       out.numTris = n;
-      BUILD_CHECK(hipMemcpyAsync(bounds, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(k_centroid_bounds, dim3(gridT), dim3(B), 0, stream, n, boxLo, boxHi, bounds);
+      BUILD_CHECK(hipMemcpyAsync(bounds.ptr, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
+      hipLaunchKernelGGL(k_centroid_bounds, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, bounds.ptr);
       BUILD_CHECK(hipGetLastError());
     }
   }
 
-  BUILD_CHECK(hipMalloc(&out.tris, sizeof(DevTri) * n));
+  BUILD_CHECK(tris.alloc(n));
   if(n == 1)
   {
-    BUILD_CHECK(hipMemcpyAsync(out.tris, trisTmp, sizeof(DevTri), hipMemcpyDeviceToDevice, stream));
+    BUILD_CHECK(hipMemcpyAsync(tris.ptr, trisTmp.ptr, sizeof(DevTri), hipMemcpyDeviceToDevice, stream));
     BUILD_CHECK(hipStreamSynchronize(stream));
     out.root     = ~0;  // leaf 0
     out.numNodes = 0;
   }
   else
   {
-    BUILD_CHECK(hipMalloc(&keysA, sizeof(uint64_t) * n));
-    BUILD_CHECK(hipMalloc(&keysB, sizeof(uint64_t) * n));
-    BUILD_CHECK(hipMalloc(&valsA, sizeof(uint32_t) * n));
-    BUILD_CHECK(hipMalloc(&valsB, sizeof(uint32_t) * n));
-    hipLaunchKernelGGL(k_morton, dim3(gridT), dim3(B), 0, stream, n, boxLo, boxHi, bounds, keysA, valsA);
+    BUILD_CHECK(keysA.alloc(n));
+    BUILD_CHECK(keysB.alloc(n));
+    BUILD_CHECK(valsA.alloc(n));
+    BUILD_CHECK(valsB.alloc(n));
+    hipLaunchKernelGGL(k_morton, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, bounds.ptr, keysA.ptr, valsA.ptr);
     BUILD_CHECK(hipGetLastError());
-    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, keysA, keysB, valsA, valsB, int(n), 0, 63, stream));
-    BUILD_CHECK(hipMalloc(&sortTemp, sortBytes));
-    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(sortTemp, sortBytes, keysA, keysB, valsA, valsB, int(n), 0, 63, stream));
+    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, keysA.ptr, keysB.ptr, valsA.ptr, valsB.ptr, int(n), 0, 63, stream));
+    BUILD_CHECK(sortTemp.alloc(sortBytes));
+    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(sortTemp.ptr, sortBytes, keysA.ptr, keysB.ptr, valsA.ptr, valsB.ptr, int(n), 0, 63, stream));
 
-    BUILD_CHECK(hipMalloc(&out.nodes, sizeof(float4) * 4 * (n - 1)));
+    BUILD_CHECK(nodes.alloc(4 * size_t(n - 1)));
     if(!in.karrasTopology)
     {
-      BUILD_CHECK(hipMalloc(&cidA, sizeof(int) * n)); BUILD_CHECK(hipMalloc(&cidB, sizeof(int) * n)); BUILD_CHECK(hipMalloc(&nn, sizeof(int) * n));
-      BUILD_CHECK(hipMalloc(&cloA, sizeof(float4) * n)); BUILD_CHECK(hipMalloc(&chiA, sizeof(float4) * n));
-      BUILD_CHECK(hipMalloc(&cloB, sizeof(float4) * n)); BUILD_CHECK(hipMalloc(&chiB, sizeof(float4) * n));
-      BUILD_CHECK(hipMalloc(&flags, sizeof(unsigned long long) * n)); BUILD_CHECK(hipMalloc(&pos, sizeof(unsigned long long) * n));
-      BUILD_CHECK(hipMalloc(&totals, sizeof(unsigned long long)));
-      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, flags, pos, int(n), stream));
-      BUILD_CHECK(hipMalloc(&scanTemp, scanBytes));
-      hipLaunchKernelGGL(k_ploc_init, dim3(gridT), dim3(B), 0, stream, int(n), valsB, boxLo, boxHi, cidA, cloA, chiA);
+      BUILD_CHECK(cidA.alloc(n)); BUILD_CHECK(cidB.alloc(n)); BUILD_CHECK(nn.alloc(n));
+      BUILD_CHECK(cloA.alloc(n)); BUILD_CHECK(chiA.alloc(n));
+      BUILD_CHECK(cloB.alloc(n)); BUILD_CHECK(chiB.alloc(n));
+      BUILD_CHECK(flags.alloc(n)); BUILD_CHECK(pos.alloc(n));
+      BUILD_CHECK(totals.alloc(1));
+      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, flags.ptr, pos.ptr, int(n), stream));
+      BUILD_CHECK(scanTemp.alloc(scanBytes));
+      hipLaunchKernelGGL(k_ploc_init, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, cidA.ptr, cloA.ptr, chiA.ptr);
       BUILD_CHECK(hipGetLastError());
       int m = int(n), nodeBase = 0, rootRef = BVH_EMPTY;
-      while(m > 1 && ok)
+      while(m > 1)
       {
         const unsigned g = unsigned(m + B - 1) / B;
-        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, stream, m, cloA, chiA, nn);
-        hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, m, nn, flags);
-        BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp, scanBytes, flags, pos, m, stream));
-        hipLaunchKernelGGL(k_ploc_emit, dim3(g), dim3(B), 0, stream, m, nn, flags, pos, cidA, cloA, chiA, cidB, cloB, chiB, nodeBase, out.nodes, totals);
+        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, stream, m, cloA.ptr, chiA.ptr, nn.ptr);
+        hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, m, nn.ptr, flags.ptr);
+        BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp.ptr, scanBytes, flags.ptr, pos.ptr, m, stream));
+        hipLaunchKernelGGL(k_ploc_emit, dim3(g), dim3(B), 0, stream, m, nn.ptr, flags.ptr, pos.ptr, cidA.ptr, cloA.ptr, chiA.ptr, cidB.ptr, cloB.ptr, chiB.ptr, nodeBase, nodes.ptr, totals.ptr);
         BUILD_CHECK(hipGetLastError());
         unsigned long long t = 0;
-        BUILD_CHECK(hipMemcpyAsync(&t, totals, sizeof(t), hipMemcpyDeviceToHost, stream));
+        BUILD_CHECK(hipMemcpyAsync(&t, totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream));
         BUILD_CHECK(hipStreamSynchronize(stream));
         const int survivors = int(uint32_t(t)), merges = int(t >> 32);
         if(merges < 1 || survivors != m - merges)
         {
           err = "PLOC round made no progress";
-          ok  = false;
-          break;
+          return false;
         }
         nodeBase += merges;
         m = survivors;
         std::swap(cidA, cidB); std::swap(cloA, cloB); std::swap(chiA, chiB);
       }
-      if(!ok)
-        break;
-      BUILD_CHECK(hipMemcpy(&rootRef, cidA, sizeof(int), hipMemcpyDeviceToHost));
+      BUILD_CHECK(hipMemcpy(&rootRef, cidA.ptr, sizeof(int), hipMemcpyDeviceToHost));
       if(nodeBase != int(n) - 1 || rootRef != int(n) - 2)
       {
         err = "PLOC produced an inconsistent tree";
-        ok  = false;
-        break;
+        return false;
       }
-      hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB, trisTmp, out.tris);
+      hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, trisTmp.ptr, tris.ptr);
       BUILD_CHECK(hipGetLastError());
       BUILD_CHECK(hipStreamSynchronize(stream));
       out.root     = rootRef;
@@ -748,64 +727,44 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
     }
     else
     {
-    BUILD_CHECK(hipMalloc(&children, sizeof(int2) * (n - 1)));
-    BUILD_CHECK(hipMalloc(&parentInternal, sizeof(int) * (n - 1)));
-    BUILD_CHECK(hipMalloc(&parentLeaf, sizeof(int) * n));
-    BUILD_CHECK(hipMalloc(&nodeLo, sizeof(float4) * (n - 1)));
-    BUILD_CHECK(hipMalloc(&nodeHi, sizeof(float4) * (n - 1)));
-    BUILD_CHECK(hipMalloc(&arrive, sizeof(unsigned) * (n - 1)));
-    BUILD_CHECK(hipMalloc(&nodeCnt, sizeof(int) * (n - 1)));
-    BUILD_CHECK(hipMemsetAsync(arrive, 0, sizeof(unsigned) * (n - 1), stream));
-    hipLaunchKernelGGL(k_hierarchy, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), keysB, children, parentInternal, parentLeaf);
+    BUILD_CHECK(children.alloc(n - 1));
+    BUILD_CHECK(parentInternal.alloc(n - 1));
+    BUILD_CHECK(parentLeaf.alloc(n));
+    BUILD_CHECK(nodeLo.alloc(n - 1));
+    BUILD_CHECK(nodeHi.alloc(n - 1));
+    BUILD_CHECK(arrive.alloc(n - 1));
+    BUILD_CHECK(nodeCnt.alloc(n - 1));
+    BUILD_CHECK(hipMemsetAsync(arrive.ptr, 0, sizeof(unsigned) * (n - 1), stream));
+    hipLaunchKernelGGL(k_hierarchy, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), keysB.ptr, children.ptr, parentInternal.ptr, parentLeaf.ptr);
     BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_fit, dim3(gridT), dim3(B), 0, stream, int(n), valsB, boxLo, boxHi, children, parentInternal, parentLeaf, nodeLo, nodeHi, arrive, nodeCnt);
+    hipLaunchKernelGGL(k_fit, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, children.ptr, parentInternal.ptr, parentLeaf.ptr, nodeLo.ptr, nodeHi.ptr, arrive.ptr, nodeCnt.ptr);
     BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_emit_nodes, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), valsB, boxLo, boxHi, children, nodeLo, nodeHi, nodeCnt, out.nodes);
+    hipLaunchKernelGGL(k_emit_nodes, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, children.ptr, nodeLo.ptr, nodeHi.ptr, nodeCnt.ptr, nodes.ptr);
     BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB, trisTmp, out.tris);
+    hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, trisTmp.ptr, tris.ptr);
     BUILD_CHECK(hipGetLastError());
     BUILD_CHECK(hipStreamSynchronize(stream));
     out.root     = 0;
     out.numNodes = n - 1;
     }
   }
-  if(out.numNodes >= 3 && in.reinsertPasses > 0 && !reinsertBvh2(out.nodes, int(out.numNodes), out.root, in.reinsertPasses, in.reinsertRounds, stream, err, &out.reinsertMoves))
+  if(out.numNodes >= 3 && in.reinsertPasses > 0 && !reinsertBvh2(nodes.ptr, int(out.numNodes), out.root, in.reinsertPasses, in.reinsertRounds, stream, err, &out.reinsertMoves))
+    return false;
+  BUILD_CHECK(hipMemcpy(hb, bounds.ptr, sizeof(hb), hipMemcpyDeviceToHost));
+  for(int c = 0; c < 3; ++c)
   {
-    ok = false;
-    break;
+    auto toF = [](uint32_t u) {
+      uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+      float    f;
+      memcpy(&f, &v, 4);
+      return f;
+    };
+    out.centroidLo[c] = toF(hb[c]);
+    out.centroidHi[c] = toF(hb[3 + c]);
   }
-  BUILD_CHECK(hipMemcpy(hb, bounds, sizeof(hb), hipMemcpyDeviceToHost));
-  } while(0);
-  if(ok)
-  {
-    for(int c = 0; c < 3; ++c)
-    {
-      auto toF = [](uint32_t u) {
-        uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-        float    f;
-        memcpy(&f, &v, 4);
-        return f;
-      };
-      out.centroidLo[c] = toF(hb[c]);
-      out.centroidHi[c] = toF(hb[3 + c]);
-    }
-  }
-  if(!ok)
-  {
-    if(out.nodes) (void)hipFree(out.nodes);
-    if(out.tris) (void)hipFree(out.tris);
-    out.nodes = nullptr;
-    out.tris  = nullptr;
-  }
-  {
-    (void)hipFree(trisTmp); (void)hipFree(boxLo); (void)hipFree(boxHi); (void)hipFree(nodeLo); (void)hipFree(nodeHi);
-    (void)hipFree(bounds); (void)hipFree(valsA); (void)hipFree(valsB); (void)hipFree(keysA); (void)hipFree(keysB);
-    (void)hipFree(children); (void)hipFree(parentInternal); (void)hipFree(parentLeaf); (void)hipFree(arrive); (void)hipFree(nodeCnt); (void)hipFree(sortTemp);
-    (void)hipFree(cidA); (void)hipFree(cidB); (void)hipFree(nn); (void)hipFree(cloA); (void)hipFree(chiA); (void)hipFree(cloB); (void)hipFree(chiB);
-    (void)hipFree(flags); (void)hipFree(pos); (void)hipFree(totals); (void)hipFree(scanTemp);
-    (void)hipFree(splitArea); (void)hipFree(splitSum); (void)hipFree(splitCounts); (void)hipFree(splitOffsets); (void)hipFree(splitTemp);
-    return ok;
-  }
+  out.nodes = std::move(nodes);
+  out.tris  = std::move(tris);
+  return true;
 }
 
 }  // namespace pt

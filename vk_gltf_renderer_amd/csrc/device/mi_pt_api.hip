@@ -15,6 +15,7 @@
 
 #include "mi_pt.h"
 #include "bvh_refit.h"
+#include "dev_buf.h"
 #include "material_patch.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
@@ -39,35 +40,7 @@ int fail(int code, const std::string& msg)
       return fail(MI_PT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));                                       \
   } while(0)
 
-template <typename T>
-struct DevBuf
-{
-  T*     ptr   = nullptr;
-  size_t count = 0;
-  hipError_t alloc(size_t n)
-  {
-    release();
-    count = n;
-    if(n == 0)
-      return hipSuccess;
-    return hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
-  }
-  hipError_t upload(const T* src, size_t n)
-  {
-    hipError_t e = alloc(n);
-    if(e != hipSuccess || n == 0)
-      return e;
-    return hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice);
-  }
-  void release()
-  {
-    if(ptr)
-      (void)hipFree(ptr);
-    ptr   = nullptr;
-    count = 0;
-  }
-  ~DevBuf() { release(); }
-};
+using pt::DevBuf;
 
 enum TimedKernel { TK_GENERATE, TK_TRACE, TK_SORT, TK_SHADE, TK_SHADOW, TK_ACCUM, TK_PRIMARY, TK_SHADE_FIRST, TK_COUNT };
 
@@ -190,10 +163,10 @@ struct MiPt
   DevBuf<MiEnvAccel>          envAccel;
   DevBuf<pt::DevAlphaTri>     alphaTris;
   DevBuf<pt::DevShadeTri>     shadeTris;
-  float4*                     bvhNodes  = nullptr;
-  uint4*                      bvh8Nodes = nullptr;
+  DevBuf<float4>              bvhNodes;    // the BVH2 (bvhBuilder bit 0), 4 float4 per node ...
+  DevBuf<uint4>               bvh8Nodes;   // ... or the 8-wide BVH collapsed from it, 5 uint4 per node
   DevBuf<float>               bvh8Planes;  // the nodes' planes as floats for the packet walk (DevScene::bvh8Planes)
-  pt::DevTri*                 bvhTris   = nullptr;
+  DevBuf<pt::DevTri>          bvhTris;     // the triangle records, in the order of whichever of the two is resident
   bool                        wide      = true;
   pt::DevScene                scene{};
   bool                        hasAlpha = false, hasAlphaTest = false, hasVolumeScatter = false, simpleMaterials = true, hasTransmissive = false;
@@ -332,12 +305,6 @@ struct MiPt
 
   ~MiPt()
   {
-    if(bvhNodes)
-      (void)hipFree(bvhNodes);
-    if(bvhTris)
-      (void)hipFree(bvhTris);
-    if(bvh8Nodes)
-      (void)hipFree(bvh8Nodes);
     for(hipEvent_t e : eventPool)
       (void)hipEventDestroy(e);
     for(hipEvent_t e : fcDone)
@@ -639,22 +606,29 @@ int buildAcceleration(MiPt* pt)
     dropAcceleration(pt);
   return rc;
 }
+// The structure's arrays as the kernels see them (all null once they are released); the per-triangle shade and alpha records are made from
+// them afterwards (buildAccelerationOver)
+void publishAcceleration(MiPt* pt)
+{
+  pt::DevScene& S = pt->scene;
+  S.bvhNodes = pt->bvhNodes.ptr; S.bvh8Nodes = pt->bvh8Nodes.ptr; S.tris = pt->bvhTris.ptr;
+  S.bvh8Planes = pt->bvh8Nodes.ptr ? pt->bvh8Planes.ptr : nullptr;
+  S.shadeTris = nullptr;
+  S.alphaTris = nullptr;
+  pt->sceneDevDirty = true;
+}
 // The state a failed build or refit leaves: an EMPTY structure, no refit data, the error message kept.
 void dropAcceleration(MiPt* pt)
 {
   {
     const std::string why = g_lastError;  // (the frees below must not disturb the message)
     releaseRefitData(pt);
-    if(pt->bvhNodes) (void)hipFree(pt->bvhNodes);
-    if(pt->bvhTris) (void)hipFree(pt->bvhTris);
-    if(pt->bvh8Nodes) (void)hipFree(pt->bvh8Nodes);
-    pt->bvhNodes = nullptr; pt->bvhTris = nullptr; pt->bvh8Nodes = nullptr;
+    pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
     pt->bvh8Planes.release(); pt->shadeTris.release(); pt->alphaTris.release();
+    publishAcceleration(pt);
     pt::DevScene& S = pt->scene;
-    S.bvhNodes = nullptr; S.bvh8Nodes = nullptr; S.tris = nullptr; S.bvh8Planes = nullptr; S.shadeTris = nullptr; S.alphaTris = nullptr;
     S.numTris = 0; S.bvh8NumNodes = 0; S.bvhRoot = pt::BVH_EMPTY;
     pt->staticStats.bvhNodeCount = pt->staticStats.bvhTriangleCount = 0;
-    pt->sceneDevDirty = true;
     g_lastError = why;
   }
 }
@@ -714,7 +688,7 @@ bool residentWanted(const MiPt* pt)
 }
 bool residentInForce(const MiPt* pt)
 {
-  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refitLevels.empty() && pt->bvh8Nodes && pt->wide;
+  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refitLevels.empty() && pt->bvh8Nodes.ptr && pt->wide;
 }
 int buildAccelerationOver(MiPt* pt, bool resident);
 int buildAccelerationUnguarded(MiPt* pt)
@@ -755,10 +729,7 @@ int buildAccelerationOver(MiPt* pt, bool resident)
   pt->scene.nodes = pt->nodes.ptr;
 
   // release the previous structure (an update), then build
-  if(pt->bvhNodes) (void)hipFree(pt->bvhNodes);
-  if(pt->bvhTris) (void)hipFree(pt->bvhTris);
-  if(pt->bvh8Nodes) (void)hipFree(pt->bvh8Nodes);
-  pt->bvhNodes = nullptr; pt->bvhTris = nullptr; pt->bvh8Nodes = nullptr;
+  pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
   pt->refitCapable = false;
   if(pt->accelBuilds++ == pt->sw.failBuildAt && pt->sw.failBuildAt > 0)  // test hook (armed at mi_pt_create): this REbuild fails after the old structure is gone
     return fail(MI_PT_ERR_HIP, "BVH build failed: MI_PT_DIAG_FAIL_BUILD");
@@ -781,8 +752,6 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     std::string        err;
     if(!pt::buildBvh(in, bo, nullptr, err))
       return fail(MI_PT_ERR_HIP, "BVH build failed: " + err);
-    pt->bvhNodes = bo.nodes;
-    pt->bvhTris  = bo.tris;
     pt->scene.bvhRoot = bo.root;
     pt->scene.numTris = int(bo.numTris);
     pt->scene.bvh8NumNodes = 0;
@@ -802,24 +771,16 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       b8opt.sahCollapse = !pt->sw.collapseGreedy; b8opt.hostCollapse = pt->sw.hostCollapse;
       b8opt.keepRefit   = pt->accelMode != MI_PT_ACCEL_REBUILD;
       pt->refitCapable  = !pt->sw.hostCollapse && bo.numNodes > 0;  // (a one-reference scene takes the host collapse: bvh8.hip)
-      const bool built  = pt::buildBvh8(bo, b8, nullptr, err, b8opt);
-      // the refit data, owned from here on (the host collapse keeps none: its updates rebuild)
-      pt->refitSlotBox.ptr = b8.slotBox; pt->refitSlotBox.count = b8.slotBox ? b8.numTris : 0;
-      pt->refitNodeBox.ptr = b8.nodeBox; pt->refitNodeBox.count = b8.nodeBox ? b8.numNodes : 0;
-      if(!built)
-      {
-        if(b8.nodes)
-          (void)hipFree(b8.nodes);
-        if(b8.tris)
-          (void)hipFree(b8.tris);
+      if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
         return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
-      }
       // the wide structure owns its own triangle order; the BVH2 arrays are no longer needed
-      (void)hipFree(pt->bvhNodes);
-      (void)hipFree(pt->bvhTris);
-      pt->bvhNodes  = nullptr;
-      pt->bvhTris   = b8.tris;
-      pt->bvh8Nodes = b8.nodes;
+      bo.nodes.release();
+      bo.tris.release();
+      pt->bvhTris   = std::move(b8.tris);
+      pt->bvh8Nodes = std::move(b8.nodes);
+      // the refit data (the host collapse keeps none: its updates rebuild)
+      pt->refitSlotBox = std::move(b8.slotBox);
+      pt->refitNodeBox = std::move(b8.nodeBox);
       pt->scene.bvhRoot = 0;
       pt->scene.bvh8NumNodes = int(b8.numNodes);
       pt->staticStats.bvhNodeCount = b8.numNodes;
@@ -827,27 +788,27 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       if(!pt->sw.noPlanes)  // A/B switch of the packet walk's float planes
       {
         HIP_TRY(pt->bvh8Planes.alloc(size_t(b8.numNodes) * 48));
-        pt::launchBvh8Planes(b8.nodes, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
+        pt::launchBvh8Planes(pt->bvh8Nodes.ptr, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
         HIP_TRY(hipGetLastError());
       }
-      if(b8.slotBox && b8.nodeBox)
+      if(pt->refitSlotBox.ptr && pt->refitNodeBox.ptr)
       {
         // the refit data: the boxes the build filed the references under stay as they are (REFIT_HOME), the SAH cost of the tree as built.
         // The nodes are requantised once from the unions of those boxes (a BVH2 box may be looser than the union below it): the tree an
         // update refits back to the build's pose is then this one, byte for byte.
         HIP_TRY(pt->refitBuiltBox.alloc(b8.numTris));
-        HIP_TRY(hipMemcpy(pt->refitBuiltBox.ptr, b8.slotBox, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(pt->refitBuiltBox.ptr, pt->refitSlotBox.ptr, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
         HIP_TRY(pt->refitSah.alloc(b8.numNodes));
         HIP_TRY(pt->refitSahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
         HIP_TRY(pt->refitDirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
-        pt::launchRefitLevels(b8.nodes, b8.levels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+        pt::launchRefitLevels(pt->bvh8Nodes.ptr, b8.levels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
         if(pt->bvh8Planes.ptr)
-          pt::launchBvh8Planes(b8.nodes, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
+          pt::launchBvh8Planes(pt->bvh8Nodes.ptr, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
         HIP_TRY(hipGetLastError());
         if(int rc = readSahCost(pt, pt->sahAtBuild))
           return rc;
         pt->sahNow      = pt->sahAtBuild;
-        pt->refitLevels = b8.levels;
+        pt->refitLevels = std::move(b8.levels);
         pt->builtNodes  = pt->hostNodes;
         pt->primDirty.assign(pt->primTriangles.size(), 0);
         pt->primDeformed.assign(pt->primTriangles.size(), 0);
@@ -860,17 +821,19 @@ int buildAccelerationOver(MiPt* pt, bool resident)
         pt->refitNodeBox.release();
       }
     }
+    else
+    {
+      pt->bvhNodes = std::move(bo.nodes);
+      pt->bvhTris  = std::move(bo.tris);
+    }
   }
   if(resident && !pt->residentTree && hiddenTris > 0)  // no refit data came of it (a one-reference scene: bvh8.hip), so nothing could hide them
   {
     --pt->accelBuilds;
     return buildAccelerationOver(pt, false);
   }
+  publishAcceleration(pt);
   pt::DevScene& S = pt->scene;
-  S.bvhNodes = pt->bvhNodes; S.bvh8Nodes = pt->bvh8Nodes; S.tris = pt->bvhTris;
-  S.bvh8Planes = pt->bvh8Nodes ? pt->bvh8Planes.ptr : nullptr;
-  S.shadeTris = nullptr;
-  S.alphaTris = nullptr;
   if(S.numTris > 0)
   {
     HIP_TRY(pt->shadeTris.alloc(size_t(S.numTris)));
@@ -895,17 +858,16 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       if(!pt->hostVisible[n])
         dirty[n] = pt::REFIT_HIDDEN;
     HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris, pt->refitSlotBox.ptr,
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris.ptr, pt->refitSlotBox.ptr,
                         uint32_t(S.numTris), nullptr);
-    pt::launchRefitLevels(pt->bvh8Nodes, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+    pt::launchRefitLevels(pt->bvh8Nodes.ptr, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
     if(pt->bvh8Planes.ptr)
-      pt::launchBvh8Planes(pt->bvh8Nodes, uint32_t(S.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
+      pt::launchBvh8Planes(pt->bvh8Nodes.ptr, uint32_t(S.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
     HIP_TRY(hipGetLastError());
     if(int rc = readSahCost(pt, pt->sahNow))
       return rc;
     HIP_TRY(hipDeviceSynchronize());
   }
-  pt->sceneDevDirty = true;
   return MI_PT_OK;
 }
 
@@ -957,11 +919,11 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
     HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * numNodes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris, pt->refitSlotBox.ptr,
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris.ptr, pt->refitSlotBox.ptr,
                         uint32_t(pt->scene.numTris), nullptr);
-    pt::launchRefitLevels(pt->bvh8Nodes, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
+    pt::launchRefitLevels(pt->bvh8Nodes.ptr, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
     if(pt->bvh8Planes.ptr)
-      pt::launchBvh8Planes(pt->bvh8Nodes, uint32_t(pt->scene.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
+      pt::launchBvh8Planes(pt->bvh8Nodes.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
     HIP_TRY(hipGetLastError());
     if(int e = readSahCost(pt, pt->sahNow))
       return e;
@@ -999,7 +961,7 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
 // keeps the topology (`sameTopology`: primitives, materials and visibility unchanged), a full build otherwise.
 int updateAcceleration(MiPt* pt, bool sameTopology, const std::vector<uint8_t>& moved)
 {
-  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refitLevels.empty() && pt->bvh8Nodes && pt->wide)
+  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refitLevels.empty() && pt->bvh8Nodes.ptr && pt->wide)
     return refitAcceleration(pt, moved);
   return buildAcceleration(pt);
 }
@@ -1033,8 +995,7 @@ AlphaKey alphaKey(const MiGltfShadeMaterial& mat, const MiGltfTextureInfo* infos
 
 uint64_t refitBytes(const MiPt* pt)
 {
-  auto bytes = [](const auto& b) { return uint64_t(b.count) * sizeof(*b.ptr); };
-  return bytes(pt->refitSlotBox) + bytes(pt->refitBuiltBox) + bytes(pt->refitNodeBox) + bytes(pt->refitSah) + bytes(pt->refitSahPartial) + bytes(pt->refitDirty);
+  return pt->refitSlotBox.bytes() + pt->refitBuiltBox.bytes() + pt->refitNodeBox.bytes() + pt->refitSah.bytes() + pt->refitSahPartial.bytes() + pt->refitDirty.bytes();
 }
 
 // What a material bakes into the triangles of the instances that use it (MiPt::matInstFlags; reference: getInstanceFlag, src/gltf_scene_rtx.cpp:271-295) ...
@@ -1173,7 +1134,7 @@ int patchTriangleData(MiPt* pt, const std::vector<uint8_t>& flags, std::vector<u
     if(pt->matDirty.count != dirty.size())
       HIP_TRY(pt->matDirty.alloc(dirty.size()));
     HIP_TRY(hipMemcpy(pt->matDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris, hadRecords ? pt->alphaTris.ptr : nullptr, pt->shadeTris.ptr,
+    pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris.ptr, hadRecords ? pt->alphaTris.ptr : nullptr, pt->shadeTris.ptr,
                              uint32_t(S.numTris), nullptr);
     HIP_TRY(hipGetLastError());
   }
@@ -2830,21 +2791,17 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_memory: null argument");
   HIP_TRY(hipSetDevice(pt->device));
-  auto bytes = [](const auto& b) { return uint64_t(b.count) * sizeof(*b.ptr); };
-  const pt::DevScene& sc = pt->scene;
-  uint64_t scene = bytes(pt->materials) + bytes(pt->texInfos) + bytes(pt->nodes) + bytes(pt->prims) + bytes(pt->lights) + bytes(pt->textures) + bytes(pt->texels) + bytes(pt->texQuads)
-                   + bytes(pt->geometry) + bytes(pt->instFlags) + bytes(pt->srgbLut) + bytes(pt->envPixels) + bytes(pt->envAccel) + bytes(pt->alphaTris)
-                   + bytes(pt->shadeTris) + bytes(pt->texRefs) + bytes(pt->coreTex) + bytes(pt->bvh8Planes) + bytes(pt->deformPool) + bytes(pt->deformTasks)
-                   + bytes(pt->deformBlockTask) + bytes(pt->deformJoints) + bytes(pt->deformWeights) + refitBytes(pt) + bytes(pt->vmPrevPositions) + bytes(pt->vmPrims)
-                   + bytes(pt->vmDeformIDs);
-  // the acceleration structure is raw allocations: 64-B BVH2 nodes or 80-B BVH8 nodes + 48-B triangle records
-  scene += uint64_t(pt->staticStats.bvhNodeCount) * pt->staticStats.bvhNodeBytes + uint64_t(sc.numTris) * sizeof(pt::DevTri);
-  const uint64_t pathState = bytes(pt->pathArrays) + bytes(pt->optThroughput) + bytes(pt->optMisc) + bytes(pt->optMedium) + bytes(pt->optPixelSum) + bytes(pt->optGuides)
-                             + bytes(pt->optShadowAux2) + bytes(pt->queueMem) + bytes(pt->queuePayload) + bytes(pt->candPool) + bytes(pt->candLists);
-  const uint64_t renderer = pathState + bytes(pt->firstHit) + bytes(pt->accumOwn)
-                            + bytes(pt->albedo) + bytes(pt->normal) + bytes(pt->denoiseA) + bytes(pt->denoiseB) + bytes(pt->tonemapped) + bytes(pt->depth)
-                            + bytes(pt->selection) + bytes(pt->ownedTiles) + bytes(pt->sceneDev) + bytes(pt->fcRing) + bytes(pt->stats)
-                            + bytes(pt->motion) + bytes(pt->history) + bytes(pt->prevObjectToWorld) + bytes(pt->firstHitTri);
+  const uint64_t scene = pt->materials.bytes() + pt->texInfos.bytes() + pt->nodes.bytes() + pt->prims.bytes() + pt->lights.bytes() + pt->textures.bytes() + pt->texels.bytes() + pt->texQuads.bytes()
+                         + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->alphaTris.bytes()
+                         + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deformPool.bytes() + pt->deformTasks.bytes()
+                         + pt->deformBlockTask.bytes() + pt->deformJoints.bytes() + pt->deformWeights.bytes() + refitBytes(pt) + pt->vmPrevPositions.bytes() + pt->vmPrims.bytes()
+                         + pt->vmDeformIDs.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
+  const uint64_t pathState = pt->pathArrays.bytes() + pt->optThroughput.bytes() + pt->optMisc.bytes() + pt->optMedium.bytes() + pt->optPixelSum.bytes() + pt->optGuides.bytes()
+                             + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
+  const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
+                            + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
+                            + pt->selection.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
   out->sceneBytes       = scene;

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_buf.h"
 #include "pt_scene.h"
 
 namespace pt {
@@ -27,8 +28,8 @@ struct BvhBuildInput
 };
 struct BvhBuildOutput
 {
-  float4*  nodes    = nullptr;  // device, 4 float4 per node
-  DevTri*  tris     = nullptr;  // device, Morton order (leaf reference ~i = triangle i of this array)
+  DevBuf<float4> nodes;  // 4 float4 per node
+  DevBuf<DevTri> tris;   // Morton order (leaf reference ~i = triangle i of this array)
   uint32_t numNodes = 0, numTris = 0;   // numTris = REFERENCES: a pre-split triangle appears once per reference (each a full copy of its record)
   uint32_t sceneTris = 0;               // triangles the references were made from
   int      root     = 0;
@@ -42,14 +43,13 @@ struct RefitBox;  // bvh_refit.h
 // 8-wide compressed BVH collapsed from the BVH2 above (bvh8.hip)
 struct Bvh8Output
 {
-  uint4*   nodes    = nullptr;  // device, 5 uint4 per node
-  DevTri*  tris     = nullptr;  // device, node order (triangles of a node's leaf children are contiguous)
+  DevBuf<uint4>  nodes;  // 5 uint4 per node
+  DevBuf<DevTri> tris;   // node order (triangles of a node's leaf children are contiguous)
   uint32_t numNodes = 0, numTris = 0;
-  // the refit data (Bvh8Options::keepRefit, device collapse only; the caller owns and frees them): per triangle slot the box the builder
+  // the refit data (Bvh8Options::keepRefit, device collapse only): per triangle slot the box the builder
   // filed that reference under, per node room for its box (left for k_refit_level to fill), and the start of every level of the
   // breadth-first node array (+ numNodes at the end)
-  RefitBox*             nodeBox = nullptr;
-  RefitBox*             slotBox = nullptr;
+  DevBuf<RefitBox>      nodeBox, slotBox;
   std::vector<uint32_t> levels;
 };
 struct Bvh8Options  // (MI_PT_COLLAPSE / MI_PT_HOST_COLLAPSE, read and validated once in mi_pt_create: RunSwitches)
