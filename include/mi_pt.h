@@ -471,6 +471,66 @@ MI_PT_API int mi_pt_read_first_hit_triangle(MiPt* pt, uint32_t* hostPrimTriB1B2)
  * MI_PT_ERR_ARGUMENT for a render primitive the deformation tables do not deform. */
 MI_PT_API int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Ray queries and picking against the resident scene (replaces nvvk::RayPicker over the TLAS: reference src/ui_renderer.cpp:95-150).
+ * The rays walk the acceleration structure the frames walk, in its CURRENT state: the pose after mi_pt_update_deformation, the tree after
+ * a refit, the visibility and material ids of resident mode.
+ *  - Geometry: every triangle of every visible render node, taken as OPAQUE, with no face culling -- the ray flags of the reference's
+ *    selection ray (RAY_FLAG_FORCE_OPAQUE, pathtrace_functions.h.slang:813-820) and of the selection pass behind mi_pt_read_selection.
+ *    Alpha-tested and transmissive surfaces are hit like any other; hidden nodes are never hit.  Alpha-aware queries are out of scope.
+ *  - Acceptance: a triangle is accepted iff the walks' ray / triangle test accepts it and tMin < t < tMax.  t is in units of |direction|
+ *    (the direction need not be normalised).  Nothing behind the origin is hit: a negative tMin acts as 0.
+ *  - MI_PT_QUERY_CLOSEST: the smallest t wins, exact ties go to the smaller (renderNode, triangle) -- the rule of the closest-hit walks.
+ *    The record does not depend on the tree: BVH2, the 8-wide tree, a refitted and a freshly built tree return the same 64 bytes.
+ *  - MI_PT_QUERY_ANY: the walk stops at the first accepted triangle.  MI_PT_HIT is set iff CLOSEST would set it; WHICH accepted triangle
+ *    the record describes is unspecified.
+ *  - A miss: flags == 0, renderNode == -1, every other field zero.
+ *  - An invalid ray (a non-finite origin or direction component, a zero direction, NaN tMin or tMax) is not walked: flags ==
+ *    MI_PT_HIT_INVALID_RAY, renderNode == -1, everything else zero.  The call still succeeds (device rays cannot be validated on the host).
+ *  - MI_PT_HIT_FRONT_FACE: the ray met the side the triangle's OBJECT-space winding faces, the bit the shade kernel derives for the same hit:
+ *    the sign of the world-space determinant of the ray / triangle test (positive = the world-space winding faces the ray), inverted for a
+ *    render node whose objectToWorld mirrors (det < 0: world-space winding is the mirror of object-space winding).
+ *  - b1, b2, triangle: of the WHOLE source triangle, also where the tree holds pre-split references (as mi_pt_read_first_hit_triangle).
+ *  - materialID: the material the resident records shade the triangle with (max(0, GltfRenderNode::materialID) after variants / patches).
+ * Queries leave MiPtStats and the frame timing untouched.  Like every entry point they flush a pending frame queue first. */
+typedef struct MiPtRay /* 32 B */
+{
+  float origin[3];
+  float tMin;
+  float direction[3];
+  float tMax;
+} MiPtRay;
+typedef struct MiPtRayHit /* 64 B */
+{
+  float    t;            /* in units of |direction|; zero on a miss */
+  float    b1, b2;       /* barycentrics of vertices 1 and 2 of the whole source triangle (b0 = 1 - b1 - b2) */
+  uint32_t flags;        /* MI_PT_HIT_* */
+  int32_t  renderNode;   /* -1 on a miss */
+  int32_t  renderPrimID;
+  uint32_t triangle;     /* index inside the render primitive */
+  int32_t  materialID;
+  float    position[3];  /* fma(t, direction, origin) per component */
+  float    reserved0;
+  float    normal[3];    /* unit geometric normal of the world-space triangle, turned to face the ray (dot(normal, direction) <= 0) */
+  float    reserved1;
+} MiPtRayHit;
+enum { MI_PT_HIT = 1, MI_PT_HIT_FRONT_FACE = 2, MI_PT_HIT_INVALID_RAY = 4 };
+enum { MI_PT_QUERY_CLOSEST = 0, MI_PT_QUERY_ANY = 1 };
+/* numRays rays from host memory, numRays records into host memory; synchronises.  The staging buffers are allocated on the first call and
+ * grown, never before: an instance that never queries holds no memory for it; afterwards they count in MiPtMemory::rendererBytes.
+ * numRays == 0 succeeds.  MI_PT_ERR_ARGUMENT: a negative count, a NULL pointer with a positive count, an unknown mode. */
+MI_PT_API int mi_pt_query_rays(MiPt* pt, const MiPtRay* hostRays, int numRays, int mode, MiPtRayHit* hostHits);
+/* The same over device memory (numRays x 32 B in, numRays x 64 B out, 16-byte aligned; e.g. torch tensors), asynchronous on hipStream
+ * (NULL = the default stream); allocates nothing.  The scene must not be updated while the query is in flight (the update calls synchronise
+ * the device, so a caller that issues both from one thread need not care). */
+MI_PT_API int mi_pt_query_rays_device(MiPt* pt, const void* deviceRays, int numRays, int mode, void* deviceHits, void* hipStream);
+/* Picking: pixelXY holds numPixels (x, y) pairs in continuous pixel coordinates under the current frame info and size; the ray of (x, y) is the
+ * camera ray getRay(floor(xy), frac(xy)) with tMin = 0, tMax = infinity, CLOSEST -- so (px + 0.5, py + 0.5) is the selection ray of pixel
+ * (px, py), and renderNode + 1 there is what mi_pt_read_selection holds after a first frame.  The tile partition does not matter (every rank
+ * holds the whole scene).  MI_PT_ERR_STATE before mi_pt_resize / mi_pt_set_frame_info; a pixel outside the image (or not finite) is
+ * MI_PT_ERR_ARGUMENT, with nothing written.  Synchronises; stages like mi_pt_query_rays. */
+MI_PT_API int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHits);
+
 /* device address of the last denoise result (NULL before the first), valid until the next denoise / resize */
 MI_PT_API const void* mi_pt_denoised_device_ptr(MiPt* pt);
 
@@ -515,7 +575,8 @@ MI_PT_API const char* mi_pt_version(void);
  * 8: MiPtAccelInfo and the refit entry points (mi_pt_set_accel_update, mi_pt_get_accel_info).
  * 9: MiPtTemporalParams and the motion / temporal entry points (mi_pt_read_first_hit, mi_pt_set_temporal, mi_pt_read_motion, mi_pt_denoise_temporal,
  *    mi_pt_reset_history).  (Still 9: mi_pt_set_vertex_motion, mi_pt_read_first_hit_triangle, mi_pt_read_previous_positions -- new entry points, no
- *    struct a caller allocates changed.) */
+ *    struct a caller allocates changed.  Still 9: MiPtRay / MiPtRayHit and mi_pt_query_rays, mi_pt_query_rays_device, mi_pt_pick -- new types and
+ *    entry points, no struct a caller already allocates changed.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

@@ -159,6 +159,15 @@ class MiPtTemporalParams(C.Structure):
                 ("maxHistory", f32), ("normalCos", f32), ("depthTolerance", f32)]
 
 
+class MiPtRay(C.Structure):
+    _fields_ = [("origin", f32 * 3), ("tMin", f32), ("direction", f32 * 3), ("tMax", f32)]
+
+
+class MiPtRayHit(C.Structure):
+    _fields_ = [("t", f32), ("b1", f32), ("b2", f32), ("flags", u32), ("renderNode", i32), ("renderPrimID", i32), ("triangle", u32),
+                ("materialID", i32), ("position", f32 * 3), ("reserved0", f32), ("normal", f32 * 3), ("reserved1", f32)]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -171,6 +180,8 @@ assert C.sizeof(MiGltfShadeMaterial) == 288
 assert C.sizeof(MiSceneFrameInfo) == 396
 assert C.sizeof(MiPtAccelInfo) == 64
 assert C.sizeof(MiPtAccelResidentInfo) == 40
+assert C.sizeof(MiPtRay) == 32
+assert C.sizeof(MiPtRayHit) == 64
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
@@ -179,6 +190,8 @@ MI_PT_DEFORM_DEFER_BUILD = 1
  MI_SCENE_CHANGED_VISIBILITY) = 1, 2, 4, 8, 16, 32
 MI_PT_ACCEL_REBUILD, MI_PT_ACCEL_REFIT, MI_PT_ACCEL_AUTO = 0, 1, 2
 MI_PT_ACCEL_LAST_BUILD, MI_PT_ACCEL_LAST_REFIT = 0, 1
+MI_PT_HIT, MI_PT_HIT_FRONT_FACE, MI_PT_HIT_INVALID_RAY = 1, 2, 4
+MI_PT_QUERY_CLOSEST, MI_PT_QUERY_ANY = 0, 1
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
@@ -308,6 +321,9 @@ PT_SYMBOLS = {
     "mi_pt_set_vertex_motion": (i32, [VP, i32]),
     "mi_pt_read_first_hit_triangle": (i32, [VP, P(u32)]),
     "mi_pt_read_previous_positions": (i32, [VP, i32, P(f32)]),
+    "mi_pt_query_rays": (i32, [VP, P(MiPtRay), i32, i32, P(MiPtRayHit)]),
+    "mi_pt_query_rays_device": (i32, [VP, VP, i32, i32, VP, VP]),
+    "mi_pt_pick": (i32, [VP, P(f32), i32, P(MiPtRayHit)]),
 }
 
 

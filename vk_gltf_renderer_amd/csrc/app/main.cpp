@@ -19,7 +19,7 @@ int main(int argc, char** argv)
   ParameterRegistry registry;
   std::string       sceneFile, hdrFile = "std_env.hdr", outputFile;
   int               size[2] = {1280, 720};
-  std::string       sequenceFile, sequenceString, saveSelftest;
+  std::string       sequenceFile, sequenceString, saveSelftest, pick;
   int               frames = 1, framesInFlight = 32;
   bool              headless = false, vvl = false, selftest = false, benchmark = false;
   registry.add("scenefile", "Input scene filename (.gltf / .glb)", &sceneFile);
@@ -29,6 +29,7 @@ int main(int argc, char** argv)
   registry.add("frames", "Number of frames to render in headless mode", &frames);
   registry.add("headless", "Run without a window", &headless, true);
   registry.add("framesInFlight", "Headless: app frames traced as one set of launches (same image as one by one; 1 = like the reference)", &framesInFlight);
+  registry.add("pick", "Headless: \"x y\" in continuous pixel coordinates; after the last frame, pick there and print one PICK {...} line", &pick);
   registry.add("benchmark", "Benchmark mode: run the scripted sequences of --sequencefile / --sequencestring", &benchmark);
   registry.add("sequencefile", "Benchmark script (.cfg) with SEQUENCE blocks", &sequenceFile);
   registry.add("sequencestring", "Benchmark script given on the command line", &sequenceString);
@@ -138,6 +139,20 @@ int main(int argc, char** argv)
     f += done;
   }
   app.onLastHeadlessFrame(uint32_t(frames));
+  if(!pick.empty())
+  {
+    // what the reference logs after a click in the viewport (src/ui_renderer.cpp:95-150: nvvk::RayPicker over the TLAS), from mi_pt_pick
+    float      xy[2] = {0.0f, 0.0f};
+    MiPtRayHit hit{};
+    if(sscanf(pick.c_str(), "%f %f", &xy[0], &xy[1]) != 2 || !app.pathTracer().handle() || mi_pt_pick(app.pathTracer().handle(), xy, 1, &hit) != MI_PT_OK)
+    {
+      fprintf(stderr, "--pick \"%s\" failed: %s\n", pick.c_str(), app.pathTracer().handle() ? mi_pt_last_error() : "no renderer");
+      return 1;
+    }
+    // (%.9g: a float survives the round trip through the text)
+    printf("PICK {\"x\": %.9g, \"y\": %.9g, \"hit\": %s, \"renderNode\": %d, \"renderPrimID\": %d, \"triangle\": %u, \"position\": [%.9g, %.9g, %.9g], \"distance\": %.9g}\n",
+           xy[0], xy[1], (hit.flags & MI_PT_HIT) ? "true" : "false", hit.renderNode, hit.renderPrimID, hit.triangle, hit.position[0], hit.position[1], hit.position[2], hit.t);
+  }
   if(app.pathTracer().collectsCounters() && app.pathTracer().handle())
   {
     MiPtStats st{};

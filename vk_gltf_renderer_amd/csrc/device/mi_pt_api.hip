@@ -286,6 +286,9 @@ struct MiPt
   float4*                 accum = nullptr;  // accumOwn.ptr or caller-bound memory
   DevBuf<float>           depth;
   DevBuf<uint32_t>        selection;
+  // ray queries and picking (mi_pt_query_rays, mi_pt_pick): staging of the host forms, allocated by the first such call and grown, never before
+  DevBuf<MiPtRay>         queryRays;  // (mi_pt_pick stages its pixel positions here: 8 of the 32 bytes per ray)
+  DevBuf<MiPtRayHit>      queryHits;
   DevBuf<pt::StatCounters> stats;
   bool                    collectCounters = false;
   bool                    timingEnabled   = false;
@@ -2477,6 +2480,81 @@ int mi_pt_read_selection(MiPt* pt, uint32_t* host)
   HIP_TRY(hipMemcpy(host, pt->selection.ptr, size_t(pt->width) * size_t(pt->height) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
+// ---- ray queries and picking (query.hip) --------------------------------------------------------------------------------------------------------
+namespace {
+int queryStaging(MiPt* pt, size_t n)
+{
+  if(n > pt->queryRays.count)
+    HIP_TRY(pt->queryRays.alloc(n));
+  if(n > pt->queryHits.count)
+    HIP_TRY(pt->queryHits.alloc(n));
+  return MI_PT_OK;
+}
+bool queryModeKnown(int mode) { return mode == MI_PT_QUERY_CLOSEST || mode == MI_PT_QUERY_ANY; }
+}  // namespace
+
+int mi_pt_query_rays(MiPt* pt, const MiPtRay* hostRays, int numRays, int mode, MiPtRayHit* hostHits)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || numRays < 0 || !queryModeKnown(mode) || (numRays > 0 && (!hostRays || !hostHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays: bad arguments");
+  if(numRays == 0)
+    return MI_PT_OK;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(int rc = queryStaging(pt, size_t(numRays)))
+    return rc;
+  HIP_TRY(hipMemcpy(pt->queryRays.ptr, hostRays, size_t(numRays) * sizeof(MiPtRay), hipMemcpyHostToDevice));
+  pt::launchQueryRays(pt->scene, pt->wide, mode == MI_PT_QUERY_ANY, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, size_t(numRays) * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+int mi_pt_query_rays_device(MiPt* pt, const void* deviceRays, int numRays, int mode, void* deviceHits, void* hipStream)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || numRays < 0 || !queryModeKnown(mode) || (numRays > 0 && (!deviceRays || !deviceHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device: bad arguments");
+  if(numRays > 0 && ((reinterpret_cast<uintptr_t>(deviceRays) | reinterpret_cast<uintptr_t>(deviceHits)) & 15u))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device: rays and hits must be 16-byte aligned");
+  if(numRays == 0)
+    return MI_PT_OK;
+  HIP_TRY(hipSetDevice(pt->device));
+  pt::launchQueryRays(pt->scene, pt->wide, mode == MI_PT_QUERY_ANY, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays), static_cast<MiPtRayHit*>(deviceHits),
+                      reinterpret_cast<hipStream_t>(hipStream));
+  HIP_TRY(hipGetLastError());
+  return MI_PT_OK;
+}
+int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHits)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || numPixels < 0 || (numPixels > 0 && (!pixelXY || !hostHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick: bad arguments");
+  if(pt->width <= 0 || !pt->haveFrameInfo)
+    return fail(MI_PT_ERR_STATE, "mi_pt_pick: call mi_pt_resize and mi_pt_set_frame_info first");
+  for(int i = 0; i < numPixels; ++i)
+  {
+    const float x = pixelXY[2 * i], y = pixelXY[2 * i + 1];
+    if(!(x >= 0.0f && x < float(pt->width) && y >= 0.0f && y < float(pt->height)))  // (NaN fails too)
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick: pixel " + std::to_string(i) + " lies outside the image");
+  }
+  if(numPixels == 0)
+    return MI_PT_OK;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(int rc = queryStaging(pt, size_t(numPixels)))
+    return rc;
+  HIP_TRY(hipMemcpy(pt->queryRays.ptr, pixelXY, size_t(numPixels) * sizeof(float2), hipMemcpyHostToDevice));
+  pt::FrameConsts fc;
+  memset(&fc, 0, sizeof(fc));
+  fc.frameInfo = pt->frameInfo;
+  fc.width     = pt->width;
+  fc.height    = pt->height;
+  pt::launchPickRays(pt->scene, fc, pt->wide, reinterpret_cast<const float2*>(pt->queryRays.ptr), uint32_t(numPixels), pt->queryHits.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, size_t(numPixels) * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
 int mi_pt_read_depth(MiPt* pt, float* host)
 {
   FLUSH_PENDING(pt);
@@ -2800,7 +2878,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
                             + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));

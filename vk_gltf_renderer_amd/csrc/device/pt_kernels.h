@@ -50,6 +50,11 @@ void launchTraceShadow(const LaunchCtx& c, int nxt);  // nxt: active queue the p
 void launchFlushSurvivors(const LaunchCtx& c, int cur);  // cur: the active queue the last shade launch appended to (paths alive when the bounce loop stopped)
 void launchFinishSample(const LaunchCtx& c, int sampleIndex, float4* accum, float* depth, float4* albedo, float4* normal);
 void launchSelection(const LaunchCtx& c, uint32_t* selection);
+// ray queries and picking (query.hip, pt_query.h): one ray per lane over the resident structure (`wide`: the 8-wide tree), every triangle opaque, no
+// culling; `any`: stop at the first accepted triangle.  rays / xy / hits are device memory, 16 / 8 / 16-byte aligned.  launchPickRays forms ray i as
+// the camera ray of the continuous pixel position xy[i] under fc.frameInfo / fc.width / fc.height (nothing else of fc is read)
+void launchQueryRays(const DevScene& scene, bool wide, bool any, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
+void launchPickRays(const DevScene& scene, const FrameConsts& fc, bool wide, const float2* xy, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
 
 // a-trous edge-avoiding wavelet filter (denoise.hip)
 void launchAtrous(const float4* in, float4* out, const float4* albedo, const float4* normal, int width, int height, int step, float sigmaColor,

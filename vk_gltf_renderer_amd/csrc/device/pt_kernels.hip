@@ -13,6 +13,7 @@
 #include "pt_shading.h"
 #include "pt_bvh.h"
 #include "pt_bvh8.h"
+#include "pt_camera.h"
 #include "pt_packet.h"
 #include "pt_feed.h"
 #include "pt_visualize.h"
@@ -152,25 +153,7 @@ PT_DEV bool slotToPixel(const FrameConsts& fc, const uint32_t* ownedTiles, uint3
   return px < fc.width && py < fc.height;
 }
 
-// ---- camera (pathtrace_functions.h.slang:784-811, gltf_pathtrace.slang:502-529) ------------------------------------------
-PT_DEV void getRay(const FrameConsts& fc, f2 samplePos, f2 offset, f3& origin, f3& direction)
-{
-  const MiSceneFrameInfo& fi = fc.frameInfo;
-  // (IEEE division / square root whatever the compile options -- divExact, normalizeExact: camera rays agree with the oracle bit for bit)
-  f2 clip = mk2(divExact(samplePos.x + offset.x, float(fc.width)) * 2.0f - 1.0f, divExact(samplePos.y + offset.y, float(fc.height)) * 2.0f - 1.0f);
-  f4 view = mulFull(fi.projInv, mk4(clip.x, clip.y, -1.0f, 1.0f));
-  view    = mk4(divExact(view.x, view.w), divExact(view.y, view.w), divExact(view.z, view.w), divExact(view.w, view.w));
-  if(hasFlag(fi.flags, MI_SCENE_IS_ORTHOGRAPHIC))
-  {
-    origin    = xyz(mulFull(fi.viewInv, view));
-    direction = normalizeExact(xyz(mulFull(fi.viewInv, mk4(0, 0, -1, 0))));
-  }
-  else
-  {
-    origin    = mk3(fi.viewInv[12], fi.viewInv[13], fi.viewInv[14]);
-    direction = normalizeExact(xyz(mulFull(fi.viewInv, view)) - origin);
-  }
-}
+// ---- camera: getRay (pt_camera.h, shared with query.hip) ---------------------------------------------------------------
 
 PT_DEV uint4 packMedium(f3 ext, f3 sc, float g)
 {

@@ -1,0 +1,100 @@
+// Ray queries against the resident scene (mi_pt_query_rays / mi_pt_query_rays_device / mi_pt_pick, include/mi_pt.h): everything per ray that
+// is not the walk -- ray validation, the acceptance test, the closest-hit rule and the hit record.  Plain PT_DEV code: query.hip runs it per
+// lane, tests/host_shim/query_on_host.cpp compiles it for the CPU.
+#pragma once
+#include "pt_bvh.h"
+
+namespace pt {
+
+static_assert(sizeof(MiPtRay) == 32 && sizeof(MiPtRayHit) == 64, "the query records are 32 and 64 bytes (include/mi_pt.h)");
+
+// A ray the walk can take: finite origin and direction, a direction that is not zero, bounds that are not NaN (infinite bounds are fine).
+// Denormal direction components are accepted: makeRaySetup replaces what it cannot invert by +-1e-30.
+PT_DEV bool queryRayValid(const MiPtRay& ray)
+{
+  const f3   o = mk3(ray.origin), d = mk3(ray.direction);
+  const bool nonZero = d.x != 0.0f || d.y != 0.0f || d.z != 0.0f;
+  const bool bounds  = ray.tMin == ray.tMin && ray.tMax == ray.tMax;  // (not NaN)
+  return isFinite3(o) && isFinite3(d) && nonZero && bounds;
+}
+// Nothing behind the origin is hit (the node tests clip at t = 0): a negative tMin acts as 0.
+PT_DEV float queryTMin(float tMin) { return fmaxf(tMin, 0.0f); }
+// The open interval: a hit AT a bound is not accepted.
+PT_DEV bool queryAccept(float t, float tMin, float tMax) { return t > tMin && t < tMax; }
+
+struct QueryBest
+{
+  float    t, u, v;
+  int      tri;  // index into DevScene::tris, -1 = nothing yet
+  uint32_t rnode, prim;
+  bool     front;  // TriHit::front: the world-space winding faces the ray
+};
+PT_DEV QueryBest queryNoHit(float tMax)
+{
+  QueryBest b;
+  b.t = tMax; b.u = b.v = 0.0f; b.tri = -1; b.rnode = b.prim = 0xffffffffu; b.front = false;
+  return b;
+}
+// RAY_FLAG_FORCE_OPAQUE, no culling (k_selection's test): the triangle is a candidate iff intersectTri accepts it and tMin < t < tMax; among
+// candidates the smallest t wins, exact ties go to the smaller (renderNode, triangle).  Returns whether the triangle was accepted at all.
+PT_DEV bool queryTestTri(const DevScene& sc, const RaySetup& r, int triIndex, float tMin, float tMax, QueryBest& best)
+{
+  const DevTri T = sc.tris[triIndex];
+  TriHit       h;
+  if(!intersectTri(xyz(T.a), xyz(T.b), xyz(T.c), r.org, r.dir, h) || !queryAccept(h.t, tMin, tMax))
+    return false;
+  const uint32_t rnode = __float_as_uint(T.a.w), prim = __float_as_uint(T.b.w);
+  if(best.tri < 0 || h.t < best.t || (h.t == best.t && (rnode < best.rnode || (rnode == best.rnode && prim < best.prim))))
+  {
+    best.t = h.t; best.u = h.u; best.v = h.v; best.tri = triIndex; best.rnode = rnode; best.prim = prim; best.front = h.front;
+  }
+  return true;
+}
+
+PT_DEV MiPtRayHit queryMiss(uint32_t flags)
+{
+  MiPtRayHit hit;
+  memset(&hit, 0, sizeof(hit));
+  hit.flags      = flags;
+  hit.renderNode = -1;
+  return hit;
+}
+// The record of an accepted hit: t, u, v and `front` as intersectTri returned them for triangle slot triIndex.
+PT_DEV MiPtRayHit fillHit(const DevScene& sc, int triIndex, float t, float u, float v, bool front, const MiPtRay& ray)
+{
+#pragma clang fp contract(off)
+  const DevTri      T = sc.tris[triIndex];
+  const DevShadeTri S = sc.shadeTris[triIndex];
+  MiPtRayHit        hit;
+  memset(&hit, 0, sizeof(hit));
+  hit.t  = t;
+  hit.b1 = u;
+  hit.b2 = v;
+  // facing is decided in object space, like the walks' culling and the shade kernel's geometric normal (pt_shade_body.h, getHitState: the
+  // object-space normal through worldToObject^T): TriHit::front is the WORLD-space winding, which a mirroring instance (INST_FLIP_FACING) inverts
+  const bool frontFace = front != ((__float_as_uint(T.c.w) & INST_FLIP_FACING) != 0u);
+  hit.flags        = MI_PT_HIT | (frontFace ? MI_PT_HIT_FRONT_FACE : 0u);
+  hit.renderNode   = int32_t(S.rnode);
+  hit.renderPrimID = S.renderPrimID;
+  hit.triangle     = S.prim;
+  hit.materialID   = S.materialID;
+  hit.position[0]  = __fmaf_rn(t, ray.direction[0], ray.origin[0]);
+  hit.position[1]  = __fmaf_rn(t, ray.direction[1], ray.origin[1]);
+  hit.position[2]  = __fmaf_rn(t, ray.direction[2], ray.origin[2]);
+  // unit geometric normal of the world-space triangle; the edges are brought to unit scale first so that neither a tiny nor a huge triangle
+  // leaves the range of the squared length
+  f3          e1 = xyz(T.b), e2 = xyz(T.c);
+  const float m  = fmaxf(fmaxf(fmaxf(fabsf(e1.x), fabsf(e1.y)), fmaxf(fabsf(e1.z), fabsf(e2.x))), fmaxf(fabsf(e2.y), fabsf(e2.z)));
+  const float s  = divExact(1.0f, m);
+  e1 = e1 * s;
+  e2 = e2 * s;
+  f3 n = normalizeExact(crossFma(e1, e2));
+  if(dotFma(n, mk3(ray.direction)) > 0.0f)
+    n = -n;
+  hit.normal[0] = n.x;
+  hit.normal[1] = n.y;
+  hit.normal[2] = n.z;
+  return hit;
+}
+
+}  // namespace pt

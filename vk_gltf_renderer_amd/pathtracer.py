@@ -14,6 +14,13 @@ import numpy as np
 from . import _capi as capi
 
 
+# MiPtRayHit (include/mi_pt.h) as a structured numpy record: 64 bytes
+HIT_DTYPE = np.dtype([("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("flags", "<u4"), ("renderNode", "<i4"), ("renderPrimID", "<i4"), ("triangle", "<u4"),
+                      ("materialID", "<i4"), ("position", "<f4", (3,)), ("reserved0", "<f4"), ("normal", "<f4", (3,)), ("reserved1", "<f4")])
+assert HIT_DTYPE.itemsize == 64
+_QUERY_MODES = {"closest": capi.MI_PT_QUERY_CLOSEST, "any": capi.MI_PT_QUERY_ANY}
+
+
 class MiError(RuntimeError):
     pass
 
@@ -348,6 +355,38 @@ class PathTracer:
         out = np.empty((self.height, self.width), dtype=np.uint32)
         _check_pt(self._l.mi_pt_read_selection(self._p, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
+
+    def query_rays(self, rays, mode="closest", stream=None):
+        """Rays against the resident scene (mi_pt_query_rays): every triangle of every visible render node, opaque, no culling.  `rays`: (n, 8)
+        float32 rows of origin.xyz, tMin, direction.xyz, tMax; mode "closest" or "any" (include/mi_pt.h has the semantics).  A numpy array
+        returns a structured array of HIT_DTYPE records (synchronises).  A torch tensor on this instance's device goes through the device form
+        and returns an (n, 64) uint8 tensor of the same records, asynchronous on `stream` (default: torch's current stream)."""
+        m = _QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous()):
+                raise ValueError("query_rays: a contiguous (n, 8) float32 device tensor is required")
+            hits = torch.empty((rays.shape[0], 64), dtype=torch.uint8, device=rays.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check_pt(self._l.mi_pt_query_rays_device(self._p, C.c_void_p(rays.data_ptr()), int(rays.shape[0]), m, C.c_void_p(hits.data_ptr()),
+                                                      C.c_void_p(stream or 0)))
+            return hits
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("query_rays: an (n, 8) float32 array is required")
+        hits = np.zeros(rays.shape[0], HIT_DTYPE)
+        _check_pt(self._l.mi_pt_query_rays(self._p, rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), int(rays.shape[0]), m,
+                                           hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+        return hits
+
+    def pick(self, xy):
+        """The closest hits of the camera rays through the continuous pixel positions `xy` ((n, 2) or one (x, y); (px + 0.5, py + 0.5) is the
+        selection ray of pixel (px, py)) under the current frame info and size (mi_pt_pick).  Returns HIT_DTYPE records, one per position."""
+        xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+        hits = np.zeros(xy.shape[0], HIT_DTYPE)
+        _check_pt(self._l.mi_pt_pick(self._p, xy.ctypes.data_as(C.POINTER(C.c_float)), int(xy.shape[0]), hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+        return hits
 
     def read_depth(self):
         out = np.empty((self.height, self.width), dtype=np.float32)
