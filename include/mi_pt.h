@@ -477,7 +477,7 @@ MI_PT_API int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* p
  * a refit, the visibility and material ids of resident mode.
  *  - Geometry: every triangle of every visible render node, taken as OPAQUE, with no face culling -- the ray flags of the reference's
  *    selection ray (RAY_FLAG_FORCE_OPAQUE, pathtrace_functions.h.slang:813-820) and of the selection pass behind mi_pt_read_selection.
- *    Alpha-tested and transmissive surfaces are hit like any other; hidden nodes are never hit.  Alpha-aware queries are out of scope.
+ *    Alpha-tested and transmissive surfaces are hit like any other; hidden nodes are never hit.  (Alpha-aware queries: the _ex calls below.)
  *  - Acceptance: a triangle is accepted iff the walks' ray / triangle test accepts it and tMin < t < tMax.  t is in units of |direction|
  *    (the direction need not be normalised).  Nothing behind the origin is hit: a negative tMin acts as 0.
  *  - MI_PT_QUERY_CLOSEST: the smallest t wins, exact ties go to the smaller (renderNode, triangle) -- the rule of the closest-hit walks.
@@ -531,6 +531,59 @@ MI_PT_API int mi_pt_query_rays_device(MiPt* pt, const void* deviceRays, int numR
  * MI_PT_ERR_ARGUMENT, with nothing written.  Synchronises; stages like mi_pt_query_rays. */
 MI_PT_API int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHits);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The same queries with options: face culling, alpha-aware acceptance, and the K nearest hits of a ray.  The three calls above keep their
+ * contract; mi_pt_default_query_options + an _ex call returns their bytes.  Per candidate triangle, in this order:
+ *  1. Acceptance interval: as above -- the walks' ray / triangle test accepts it and tMin < t < tMax.
+ *  2. Culling.  MI_PT_QUERY_CULL_MATERIAL rejects a triangle that shows the ray its back (MI_PT_HIT_FRONT_FACE would be clear: object-space
+ *     winding, inverted for a mirroring render node) unless its material is double sided, has a thickness or transmits (the instances the frames
+ *     trace with culling disabled) -- the rule of the frames' camera rays.  MI_PT_QUERY_CULL_NONE: no triangle is culled.
+ *  3. Alpha.  A triangle the frames never alpha-test is accepted untested: alphaMode OPAQUE (glass included), and the triangles
+ *     mi_scene_cut_alpha classified opaque.  Otherwise o = the opacity the frames test with: the base-colour (or diffuse) alpha factor x the
+ *     level-0 alpha texel (nearest or bilinear by the sampler's magnification filter, no UV transform) x the interpolated vertex-colour alpha;
+ *     under alphaMode MASK, 1 if that reaches the material's alphaCutoff and 0 otherwise.
+ *      - MI_PT_QUERY_ALPHA_OPAQUE: accepted whatever o is (the contract of the calls above).
+ *      - MI_PT_QUERY_ALPHA_CUTOFF: accepted iff o >= blendThreshold.  A MASK surface follows its material's cutoff whatever the threshold, a BLEND
+ *        surface the caller's threshold.
+ *      - MI_PT_QUERY_ALPHA_STOCHASTIC: accepted iff draw <= o, draw = unit float of xxhash32(xxhash32(seed, i, 0), renderNode, triangle), i the
+ *        ray's index in the call -- the closest-hit rule of the frames.  One decision per (ray, triangle), however often the walk meets the
+ *        triangle: the same call twice returns the same bytes.
+ *     o is computed in float32 with IEEE arithmetic; the frames compile the same text with fast division, so their o may differ in the last place.
+ *  - MI_PT_QUERY_CLOSEST / MI_PT_QUERY_ANY: their rules above, over the accepted set.
+ *  - MI_PT_QUERY_NEAREST_K: the maxHits accepted DISTINCT triangles with the smallest (t, renderNode, triangle), in ascending order.  Distinct is
+ *    by (renderNode, triangle): a triangle the tree holds as several pre-split references appears once.  Unused records are miss records.
+ *    maxHits == 1 returns the CLOSEST record.  There is no "more hits exist" flag: the walk culls behind the K-th hit and cannot know.  To
+ *    continue, query again with tMin = the last t; this skips what ties exactly with that t.
+ *  - Records: maxHits per ray under NEAREST_K, otherwise one; ray i owns records [i * K, (i + 1) * K).  An invalid ray: its first record has
+ *    MI_PT_HIT_INVALID_RAY, its others are plain misses.
+ *  - Every record is independent of the acceleration structure, bit for bit: BVH2, the 8-wide tree, a refitted tree, resident mode.
+ *  - The current state counts, as above; alpha-aware queries see an in-place change of alphaCutoff or of an alpha factor
+ *    (mi_pt_update_materials) at once -- on the 8-wide tree without a build: the patch rewrites the alpha records the queries read. */
+enum { MI_PT_QUERY_NEAREST_K = 2 }; /* joins MI_PT_QUERY_CLOSEST, MI_PT_QUERY_ANY */
+enum { MI_PT_QUERY_ALPHA_OPAQUE = 0, MI_PT_QUERY_ALPHA_CUTOFF = 1, MI_PT_QUERY_ALPHA_STOCHASTIC = 2 };
+enum { MI_PT_QUERY_CULL_NONE = 0, MI_PT_QUERY_CULL_MATERIAL = 1 };
+enum { MI_PT_QUERY_MAX_HITS = 8 };
+typedef struct MiPtQueryOptions /* 32 B */
+{
+  int32_t  mode;           /* MI_PT_QUERY_* */
+  int32_t  alpha;          /* MI_PT_QUERY_ALPHA_* */
+  int32_t  cull;           /* MI_PT_QUERY_CULL_* */
+  int32_t  maxHits;        /* NEAREST_K: 1..MI_PT_QUERY_MAX_HITS; otherwise 0 or 1 */
+  float    blendThreshold; /* CUTOFF: in (0, 1] */
+  uint32_t seed;           /* STOCHASTIC */
+  int32_t  reserved[2];    /* 0 */
+} MiPtQueryOptions;
+/* CLOSEST, ALPHA_OPAQUE, CULL_NONE, maxHits 1, blendThreshold 0.5, seed 0 */
+MI_PT_API void mi_pt_default_query_options(MiPtQueryOptions* options);
+/* mi_pt_query_rays / mi_pt_query_rays_device / mi_pt_pick with options; numRays (numPixels) x K records out.  MI_PT_ERR_ARGUMENT, with nothing
+ * written: whatever the plain call refuses, NULL options, an unknown mode / alpha / cull value, maxHits out of range, blendThreshold NaN or
+ * outside (0, 1] under CUTOFF, a non-zero reserved word.  The host forms stage numRays x K records (MiPtMemory::rendererBytes).  mi_pt_pick_ex
+ * takes every mode; it answers MI_PT_QUERY_ANY with the closest hit (one of the answers ANY allows).  Under non-default options it writes the camera
+ * rays out and walks them like mi_pt_query_rays_ex; the kernel that forms them may round a ray differently in the last place than mi_pt_pick's. */
+MI_PT_API int mi_pt_query_rays_ex(MiPt* pt, const MiPtRay* hostRays, int numRays, const MiPtQueryOptions* options, MiPtRayHit* hostHits);
+MI_PT_API int mi_pt_query_rays_device_ex(MiPt* pt, const void* deviceRays, int numRays, const MiPtQueryOptions* options, void* deviceHits, void* hipStream);
+MI_PT_API int mi_pt_pick_ex(MiPt* pt, const float* pixelXY, int numPixels, const MiPtQueryOptions* options, MiPtRayHit* hostHits);
+
 /* device address of the last denoise result (NULL before the first), valid until the next denoise / resize */
 MI_PT_API const void* mi_pt_denoised_device_ptr(MiPt* pt);
 
@@ -576,7 +629,8 @@ MI_PT_API const char* mi_pt_version(void);
  * 9: MiPtTemporalParams and the motion / temporal entry points (mi_pt_read_first_hit, mi_pt_set_temporal, mi_pt_read_motion, mi_pt_denoise_temporal,
  *    mi_pt_reset_history).  (Still 9: mi_pt_set_vertex_motion, mi_pt_read_first_hit_triangle, mi_pt_read_previous_positions -- new entry points, no
  *    struct a caller allocates changed.  Still 9: MiPtRay / MiPtRayHit and mi_pt_query_rays, mi_pt_query_rays_device, mi_pt_pick -- new types and
- *    entry points, no struct a caller already allocates changed.) */
+ *    entry points, no struct a caller already allocates changed.  Still 9: MiPtQueryOptions and mi_pt_default_query_options, mi_pt_query_rays_ex,
+ *    mi_pt_query_rays_device_ex, mi_pt_pick_ex -- again new types and entry points only.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

@@ -6,7 +6,10 @@ five such windows after a warm-up launch.  For scale: the segments per second of
 included) over a few frames of the same scene, from mi_pt_get_frame_timing and the segment counter.  mi_pt_pick itself (host form: upload, kernel,
 read-back of 64 B per pixel) is timed by the wall clock next to it.  Prints one JSON line.  Not a test; run it under `timeout`.
 
-usage: timeout 600 python tools/query_bench.py [--detail 0.8] [--size 1920 1080] [--rays 2073600] [--bvh 0] [--sliver]"""
+--alpha / --cull / --max-hits add a row per ray set for the _ex entry point under those options (closest hit, or NEAREST_K when --max-hits > 1).
+
+usage: timeout 600 python tools/query_bench.py [--detail 0.8] [--size 1920 1080] [--rays 2073600] [--bvh 0] [--sliver] [--alpha cutoff] [--cull material]
+       [--max-hits 4]"""
 import argparse
 import json
 import os
@@ -45,21 +48,23 @@ def camera_rays(fi, width, height):
 LAUNCHES = 20  # per timed window: one launch is a fraction of a millisecond, which measures the enqueue as much as the kernel
 
 
-def best_of(tr, rays_dev, mode, runs=5):
-    """ms per launch: the best of `runs` windows of LAUNCHES back-to-back launches between two events, after a warm-up launch."""
-    tr.query_rays(rays_dev, mode=mode)
+def best_of(tr, rays_dev, mode, runs=5, **options):
+    """ms per launch: the best of `runs` windows of LAUNCHES back-to-back launches between two events, after a warm-up launch.  options:
+    alpha / cull / max_hits of PathTracer.query_rays (the _ex entry point); the hit share is that of each ray's first record."""
+    stride = options.get("max_hits", 1) if mode == "nearest_k" else 1
+    tr.query_rays(rays_dev, mode=mode, **options)
     torch.cuda.synchronize()
     best, hits = None, None
     for _ in range(runs):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for _ in range(LAUNCHES):
-            hits = tr.query_rays(rays_dev, mode=mode)
+            hits = tr.query_rays(rays_dev, mode=mode, **options)
         b.record()
         b.synchronize()
         ms = a.elapsed_time(b) / LAUNCHES
         best = ms if best is None else min(best, ms)
-    hit_share = float((hits[:, 12] & 1).float().mean().item())  # (byte 12: the low byte of MiPtRayHit::flags)
+    hit_share = float((hits[::stride, 12] & 1).float().mean().item())  # (byte 12: the low byte of MiPtRayHit::flags)
     return best, hit_share
 
 
@@ -71,6 +76,9 @@ def main():
     ap.add_argument("--bvh", type=int, default=0)
     ap.add_argument("--sliver", action="store_true")
     ap.add_argument("--frames", type=int, default=8, help="frames of the k_trace_closest figure")
+    ap.add_argument("--alpha", choices=("opaque", "cutoff", "stochastic"), default="opaque", help="alpha mode of the extra rows (mi_pt_query_rays_device_ex)")
+    ap.add_argument("--cull", choices=("none", "material"), default="none", help="cull mode of the extra rows")
+    ap.add_argument("--max-hits", type=int, default=1, help="> 1: the extra rows are NEAREST_K with this many records per ray")
     a = ap.parse_args()
     w, h = a.size
     with tempfile.TemporaryDirectory() as tmp:
@@ -89,6 +97,12 @@ def main():
             for mode in ("closest", "any"):
                 ms, share = best_of(tr, dev, mode)
                 out["%s_%s" % (name, mode)] = {"rays": len(rays), "ms": round(ms, 4), "Mrays_s": round(len(rays) / ms * 1e-3, 1), "hit_share": round(share, 4)}
+            if a.alpha != "opaque" or a.cull != "none" or a.max_hits > 1:
+                # the same rays under the options: closest hit, or the max_hits nearest
+                mode = "nearest_k" if a.max_hits > 1 else "closest"
+                ms, share = best_of(tr, dev, mode, alpha=a.alpha, cull=a.cull, max_hits=a.max_hits)
+                out["%s_%s_%s_%s_k%d" % (name, mode, a.alpha, a.cull, a.max_hits)] = {"rays": len(rays), "ms": round(ms, 4), "Mrays_s": round(len(rays) / ms * 1e-3, 1),
+                                                                                     "hit_share": round(share, 4)}
         # mi_pt_pick, host form, wall clock: best of five
         ys, xs = np.mgrid[0:h, 0:w]
         xy = np.stack([xs.reshape(-1) + 0.5, ys.reshape(-1) + 0.5], 1).astype(np.float32)

@@ -168,6 +168,10 @@ class MiPtRayHit(C.Structure):
                 ("materialID", i32), ("position", f32 * 3), ("reserved0", f32), ("normal", f32 * 3), ("reserved1", f32)]
 
 
+class MiPtQueryOptions(C.Structure):
+    _fields_ = [("mode", i32), ("alpha", i32), ("cull", i32), ("maxHits", i32), ("blendThreshold", f32), ("seed", u32), ("reserved", i32 * 2)]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -182,6 +186,7 @@ assert C.sizeof(MiPtAccelInfo) == 64
 assert C.sizeof(MiPtAccelResidentInfo) == 40
 assert C.sizeof(MiPtRay) == 32
 assert C.sizeof(MiPtRayHit) == 64
+assert C.sizeof(MiPtQueryOptions) == 32
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
@@ -191,7 +196,10 @@ MI_PT_DEFORM_DEFER_BUILD = 1
 MI_PT_ACCEL_REBUILD, MI_PT_ACCEL_REFIT, MI_PT_ACCEL_AUTO = 0, 1, 2
 MI_PT_ACCEL_LAST_BUILD, MI_PT_ACCEL_LAST_REFIT = 0, 1
 MI_PT_HIT, MI_PT_HIT_FRONT_FACE, MI_PT_HIT_INVALID_RAY = 1, 2, 4
-MI_PT_QUERY_CLOSEST, MI_PT_QUERY_ANY = 0, 1
+MI_PT_QUERY_CLOSEST, MI_PT_QUERY_ANY, MI_PT_QUERY_NEAREST_K = 0, 1, 2
+MI_PT_QUERY_ALPHA_OPAQUE, MI_PT_QUERY_ALPHA_CUTOFF, MI_PT_QUERY_ALPHA_STOCHASTIC = 0, 1, 2
+MI_PT_QUERY_CULL_NONE, MI_PT_QUERY_CULL_MATERIAL = 0, 1
+MI_PT_QUERY_MAX_HITS = 8
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
@@ -324,6 +332,10 @@ PT_SYMBOLS = {
     "mi_pt_query_rays": (i32, [VP, P(MiPtRay), i32, i32, P(MiPtRayHit)]),
     "mi_pt_query_rays_device": (i32, [VP, VP, i32, i32, VP, VP]),
     "mi_pt_pick": (i32, [VP, P(f32), i32, P(MiPtRayHit)]),
+    "mi_pt_default_query_options": (None, [P(MiPtQueryOptions)]),
+    "mi_pt_query_rays_ex": (i32, [VP, P(MiPtRay), i32, P(MiPtQueryOptions), P(MiPtRayHit)]),
+    "mi_pt_query_rays_device_ex": (i32, [VP, VP, i32, P(MiPtQueryOptions), VP, VP]),
+    "mi_pt_pick_ex": (i32, [VP, P(f32), i32, P(MiPtQueryOptions), P(MiPtRayHit)]),
 }
 
 

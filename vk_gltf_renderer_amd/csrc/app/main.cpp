@@ -20,7 +20,7 @@ int main(int argc, char** argv)
   std::string       sceneFile, hdrFile = "std_env.hdr", outputFile;
   int               size[2] = {1280, 720};
   std::string       sequenceFile, sequenceString, saveSelftest, pick;
-  int               frames = 1, framesInFlight = 32;
+  int               frames = 1, framesInFlight = 32, pickAlpha = 0;
   bool              headless = false, vvl = false, selftest = false, benchmark = false;
   registry.add("scenefile", "Input scene filename (.gltf / .glb)", &sceneFile);
   registry.add("hdrfile", "Input HDR filename", &hdrFile);
@@ -30,6 +30,7 @@ int main(int argc, char** argv)
   registry.add("headless", "Run without a window", &headless, true);
   registry.add("framesInFlight", "Headless: app frames traced as one set of launches (same image as one by one; 1 = like the reference)", &framesInFlight);
   registry.add("pick", "Headless: \"x y\" in continuous pixel coordinates; after the last frame, pick there and print one PICK {...} line", &pick);
+  registry.add("pickAlpha", "Headless: 1 = --pick names what the viewer sees at the pixel (alpha cutoff 0.5, back faces of single-sided materials culled)", &pickAlpha);
   registry.add("benchmark", "Benchmark mode: run the scripted sequences of --sequencefile / --sequencestring", &benchmark);
   registry.add("sequencefile", "Benchmark script (.cfg) with SEQUENCE blocks", &sequenceFile);
   registry.add("sequencestring", "Benchmark script given on the command line", &sequenceString);
@@ -142,9 +143,15 @@ int main(int argc, char** argv)
   if(!pick.empty())
   {
     // what the reference logs after a click in the viewport (src/ui_renderer.cpp:95-150: nvvk::RayPicker over the TLAS), from mi_pt_pick
-    float      xy[2] = {0.0f, 0.0f};
-    MiPtRayHit hit{};
-    if(sscanf(pick.c_str(), "%f %f", &xy[0], &xy[1]) != 2 || !app.pathTracer().handle() || mi_pt_pick(app.pathTracer().handle(), xy, 1, &hit) != MI_PT_OK)
+    // (--pickAlpha 1: mi_pt_pick_ex with the alpha cutoff and the materials' face culling -- the surface the frames show there)
+    float            xy[2] = {0.0f, 0.0f};
+    MiPtRayHit       hit{};
+    MiPtQueryOptions options;
+    mi_pt_default_query_options(&options);
+    options.alpha = MI_PT_QUERY_ALPHA_CUTOFF;
+    options.cull  = MI_PT_QUERY_CULL_MATERIAL;
+    if(sscanf(pick.c_str(), "%f %f", &xy[0], &xy[1]) != 2 || !app.pathTracer().handle()
+       || (pickAlpha ? mi_pt_pick_ex(app.pathTracer().handle(), xy, 1, &options, &hit) : mi_pt_pick(app.pathTracer().handle(), xy, 1, &hit)) != MI_PT_OK)
     {
       fprintf(stderr, "--pick \"%s\" failed: %s\n", pick.c_str(), app.pathTracer().handle() ? mi_pt_last_error() : "no renderer");
       return 1;

@@ -21,6 +21,7 @@
 #include "pt_bvh.h"
 #include "pt_deform.h"
 #include "pt_kernels.h"
+#include "pt_query.h"
 
 namespace {
 
@@ -2482,15 +2483,44 @@ int mi_pt_read_selection(MiPt* pt, uint32_t* host)
 }
 // ---- ray queries and picking (query.hip) --------------------------------------------------------------------------------------------------------
 namespace {
-int queryStaging(MiPt* pt, size_t n)
+int queryStagingEx(MiPt* pt, size_t numRays, size_t numHits)
 {
-  if(n > pt->queryRays.count)
-    HIP_TRY(pt->queryRays.alloc(n));
-  if(n > pt->queryHits.count)
-    HIP_TRY(pt->queryHits.alloc(n));
+  if(numRays > pt->queryRays.count)
+    HIP_TRY(pt->queryRays.alloc(numRays));
+  if(numHits > pt->queryHits.count)
+    HIP_TRY(pt->queryHits.alloc(numHits));
   return MI_PT_OK;
 }
+int  queryStaging(MiPt* pt, size_t n) { return queryStagingEx(pt, n, n); }
 bool queryModeKnown(int mode) { return mode == MI_PT_QUERY_CLOSEST || mode == MI_PT_QUERY_ANY; }
+// The rules of a valid MiPtQueryOptions (rules.maxHits: the records per ray); false for what the header refuses.
+bool queryRulesOf(const MiPtQueryOptions* o, pt::QueryRules& rules)
+{
+  if(!o || o->reserved[0] != 0 || o->reserved[1] != 0)
+    return false;
+  if(!(queryModeKnown(o->mode) || o->mode == MI_PT_QUERY_NEAREST_K))
+    return false;
+  if(o->alpha != MI_PT_QUERY_ALPHA_OPAQUE && o->alpha != MI_PT_QUERY_ALPHA_CUTOFF && o->alpha != MI_PT_QUERY_ALPHA_STOCHASTIC)
+    return false;
+  if(o->cull != MI_PT_QUERY_CULL_NONE && o->cull != MI_PT_QUERY_CULL_MATERIAL)
+    return false;
+  if(o->mode == MI_PT_QUERY_NEAREST_K ? (o->maxHits < 1 || o->maxHits > MI_PT_QUERY_MAX_HITS) : (o->maxHits != 0 && o->maxHits != 1))
+    return false;
+  if(o->alpha == MI_PT_QUERY_ALPHA_CUTOFF && !(o->blendThreshold > 0.0f && o->blendThreshold <= 1.0f))  // (NaN fails too)
+    return false;
+  rules.alpha          = o->alpha;
+  rules.cull           = o->cull;
+  rules.maxHits        = o->mode == MI_PT_QUERY_NEAREST_K ? o->maxHits : 1;
+  rules.blendThreshold = o->blendThreshold;
+  rules.seed           = o->seed;
+  return true;
+}
+// An alpha-aware walk reads the alpha record of every triangle without INST_FORCE_OPAQUE / INST_ALPHA_PASSES.  Such a triangle sets hasAlphaTest,
+// hence hasAlpha, under which the build and the material patch keep the records (buildAccelerationOver, patchTriangleData): checked, not assumed.
+bool queryAlphaRecordsMissing(const MiPt* pt, const pt::QueryRules& rules)
+{
+  return rules.alpha != MI_PT_QUERY_ALPHA_OPAQUE && pt->hasAlphaTest && pt->scene.numTris > 0 && !pt->scene.alphaTris;
+}
 }  // namespace
 
 int mi_pt_query_rays(MiPt* pt, const MiPtRay* hostRays, int numRays, int mode, MiPtRayHit* hostHits)
@@ -2553,6 +2583,92 @@ int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHi
   pt::launchPickRays(pt->scene, fc, pt->wide, reinterpret_cast<const float2*>(pt->queryRays.ptr), uint32_t(numPixels), pt->queryHits.ptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, size_t(numPixels) * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+void mi_pt_default_query_options(MiPtQueryOptions* options)
+{
+  if(!options)
+    return;
+  memset(options, 0, sizeof(*options));
+  options->mode           = MI_PT_QUERY_CLOSEST;
+  options->alpha          = MI_PT_QUERY_ALPHA_OPAQUE;
+  options->cull           = MI_PT_QUERY_CULL_NONE;
+  options->maxHits        = 1;
+  options->blendThreshold = 0.5f;
+}
+int mi_pt_query_rays_ex(MiPt* pt, const MiPtRay* hostRays, int numRays, const MiPtQueryOptions* options, MiPtRayHit* hostHits)
+{
+  FLUSH_PENDING(pt);
+  pt::QueryRules rules;
+  if(!pt || numRays < 0 || !queryRulesOf(options, rules) || (numRays > 0 && (!hostRays || !hostHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_ex: bad arguments");
+  if(queryAlphaRecordsMissing(pt, rules))
+    return fail(MI_PT_ERR_STATE, "mi_pt_query_rays_ex: the scene has alpha-tested triangles but no alpha records");
+  if(numRays == 0)
+    return MI_PT_OK;
+  const size_t numHits = size_t(numRays) * size_t(rules.maxHits);
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(int rc = queryStagingEx(pt, size_t(numRays), numHits))
+    return rc;
+  HIP_TRY(hipMemcpy(pt->queryRays.ptr, hostRays, size_t(numRays) * sizeof(MiPtRay), hipMemcpyHostToDevice));
+  pt::launchQueryRaysEx(pt->scene, pt->wide, options->mode == MI_PT_QUERY_ANY, rules, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+int mi_pt_query_rays_device_ex(MiPt* pt, const void* deviceRays, int numRays, const MiPtQueryOptions* options, void* deviceHits, void* hipStream)
+{
+  FLUSH_PENDING(pt);
+  pt::QueryRules rules;
+  if(!pt || numRays < 0 || !queryRulesOf(options, rules) || (numRays > 0 && (!deviceRays || !deviceHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device_ex: bad arguments");
+  if(numRays > 0 && ((reinterpret_cast<uintptr_t>(deviceRays) | reinterpret_cast<uintptr_t>(deviceHits)) & 15u))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device_ex: rays and hits must be 16-byte aligned");
+  if(queryAlphaRecordsMissing(pt, rules))
+    return fail(MI_PT_ERR_STATE, "mi_pt_query_rays_device_ex: the scene has alpha-tested triangles but no alpha records");
+  if(numRays == 0)
+    return MI_PT_OK;
+  HIP_TRY(hipSetDevice(pt->device));
+  pt::launchQueryRaysEx(pt->scene, pt->wide, options->mode == MI_PT_QUERY_ANY, rules, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays),
+                        static_cast<MiPtRayHit*>(deviceHits), reinterpret_cast<hipStream_t>(hipStream));
+  HIP_TRY(hipGetLastError());
+  return MI_PT_OK;
+}
+int mi_pt_pick_ex(MiPt* pt, const float* pixelXY, int numPixels, const MiPtQueryOptions* options, MiPtRayHit* hostHits)
+{
+  FLUSH_PENDING(pt);
+  pt::QueryRules rules;
+  if(!pt || numPixels < 0 || !queryRulesOf(options, rules) || (numPixels > 0 && (!pixelXY || !hostHits)))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick_ex: bad arguments");
+  if(pt->width <= 0 || !pt->haveFrameInfo)
+    return fail(MI_PT_ERR_STATE, "mi_pt_pick_ex: call mi_pt_resize and mi_pt_set_frame_info first");
+  for(int i = 0; i < numPixels; ++i)
+  {
+    const float x = pixelXY[2 * i], y = pixelXY[2 * i + 1];
+    if(!(x >= 0.0f && x < float(pt->width) && y >= 0.0f && y < float(pt->height)))  // (NaN fails too)
+      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick_ex: pixel " + std::to_string(i) + " lies outside the image");
+  }
+  if(queryAlphaRecordsMissing(pt, rules))
+    return fail(MI_PT_ERR_STATE, "mi_pt_pick_ex: the scene has alpha-tested triangles but no alpha records");
+  if(numPixels == 0)
+    return MI_PT_OK;
+  // the pixel positions are staged behind the ray records the camera rays are written to (8 bytes each: a quarter of a ray record)
+  const size_t numHits = size_t(numPixels) * size_t(rules.maxHits), xyRays = (size_t(numPixels) + 3) / 4;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(int rc = queryStagingEx(pt, size_t(numPixels) + xyRays, numHits))
+    return rc;
+  float2* xy = reinterpret_cast<float2*>(pt->queryRays.ptr + numPixels);
+  HIP_TRY(hipMemcpy(xy, pixelXY, size_t(numPixels) * sizeof(float2), hipMemcpyHostToDevice));
+  pt::FrameConsts fc;
+  memset(&fc, 0, sizeof(fc));
+  fc.frameInfo = pt->frameInfo;
+  fc.width     = pt->width;
+  fc.height    = pt->height;
+  pt::launchPickRaysEx(pt->scene, fc, pt->wide, rules, xy, pt->queryRays.ptr, uint32_t(numPixels), pt->queryHits.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
 int mi_pt_read_depth(MiPt* pt, float* host)

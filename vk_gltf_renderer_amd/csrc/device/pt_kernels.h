@@ -55,6 +55,13 @@ void launchSelection(const LaunchCtx& c, uint32_t* selection);
 // the camera ray of the continuous pixel position xy[i] under fc.frameInfo / fc.width / fc.height (nothing else of fc is read)
 void launchQueryRays(const DevScene& scene, bool wide, bool any, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
 void launchPickRays(const DevScene& scene, const FrameConsts& fc, bool wide, const float2* xy, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
+// the same under the rules of a MiPtQueryOptions (pt_query.h: QueryRules -- face culling, alpha mode, q.maxHits records per ray: hits holds numRays x
+// q.maxHits).  any: MI_PT_QUERY_ANY (q.maxHits is 1 then).  Opaque, unculled single-hit rules run the kernels of the two launchers above.
+// rayScratch: numRays ray records, 16-byte aligned, that launchPickRaysEx writes the camera rays to.
+struct QueryRules;
+void launchQueryRaysEx(const DevScene& scene, bool wide, bool any, const QueryRules& q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
+void launchPickRaysEx(const DevScene& scene, const FrameConsts& fc, bool wide, const QueryRules& q, const float2* xy, MiPtRay* rayScratch, uint32_t numRays,
+                      MiPtRayHit* hits, hipStream_t s);
 
 // a-trous edge-avoiding wavelet filter (denoise.hip)
 void launchAtrous(const float4* in, float4* out, const float4* albedo, const float4* normal, int width, int height, int step, float sigmaColor,

@@ -5,6 +5,10 @@
 // triangle test and the camera ray are pinned to IEEE results in every translation unit anyway (divExact, normalizeExact).
 // The closest-hit walk's wave-wide triangle rounds and LDS node cache are left out on purpose: a lane never depends on another lane here, so a
 // partially filled last wave needs no care and there is no barrier in the kernel at all.
+// The _ex entry points (mi_pt_query_rays_ex, mi_pt_query_rays_device_ex, mi_pt_pick_ex) add k_query_rays_ex: the same walk with the candidate test
+// of pt_query.h's second half -- face culling, the alpha decision, a per-lane sorted list of the K nearest distinct triangles held in registers
+// (K is a compile-time bound: 1, 2, 4, 8).  The alpha mode and the cull mode are wave-uniform run-time values.  Default options take the kernels
+// above; nothing of theirs changes.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -135,6 +139,131 @@ __global__ void __launch_bounds__(QUERY_BLOCK) k_pick_rays(DevScene sc, FrameCon
   storeHit(hits, i, queryOne<WIDE, false>(sc, ray, s_stack));
 }
 
+// ---- the _ex walks --------------------------------------------------------------------------------------------------------------------------------
+// The walk of one ray into the list of its (at most) q.maxHits <= K nearest accepted distinct triangles.  ANY (K = 1): the first accepted one.
+// Returns false for an invalid ray (the list stays empty).
+template <bool WIDE, bool ANY, int K>
+PT_DEV bool queryOneEx(const DevScene& sc, const MiPtRay& ray, uint32_t rayIndex, const QueryRules& q, int* stack, QueryList<K>& L)
+{
+  L = queryListEmpty<K>(ray.tMax);
+  if(!queryRayValid(ray))
+    return false;
+  const float    tMin = queryTMin(ray.tMin), tMax = ray.tMax;
+  const RaySetup r    = makeRaySetup(mk3(ray.origin), mk3(ray.direction));
+  const uint32_t raySeed = querySeed(q.seed, rayIndex);
+  // the node tests cull with the ray's far bound while the list is not full, with its last t from then on; triangles AT that distance are still
+  // visited (padded boxes), so that the tie rule sees them
+  const float far   = fminf(tMax, 3.0e38f);
+  float       walkT = far;
+  if(sc.bvhRoot != BVH_EMPTY && tMin < tMax)
+  {
+    if(WIDE)
+    {
+      LaneStack2 st2;
+      uint32_t   stackOverflow[2 * BVH8_STACK_PRIV];
+      st2.lds = stack; st2.tid = int(threadIdx.x); st2.stride = QUERY_BLOCK; st2.sp = 0;
+      st2.privBase = stackOverflow; st2.privBits = stackOverflow + BVH8_STACK_PRIV;
+      const uint32_t octinv = rayOctInv(r.idir);
+      NodeGroup      G      = rootGroup(octinv);
+      bool           done   = false;
+      while(!done)
+      {
+        if((G.bits >> 8) == 0u)
+        {
+          if(st2.sp == 0)
+            break;
+          G = st2.pop();
+        }
+        const uint32_t child = groupPopChild(G, octinv);
+        if(G.bits >> 8)
+          st2.push(G);
+        uint32_t tBase, tMask;
+        bvh8Visit(sc, r, walkT, octinv, child, G, tBase, tMask, nullptr, 0u);
+        while(leafPending(tMask))
+        {
+          const int k = int(leafPop(tMask, 0u));  // (offset from the node's first triangle)
+          if(queryTestTriEx(sc, r, int(tBase) + k, tMin, tMax, q, raySeed, L))
+          {
+            walkT = queryListBound(L, q.maxHits, far);
+            if(ANY)
+            {
+              done = true;
+              break;
+            }
+          }
+        }
+      }
+    }
+    else
+    {
+      LaneStack st;
+      int       stackOverflow[BVH_STACK_PRIV];
+      st.lds = stack; st.tid = int(threadIdx.x); st.stride = QUERY_BLOCK; st.sp = 0; st.priv = stackOverflow;
+      bvhWalk(sc, r, walkT, st, [&](int triIndex, float tmax) -> float {
+        if(queryTestTriEx(sc, r, triIndex, tMin, tMax, q, raySeed, L))
+          return ANY ? -1.0f : queryListBound(L, q.maxHits, far);
+        return tmax;
+      });
+    }
+  }
+  return true;
+}
+
+// Ray i owns records [i * maxHits, (i + 1) * maxHits): its list in ascending order, then miss records; an invalid ray says so in its first record.
+template <bool WIDE, bool ANY, int K>
+__global__ void __launch_bounds__(QUERY_BLOCK) k_query_rays_ex(DevScene sc, QueryRules q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits)
+{
+  __shared__ int s_stack[BVH_STACK_LDS * QUERY_BLOCK];
+  const uint32_t i = blockIdx.x * uint32_t(QUERY_BLOCK) + threadIdx.x;
+  if(i >= numRays)
+    return;
+  const MiPtRay ray = loadRay(rays, i);
+  QueryList<K>  L;
+  const bool    valid = queryOneEx<WIDE, ANY, K>(sc, ray, i, q, s_stack, L);
+  MiPtRayHit*   out   = hits + size_t(i) * size_t(q.maxHits);
+#pragma unroll
+  for(int j = 0; j < K; ++j)
+    if(j < q.maxHits)
+      storeHit(out, uint32_t(j), j == 0 && !valid ? queryMiss(MI_PT_HIT_INVALID_RAY) : queryListRecord(sc, L, j, ray));
+}
+
+// mi_pt_pick_ex: the camera rays of k_pick_rays written out as MiPtRay records, for k_query_rays_ex to walk.
+__global__ void __launch_bounds__(QUERY_BLOCK) k_pick_make_rays(FrameConsts fc, const float2* xy, uint32_t numRays, MiPtRay* rays)
+{
+  const uint32_t i = blockIdx.x * uint32_t(QUERY_BLOCK) + threadIdx.x;
+  if(i >= numRays)
+    return;
+  const float2 p  = xy[i];
+  const float  fx = floorf(p.x), fy = floorf(p.y);
+  f3           origin, direction;
+  getRay(fc, mk2(fx, fy), mk2(p.x - fx, p.y - fy), origin, direction);
+  float4* o = reinterpret_cast<float4*>(rays + i);
+  o[0]      = make_float4(origin.x, origin.y, origin.z, 0.0f);
+  o[1]      = make_float4(direction.x, direction.y, direction.z, __builtin_inff());
+}
+
+template <bool WIDE, bool ANY, int K>
+void launchEx(const DevScene& scene, const QueryRules& q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s)
+{
+  const unsigned grid = (numRays + QUERY_BLOCK - 1) / QUERY_BLOCK;
+  hipLaunchKernelGGL((k_query_rays_ex<WIDE, ANY, K>), dim3(grid), dim3(QUERY_BLOCK), 0, s, scene, q, rays, numRays, hits);
+}
+template <bool WIDE>
+void launchExWidth(const DevScene& scene, bool any, const QueryRules& q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s)
+{
+  if(any)
+    launchEx<WIDE, true, 1>(scene, q, rays, numRays, hits, s);
+  else if(q.maxHits <= 1)
+    launchEx<WIDE, false, 1>(scene, q, rays, numRays, hits, s);
+  else if(q.maxHits <= 2)
+    launchEx<WIDE, false, 2>(scene, q, rays, numRays, hits, s);
+  else if(q.maxHits <= 4)
+    launchEx<WIDE, false, 4>(scene, q, rays, numRays, hits, s);
+  else
+    launchEx<WIDE, false, 8>(scene, q, rays, numRays, hits, s);
+}
+bool plainRules(const QueryRules& q) { return q.alpha == MI_PT_QUERY_ALPHA_OPAQUE && q.cull == MI_PT_QUERY_CULL_NONE && q.maxHits == 1; }
+
 }  // namespace
 
 void launchQueryRays(const DevScene& scene, bool wide, bool any, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s)
@@ -167,6 +296,34 @@ void launchPickRays(const DevScene& scene, const FrameConsts& fc, bool wide, con
     hipLaunchKernelGGL(k_pick_rays<true>, dim3(grid), dim3(QUERY_BLOCK), 0, s, scene, fc, xy, numRays, hits);
   else
     hipLaunchKernelGGL(k_pick_rays<false>, dim3(grid), dim3(QUERY_BLOCK), 0, s, scene, fc, xy, numRays, hits);
+}
+
+// any: MI_PT_QUERY_ANY (q.maxHits is 1 then).  Opaque, unculled single-hit queries are the kernels of launchQueryRays.
+void launchQueryRaysEx(const DevScene& scene, bool wide, bool any, const QueryRules& q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s)
+{
+  if(numRays == 0)
+    return;
+  if(plainRules(q))
+    launchQueryRays(scene, wide, any, rays, numRays, hits, s);
+  else if(wide)
+    launchExWidth<true>(scene, any, q, rays, numRays, hits, s);
+  else
+    launchExWidth<false>(scene, any, q, rays, numRays, hits, s);
+}
+
+// rayScratch: numRays ray records the camera rays are written to (unused under plain rules, which are k_pick_rays).
+void launchPickRaysEx(const DevScene& scene, const FrameConsts& fc, bool wide, const QueryRules& q, const float2* xy, MiPtRay* rayScratch, uint32_t numRays,
+                      MiPtRayHit* hits, hipStream_t s)
+{
+  if(numRays == 0)
+    return;
+  if(plainRules(q))
+  {
+    launchPickRays(scene, fc, wide, xy, numRays, hits, s);
+    return;
+  }
+  hipLaunchKernelGGL(k_pick_make_rays, dim3((numRays + QUERY_BLOCK - 1) / QUERY_BLOCK), dim3(QUERY_BLOCK), 0, s, fc, xy, numRays, rayScratch);
+  launchQueryRaysEx(scene, wide, false, q, rayScratch, numRays, hits, s);
 }
 
 }  // namespace pt

@@ -18,7 +18,9 @@ from . import _capi as capi
 HIT_DTYPE = np.dtype([("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("flags", "<u4"), ("renderNode", "<i4"), ("renderPrimID", "<i4"), ("triangle", "<u4"),
                       ("materialID", "<i4"), ("position", "<f4", (3,)), ("reserved0", "<f4"), ("normal", "<f4", (3,)), ("reserved1", "<f4")])
 assert HIT_DTYPE.itemsize == 64
-_QUERY_MODES = {"closest": capi.MI_PT_QUERY_CLOSEST, "any": capi.MI_PT_QUERY_ANY}
+_QUERY_MODES = {"closest": capi.MI_PT_QUERY_CLOSEST, "any": capi.MI_PT_QUERY_ANY, "nearest_k": capi.MI_PT_QUERY_NEAREST_K}
+_QUERY_ALPHA = {"opaque": capi.MI_PT_QUERY_ALPHA_OPAQUE, "cutoff": capi.MI_PT_QUERY_ALPHA_CUTOFF, "stochastic": capi.MI_PT_QUERY_ALPHA_STOCHASTIC}
+_QUERY_CULL = {"none": capi.MI_PT_QUERY_CULL_NONE, "material": capi.MI_PT_QUERY_CULL_MATERIAL}
 
 
 class MiError(RuntimeError):
@@ -356,37 +358,79 @@ class PathTracer:
         _check_pt(self._l.mi_pt_read_selection(self._p, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
 
-    def query_rays(self, rays, mode="closest", stream=None):
-        """Rays against the resident scene (mi_pt_query_rays): every triangle of every visible render node, opaque, no culling.  `rays`: (n, 8)
-        float32 rows of origin.xyz, tMin, direction.xyz, tMax; mode "closest" or "any" (include/mi_pt.h has the semantics).  A numpy array
-        returns a structured array of HIT_DTYPE records (synchronises).  A torch tensor on this instance's device goes through the device form
-        and returns an (n, 64) uint8 tensor of the same records, asynchronous on `stream` (default: torch's current stream)."""
+    @staticmethod
+    def _query_options(mode, alpha, cull, max_hits, blend_threshold, seed):
+        """MiPtQueryOptions of the keyword arguments, or None when they are the defaults of the plain entry points (which then serve the call)."""
         m = _QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+        a = _QUERY_ALPHA[alpha] if isinstance(alpha, str) else int(alpha)
+        c = _QUERY_CULL[cull] if isinstance(cull, str) else int(cull)
+        # (a call without any of the new arguments is the plain entry point's, whatever it passes for `mode`: "nearest_k" is one of the new arguments)
+        if (mode != "nearest_k" and a == capi.MI_PT_QUERY_ALPHA_OPAQUE and c == capi.MI_PT_QUERY_CULL_NONE and int(max_hits) == 1
+                and float(blend_threshold) == 0.5 and int(seed) == 0):
+            return m, None
+        o = capi.MiPtQueryOptions()
+        o.mode, o.alpha, o.cull, o.maxHits, o.blendThreshold, o.seed = m, a, c, int(max_hits), float(blend_threshold), int(seed) & 0xffffffff
+        return m, o
+
+    def query_rays(self, rays, mode="closest", stream=None, alpha="opaque", cull="none", max_hits=1, blend_threshold=0.5, seed=0):
+        """Rays against the resident scene (mi_pt_query_rays / mi_pt_query_rays_ex; include/mi_pt.h has the semantics).  `rays`: (n, 8) float32
+        rows of origin.xyz, tMin, direction.xyz, tMax; mode "closest", "any" or "nearest_k" (the max_hits nearest distinct triangles per ray, 1..8);
+        alpha "opaque" (every triangle counts), "cutoff" (opacity >= blend_threshold; MASK surfaces follow their own cutoff) or "stochastic" (the
+        frames' draw, from `seed`); cull "none" or "material" (back faces of single-sided materials are skipped).  A numpy array returns a
+        structured array of HIT_DTYPE records, (n,) or (n, max_hits) under "nearest_k" (synchronises).  A torch tensor on this instance's device
+        goes through the device form and returns an (n * K, 64) uint8 tensor of the same records (K = max_hits under "nearest_k", otherwise 1),
+        asynchronous on `stream` (default: torch's current stream).  Without the new arguments the call is the plain entry point's."""
+        m, opts = self._query_options(mode, alpha, cull, max_hits, blend_threshold, seed)
+        k = int(max_hits) if m == capi.MI_PT_QUERY_NEAREST_K else 1
+        if opts is not None and not 1 <= k <= capi.MI_PT_QUERY_MAX_HITS:
+            raise ValueError("query_rays: max_hits must lie in 1..%d" % capi.MI_PT_QUERY_MAX_HITS)
         if type(rays).__module__.split(".")[0] == "torch":
             import torch
             if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous()):
                 raise ValueError("query_rays: a contiguous (n, 8) float32 device tensor is required")
-            hits = torch.empty((rays.shape[0], 64), dtype=torch.uint8, device=rays.device)
+            hits = torch.empty((rays.shape[0] * k, 64), dtype=torch.uint8, device=rays.device)
             if stream is None:
                 stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check_pt(self._l.mi_pt_query_rays_device(self._p, C.c_void_p(rays.data_ptr()), int(rays.shape[0]), m, C.c_void_p(hits.data_ptr()),
-                                                      C.c_void_p(stream or 0)))
+            if opts is None:
+                _check_pt(self._l.mi_pt_query_rays_device(self._p, C.c_void_p(rays.data_ptr()), int(rays.shape[0]), m, C.c_void_p(hits.data_ptr()),
+                                                          C.c_void_p(stream or 0)))
+            else:
+                _check_pt(self._l.mi_pt_query_rays_device_ex(self._p, C.c_void_p(rays.data_ptr()), int(rays.shape[0]), C.byref(opts),
+                                                             C.c_void_p(hits.data_ptr()), C.c_void_p(stream or 0)))
             return hits
         rays = np.ascontiguousarray(rays, dtype=np.float32)
         if rays.ndim != 2 or rays.shape[1] != 8:
             raise ValueError("query_rays: an (n, 8) float32 array is required")
-        hits = np.zeros(rays.shape[0], HIT_DTYPE)
-        _check_pt(self._l.mi_pt_query_rays(self._p, rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), int(rays.shape[0]), m,
-                                           hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
-        return hits
+        if opts is None:
+            hits = np.zeros(rays.shape[0], HIT_DTYPE)
+            _check_pt(self._l.mi_pt_query_rays(self._p, rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), int(rays.shape[0]), m,
+                                               hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+            return hits
+        hits = np.zeros((rays.shape[0], k), HIT_DTYPE)
+        _check_pt(self._l.mi_pt_query_rays_ex(self._p, rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), int(rays.shape[0]), C.byref(opts),
+                                              hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+        return hits if m == capi.MI_PT_QUERY_NEAREST_K else hits.reshape(-1)
 
-    def pick(self, xy):
+    def pick(self, xy, mode="closest", alpha="opaque", cull="none", max_hits=1, blend_threshold=0.5, seed=0):
         """The closest hits of the camera rays through the continuous pixel positions `xy` ((n, 2) or one (x, y); (px + 0.5, py + 0.5) is the
-        selection ray of pixel (px, py)) under the current frame info and size (mi_pt_pick).  Returns HIT_DTYPE records, one per position."""
+        selection ray of pixel (px, py)) under the current frame info and size (mi_pt_pick).  Returns HIT_DTYPE records, one per position.
+        With alpha / cull / mode="nearest_k" (as query_rays; mi_pt_pick_ex): alpha="cutoff", cull="material" names what the viewer sees at the
+        pixel; "nearest_k" returns (n, max_hits) records, what lies under the cursor and behind that."""
         xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
-        hits = np.zeros(xy.shape[0], HIT_DTYPE)
-        _check_pt(self._l.mi_pt_pick(self._p, xy.ctypes.data_as(C.POINTER(C.c_float)), int(xy.shape[0]), hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
-        return hits
+        m, opts = self._query_options(mode, alpha, cull, max_hits, blend_threshold, seed)
+        if opts is None:
+            if m != capi.MI_PT_QUERY_CLOSEST:
+                raise ValueError("pick: mode must be \"closest\" or \"nearest_k\"")
+            hits = np.zeros(xy.shape[0], HIT_DTYPE)
+            _check_pt(self._l.mi_pt_pick(self._p, xy.ctypes.data_as(C.POINTER(C.c_float)), int(xy.shape[0]), hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+            return hits
+        k = int(max_hits) if m == capi.MI_PT_QUERY_NEAREST_K else 1
+        if not 1 <= k <= capi.MI_PT_QUERY_MAX_HITS:
+            raise ValueError("pick: max_hits must lie in 1..%d" % capi.MI_PT_QUERY_MAX_HITS)
+        hits = np.zeros((xy.shape[0], k), HIT_DTYPE)
+        _check_pt(self._l.mi_pt_pick_ex(self._p, xy.ctypes.data_as(C.POINTER(C.c_float)), int(xy.shape[0]), C.byref(opts),
+                                        hits.ctypes.data_as(C.POINTER(capi.MiPtRayHit))))
+        return hits if m == capi.MI_PT_QUERY_NEAREST_K else hits.reshape(-1)
 
     def read_depth(self):
         out = np.empty((self.height, self.width), dtype=np.float32)
