@@ -2482,8 +2482,63 @@ int mi_pt_read_selection(MiPt* pt, uint32_t* host)
   return MI_PT_OK;
 }
 // ---- ray queries and picking (query.hip) --------------------------------------------------------------------------------------------------------
+// Six entry points over three internal functions -- rays in host memory, rays in device memory, pixel positions.  A plain entry point is its _ex
+// form under default options: it names itself in the messages, and differs in nothing else.
 namespace {
-int queryStagingEx(MiPt* pt, size_t numRays, size_t numHits)
+// What an entry point asks for: its name (the prefix of its messages), whether its mode / options are ones the header accepts, and then their rules.
+struct QueryCall
+{
+  const char*    who;
+  bool           valid;
+  pt::QueryRules rules;  // (rules.maxHits: the records per ray)
+  bool           any;    // MI_PT_QUERY_ANY
+};
+QueryCall queryCallOfMode(const char* who, int mode)
+{
+  QueryCall c{};
+  c.who                  = who;
+  c.valid                = mode == MI_PT_QUERY_CLOSEST || mode == MI_PT_QUERY_ANY;
+  c.rules.alpha          = MI_PT_QUERY_ALPHA_OPAQUE;
+  c.rules.cull           = MI_PT_QUERY_CULL_NONE;
+  c.rules.maxHits        = 1;
+  c.rules.blendThreshold = 0.5f;
+  c.any                  = mode == MI_PT_QUERY_ANY;
+  return c;
+}
+QueryCall queryCallOf(const char* who, const MiPtQueryOptions* o)
+{
+  QueryCall c{};
+  c.who = who;
+  if(!o || o->reserved[0] != 0 || o->reserved[1] != 0)
+    return c;
+  if(o->mode != MI_PT_QUERY_CLOSEST && o->mode != MI_PT_QUERY_ANY && o->mode != MI_PT_QUERY_NEAREST_K)
+    return c;
+  if(o->alpha != MI_PT_QUERY_ALPHA_OPAQUE && o->alpha != MI_PT_QUERY_ALPHA_CUTOFF && o->alpha != MI_PT_QUERY_ALPHA_STOCHASTIC)
+    return c;
+  if(o->cull != MI_PT_QUERY_CULL_NONE && o->cull != MI_PT_QUERY_CULL_MATERIAL)
+    return c;
+  if(o->mode == MI_PT_QUERY_NEAREST_K ? (o->maxHits < 1 || o->maxHits > MI_PT_QUERY_MAX_HITS) : (o->maxHits != 0 && o->maxHits != 1))
+    return c;
+  if(o->alpha == MI_PT_QUERY_ALPHA_CUTOFF && !(o->blendThreshold > 0.0f && o->blendThreshold <= 1.0f))  // (NaN fails too)
+    return c;
+  c.valid                = true;
+  c.rules.alpha          = o->alpha;
+  c.rules.cull           = o->cull;
+  c.rules.maxHits        = o->mode == MI_PT_QUERY_NEAREST_K ? o->maxHits : 1;
+  c.rules.blendThreshold = o->blendThreshold;
+  c.rules.seed           = o->seed;
+  c.any                  = o->mode == MI_PT_QUERY_ANY;
+  return c;
+}
+int failQuery(const QueryCall& c, int code, const std::string& what) { return fail(code, std::string(c.who) + ": " + what); }
+// An alpha-aware walk reads the alpha record of every triangle without INST_FORCE_OPAQUE / INST_ALPHA_PASSES.  Such a triangle sets hasAlphaTest,
+// hence hasAlpha, under which the build and the material patch keep the records (buildAccelerationOver, patchTriangleData): checked, not assumed.
+bool queryAlphaRecordsMissing(const MiPt* pt, const pt::QueryRules& rules)
+{
+  return rules.alpha != MI_PT_QUERY_ALPHA_OPAQUE && pt->hasAlphaTest && pt->scene.numTris > 0 && !pt->scene.alphaTris;
+}
+const char* const QUERY_NO_ALPHA_RECORDS = "the scene has alpha-tested triangles but no alpha records";
+int queryStaging(MiPt* pt, size_t numRays, size_t numHits)
 {
   if(numRays > pt->queryRays.count)
     HIP_TRY(pt->queryRays.alloc(numRays));
@@ -2491,99 +2546,94 @@ int queryStagingEx(MiPt* pt, size_t numRays, size_t numHits)
     HIP_TRY(pt->queryHits.alloc(numHits));
   return MI_PT_OK;
 }
-int  queryStaging(MiPt* pt, size_t n) { return queryStagingEx(pt, n, n); }
-bool queryModeKnown(int mode) { return mode == MI_PT_QUERY_CLOSEST || mode == MI_PT_QUERY_ANY; }
-// The rules of a valid MiPtQueryOptions (rules.maxHits: the records per ray); false for what the header refuses.
-bool queryRulesOf(const MiPtQueryOptions* o, pt::QueryRules& rules)
-{
-  if(!o || o->reserved[0] != 0 || o->reserved[1] != 0)
-    return false;
-  if(!(queryModeKnown(o->mode) || o->mode == MI_PT_QUERY_NEAREST_K))
-    return false;
-  if(o->alpha != MI_PT_QUERY_ALPHA_OPAQUE && o->alpha != MI_PT_QUERY_ALPHA_CUTOFF && o->alpha != MI_PT_QUERY_ALPHA_STOCHASTIC)
-    return false;
-  if(o->cull != MI_PT_QUERY_CULL_NONE && o->cull != MI_PT_QUERY_CULL_MATERIAL)
-    return false;
-  if(o->mode == MI_PT_QUERY_NEAREST_K ? (o->maxHits < 1 || o->maxHits > MI_PT_QUERY_MAX_HITS) : (o->maxHits != 0 && o->maxHits != 1))
-    return false;
-  if(o->alpha == MI_PT_QUERY_ALPHA_CUTOFF && !(o->blendThreshold > 0.0f && o->blendThreshold <= 1.0f))  // (NaN fails too)
-    return false;
-  rules.alpha          = o->alpha;
-  rules.cull           = o->cull;
-  rules.maxHits        = o->mode == MI_PT_QUERY_NEAREST_K ? o->maxHits : 1;
-  rules.blendThreshold = o->blendThreshold;
-  rules.seed           = o->seed;
-  return true;
-}
-// An alpha-aware walk reads the alpha record of every triangle without INST_FORCE_OPAQUE / INST_ALPHA_PASSES.  Such a triangle sets hasAlphaTest,
-// hence hasAlpha, under which the build and the material patch keep the records (buildAccelerationOver, patchTriangleData): checked, not assumed.
-bool queryAlphaRecordsMissing(const MiPt* pt, const pt::QueryRules& rules)
-{
-  return rules.alpha != MI_PT_QUERY_ALPHA_OPAQUE && pt->hasAlphaTest && pt->scene.numTris > 0 && !pt->scene.alphaTris;
-}
-}  // namespace
 
-int mi_pt_query_rays(MiPt* pt, const MiPtRay* hostRays, int numRays, int mode, MiPtRayHit* hostHits)
+int queryHostRays(MiPt* pt, const QueryCall& c, const MiPtRay* hostRays, int numRays, MiPtRayHit* hostHits)
 {
   FLUSH_PENDING(pt);
-  if(!pt || numRays < 0 || !queryModeKnown(mode) || (numRays > 0 && (!hostRays || !hostHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays: bad arguments");
+  if(!pt || numRays < 0 || !c.valid || (numRays > 0 && (!hostRays || !hostHits)))
+    return failQuery(c, MI_PT_ERR_ARGUMENT, "bad arguments");
+  if(queryAlphaRecordsMissing(pt, c.rules))
+    return failQuery(c, MI_PT_ERR_STATE, QUERY_NO_ALPHA_RECORDS);
   if(numRays == 0)
     return MI_PT_OK;
+  const size_t numHits = size_t(numRays) * size_t(c.rules.maxHits);
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
-  if(int rc = queryStaging(pt, size_t(numRays)))
+  if(int rc = queryStaging(pt, size_t(numRays), numHits))
     return rc;
   HIP_TRY(hipMemcpy(pt->queryRays.ptr, hostRays, size_t(numRays) * sizeof(MiPtRay), hipMemcpyHostToDevice));
-  pt::launchQueryRays(pt->scene, pt->wide, mode == MI_PT_QUERY_ANY, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
+  pt::launchQueryRaysEx(pt->scene, pt->wide, c.any, c.rules, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, size_t(numRays) * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
-int mi_pt_query_rays_device(MiPt* pt, const void* deviceRays, int numRays, int mode, void* deviceHits, void* hipStream)
+int queryDeviceRays(MiPt* pt, const QueryCall& c, const void* deviceRays, int numRays, void* deviceHits, void* hipStream)
 {
   FLUSH_PENDING(pt);
-  if(!pt || numRays < 0 || !queryModeKnown(mode) || (numRays > 0 && (!deviceRays || !deviceHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device: bad arguments");
+  if(!pt || numRays < 0 || !c.valid || (numRays > 0 && (!deviceRays || !deviceHits)))
+    return failQuery(c, MI_PT_ERR_ARGUMENT, "bad arguments");
   if(numRays > 0 && ((reinterpret_cast<uintptr_t>(deviceRays) | reinterpret_cast<uintptr_t>(deviceHits)) & 15u))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device: rays and hits must be 16-byte aligned");
+    return failQuery(c, MI_PT_ERR_ARGUMENT, "rays and hits must be 16-byte aligned");
+  if(queryAlphaRecordsMissing(pt, c.rules))
+    return failQuery(c, MI_PT_ERR_STATE, QUERY_NO_ALPHA_RECORDS);
   if(numRays == 0)
     return MI_PT_OK;
   HIP_TRY(hipSetDevice(pt->device));
-  pt::launchQueryRays(pt->scene, pt->wide, mode == MI_PT_QUERY_ANY, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays), static_cast<MiPtRayHit*>(deviceHits),
-                      reinterpret_cast<hipStream_t>(hipStream));
+  pt::launchQueryRaysEx(pt->scene, pt->wide, c.any, c.rules, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays), static_cast<MiPtRayHit*>(deviceHits),
+                        reinterpret_cast<hipStream_t>(hipStream));
   HIP_TRY(hipGetLastError());
   return MI_PT_OK;
 }
-int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHits)
+int queryPixels(MiPt* pt, const QueryCall& c, const float* pixelXY, int numPixels, MiPtRayHit* hostHits)
 {
   FLUSH_PENDING(pt);
-  if(!pt || numPixels < 0 || (numPixels > 0 && (!pixelXY || !hostHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick: bad arguments");
+  if(!pt || numPixels < 0 || !c.valid || (numPixels > 0 && (!pixelXY || !hostHits)))
+    return failQuery(c, MI_PT_ERR_ARGUMENT, "bad arguments");
   if(pt->width <= 0 || !pt->haveFrameInfo)
-    return fail(MI_PT_ERR_STATE, "mi_pt_pick: call mi_pt_resize and mi_pt_set_frame_info first");
+    return failQuery(c, MI_PT_ERR_STATE, "call mi_pt_resize and mi_pt_set_frame_info first");
   for(int i = 0; i < numPixels; ++i)
   {
     const float x = pixelXY[2 * i], y = pixelXY[2 * i + 1];
     if(!(x >= 0.0f && x < float(pt->width) && y >= 0.0f && y < float(pt->height)))  // (NaN fails too)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick: pixel " + std::to_string(i) + " lies outside the image");
+      return failQuery(c, MI_PT_ERR_ARGUMENT, "pixel " + std::to_string(i) + " lies outside the image");
   }
+  if(queryAlphaRecordsMissing(pt, c.rules))
+    return failQuery(c, MI_PT_ERR_STATE, QUERY_NO_ALPHA_RECORDS);
   if(numPixels == 0)
     return MI_PT_OK;
+  // The pixel positions are staged in queryRays (8 bytes each: a quarter of a ray record): at its front under plain rules, which walk the camera
+  // rays where they are formed; behind the numPixels ray records the camera rays are written to otherwise.
+  const size_t n = size_t(numPixels), numHits = n * size_t(c.rules.maxHits);
+  const bool   scratch = !pt::queryRulesPlain(c.rules);
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
-  if(int rc = queryStaging(pt, size_t(numPixels)))
+  if(int rc = queryStaging(pt, scratch ? n + (n + 3) / 4 : n, numHits))
     return rc;
-  HIP_TRY(hipMemcpy(pt->queryRays.ptr, pixelXY, size_t(numPixels) * sizeof(float2), hipMemcpyHostToDevice));
+  float2* xy = reinterpret_cast<float2*>(pt->queryRays.ptr + (scratch ? n : 0));
+  HIP_TRY(hipMemcpy(xy, pixelXY, n * sizeof(float2), hipMemcpyHostToDevice));
   pt::FrameConsts fc;
   memset(&fc, 0, sizeof(fc));
   fc.frameInfo = pt->frameInfo;
   fc.width     = pt->width;
   fc.height    = pt->height;
-  pt::launchPickRays(pt->scene, fc, pt->wide, reinterpret_cast<const float2*>(pt->queryRays.ptr), uint32_t(numPixels), pt->queryHits.ptr, nullptr);
+  pt::launchPickRaysEx(pt->scene, fc, pt->wide, c.rules, xy, scratch ? pt->queryRays.ptr : nullptr, uint32_t(numPixels), pt->queryHits.ptr, nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, size_t(numPixels) * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
   return MI_PT_OK;
+}
+}  // namespace
+
+int mi_pt_query_rays(MiPt* pt, const MiPtRay* hostRays, int numRays, int mode, MiPtRayHit* hostHits)
+{
+  return queryHostRays(pt, queryCallOfMode("mi_pt_query_rays", mode), hostRays, numRays, hostHits);
+}
+int mi_pt_query_rays_device(MiPt* pt, const void* deviceRays, int numRays, int mode, void* deviceHits, void* hipStream)
+{
+  return queryDeviceRays(pt, queryCallOfMode("mi_pt_query_rays_device", mode), deviceRays, numRays, deviceHits, hipStream);
+}
+int mi_pt_pick(MiPt* pt, const float* pixelXY, int numPixels, MiPtRayHit* hostHits)
+{
+  return queryPixels(pt, queryCallOfMode("mi_pt_pick", MI_PT_QUERY_CLOSEST), pixelXY, numPixels, hostHits);
 }
 void mi_pt_default_query_options(MiPtQueryOptions* options)
 {
@@ -2598,78 +2648,15 @@ void mi_pt_default_query_options(MiPtQueryOptions* options)
 }
 int mi_pt_query_rays_ex(MiPt* pt, const MiPtRay* hostRays, int numRays, const MiPtQueryOptions* options, MiPtRayHit* hostHits)
 {
-  FLUSH_PENDING(pt);
-  pt::QueryRules rules;
-  if(!pt || numRays < 0 || !queryRulesOf(options, rules) || (numRays > 0 && (!hostRays || !hostHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_ex: bad arguments");
-  if(queryAlphaRecordsMissing(pt, rules))
-    return fail(MI_PT_ERR_STATE, "mi_pt_query_rays_ex: the scene has alpha-tested triangles but no alpha records");
-  if(numRays == 0)
-    return MI_PT_OK;
-  const size_t numHits = size_t(numRays) * size_t(rules.maxHits);
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if(int rc = queryStagingEx(pt, size_t(numRays), numHits))
-    return rc;
-  HIP_TRY(hipMemcpy(pt->queryRays.ptr, hostRays, size_t(numRays) * sizeof(MiPtRay), hipMemcpyHostToDevice));
-  pt::launchQueryRaysEx(pt->scene, pt->wide, options->mode == MI_PT_QUERY_ANY, rules, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return queryHostRays(pt, queryCallOf("mi_pt_query_rays_ex", options), hostRays, numRays, hostHits);
 }
 int mi_pt_query_rays_device_ex(MiPt* pt, const void* deviceRays, int numRays, const MiPtQueryOptions* options, void* deviceHits, void* hipStream)
 {
-  FLUSH_PENDING(pt);
-  pt::QueryRules rules;
-  if(!pt || numRays < 0 || !queryRulesOf(options, rules) || (numRays > 0 && (!deviceRays || !deviceHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device_ex: bad arguments");
-  if(numRays > 0 && ((reinterpret_cast<uintptr_t>(deviceRays) | reinterpret_cast<uintptr_t>(deviceHits)) & 15u))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_query_rays_device_ex: rays and hits must be 16-byte aligned");
-  if(queryAlphaRecordsMissing(pt, rules))
-    return fail(MI_PT_ERR_STATE, "mi_pt_query_rays_device_ex: the scene has alpha-tested triangles but no alpha records");
-  if(numRays == 0)
-    return MI_PT_OK;
-  HIP_TRY(hipSetDevice(pt->device));
-  pt::launchQueryRaysEx(pt->scene, pt->wide, options->mode == MI_PT_QUERY_ANY, rules, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays),
-                        static_cast<MiPtRayHit*>(deviceHits), reinterpret_cast<hipStream_t>(hipStream));
-  HIP_TRY(hipGetLastError());
-  return MI_PT_OK;
+  return queryDeviceRays(pt, queryCallOf("mi_pt_query_rays_device_ex", options), deviceRays, numRays, deviceHits, hipStream);
 }
 int mi_pt_pick_ex(MiPt* pt, const float* pixelXY, int numPixels, const MiPtQueryOptions* options, MiPtRayHit* hostHits)
 {
-  FLUSH_PENDING(pt);
-  pt::QueryRules rules;
-  if(!pt || numPixels < 0 || !queryRulesOf(options, rules) || (numPixels > 0 && (!pixelXY || !hostHits)))
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick_ex: bad arguments");
-  if(pt->width <= 0 || !pt->haveFrameInfo)
-    return fail(MI_PT_ERR_STATE, "mi_pt_pick_ex: call mi_pt_resize and mi_pt_set_frame_info first");
-  for(int i = 0; i < numPixels; ++i)
-  {
-    const float x = pixelXY[2 * i], y = pixelXY[2 * i + 1];
-    if(!(x >= 0.0f && x < float(pt->width) && y >= 0.0f && y < float(pt->height)))  // (NaN fails too)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_pick_ex: pixel " + std::to_string(i) + " lies outside the image");
-  }
-  if(queryAlphaRecordsMissing(pt, rules))
-    return fail(MI_PT_ERR_STATE, "mi_pt_pick_ex: the scene has alpha-tested triangles but no alpha records");
-  if(numPixels == 0)
-    return MI_PT_OK;
-  // the pixel positions are staged behind the ray records the camera rays are written to (8 bytes each: a quarter of a ray record)
-  const size_t numHits = size_t(numPixels) * size_t(rules.maxHits), xyRays = (size_t(numPixels) + 3) / 4;
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if(int rc = queryStagingEx(pt, size_t(numPixels) + xyRays, numHits))
-    return rc;
-  float2* xy = reinterpret_cast<float2*>(pt->queryRays.ptr + numPixels);
-  HIP_TRY(hipMemcpy(xy, pixelXY, size_t(numPixels) * sizeof(float2), hipMemcpyHostToDevice));
-  pt::FrameConsts fc;
-  memset(&fc, 0, sizeof(fc));
-  fc.frameInfo = pt->frameInfo;
-  fc.width     = pt->width;
-  fc.height    = pt->height;
-  pt::launchPickRaysEx(pt->scene, fc, pt->wide, rules, xy, pt->queryRays.ptr, uint32_t(numPixels), pt->queryHits.ptr, nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return queryPixels(pt, queryCallOf("mi_pt_pick_ex", options), pixelXY, numPixels, hostHits);
 }
 int mi_pt_read_depth(MiPt* pt, float* host)
 {

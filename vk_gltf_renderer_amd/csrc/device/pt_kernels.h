@@ -50,14 +50,12 @@ void launchTraceShadow(const LaunchCtx& c, int nxt);  // nxt: active queue the p
 void launchFlushSurvivors(const LaunchCtx& c, int cur);  // cur: the active queue the last shade launch appended to (paths alive when the bounce loop stopped)
 void launchFinishSample(const LaunchCtx& c, int sampleIndex, float4* accum, float* depth, float4* albedo, float4* normal);
 void launchSelection(const LaunchCtx& c, uint32_t* selection);
-// ray queries and picking (query.hip, pt_query.h): one ray per lane over the resident structure (`wide`: the 8-wide tree), every triangle opaque, no
-// culling; `any`: stop at the first accepted triangle.  rays / xy / hits are device memory, 16 / 8 / 16-byte aligned.  launchPickRays forms ray i as
-// the camera ray of the continuous pixel position xy[i] under fc.frameInfo / fc.width / fc.height (nothing else of fc is read)
-void launchQueryRays(const DevScene& scene, bool wide, bool any, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
-void launchPickRays(const DevScene& scene, const FrameConsts& fc, bool wide, const float2* xy, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
-// the same under the rules of a MiPtQueryOptions (pt_query.h: QueryRules -- face culling, alpha mode, q.maxHits records per ray: hits holds numRays x
-// q.maxHits).  any: MI_PT_QUERY_ANY (q.maxHits is 1 then).  Opaque, unculled single-hit rules run the kernels of the two launchers above.
-// rayScratch: numRays ray records, 16-byte aligned, that launchPickRaysEx writes the camera rays to.
+// ray queries and picking (query.hip, pt_query.h): one ray per lane over the resident structure (`wide`: the 8-wide tree) under the rules of a
+// MiPtQueryOptions (pt_query.h: QueryRules -- face culling, alpha mode, q.maxHits records per ray: hits holds numRays x q.maxHits).  any:
+// MI_PT_QUERY_ANY, stop at the first accepted triangle (q.maxHits is 1 then).  The plain entry points are these under queryRulesPlain rules, which
+// run kernels of their own.  rays / xy / hits are device memory, 16 / 8 / 16-byte aligned.  launchPickRaysEx forms ray i as the camera ray of the
+// continuous pixel position xy[i] under fc.frameInfo / fc.width / fc.height (nothing else of fc is read).  rayScratch: numRays ray records, 16-byte
+// aligned, that it writes the camera rays to; not touched, and may be null, under plain rules.
 struct QueryRules;
 void launchQueryRaysEx(const DevScene& scene, bool wide, bool any, const QueryRules& q, const MiPtRay* rays, uint32_t numRays, MiPtRayHit* hits, hipStream_t s);
 void launchPickRaysEx(const DevScene& scene, const FrameConsts& fc, bool wide, const QueryRules& q, const float2* xy, MiPtRay* rayScratch, uint32_t numRays,

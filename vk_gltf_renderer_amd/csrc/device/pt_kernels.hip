@@ -13,6 +13,7 @@
 #include "pt_shading.h"
 #include "pt_bvh.h"
 #include "pt_bvh8.h"
+#include "pt_lane_walk.h"
 #include "pt_camera.h"
 #include "pt_packet.h"
 #include "pt_feed.h"
@@ -1475,6 +1476,8 @@ __global__ void __launch_bounds__(256, INTERVAL ? PRIMARY_INTERVAL_MIN_WAVES : P
 
 //================================================================================================================================
 // k_selection: traceSelectionRay / TraceLow (pathtrace_functions.h.slang:813-820, raytracer_interface.h.slang:124-137)
+// One camera ray per lane through the pixel centre; the walk is the per-lane walk the ray queries use (pt_lane_walk.h), the candidate rule is its own:
+// only the render node of the closest hit is kept.
 //================================================================================================================================
 template <bool WIDE>
 __global__ void __launch_bounds__(SEL_BLOCK) k_selection(DevScene sc, FrameConsts fc, const uint32_t* ownedTiles, uint32_t* selection)
@@ -1494,54 +1497,16 @@ __global__ void __launch_bounds__(SEL_BLOCK) k_selection(DevScene sc, FrameConst
     const DevTri T = sc.tris[triIndex];
     TriHit       h;
     if(!intersectTri(xyz(T.a), xyz(T.b), xyz(T.c), r.org, r.dir, h) || !(h.t > 0.0f))
-      return;
+      return false;
     const uint32_t rnode = __float_as_uint(T.a.w), prim = __float_as_uint(T.b.w);
     if(h.t < bestT || (h.t == bestT && (rnode < bestRnode || (rnode == bestRnode && prim < bestPrim))))
     {
       bestT = h.t; bestRnode = rnode; bestPrim = prim;
     }
+    return true;
   };
   if(sc.bvhRoot != BVH_EMPTY)
-  {
-    if(WIDE)
-    {
-      LaneStack2 st2;
-      uint32_t   stackOverflow[2 * BVH8_STACK_PRIV];
-      st2.lds = s_stack; st2.tid = int(threadIdx.x); st2.stride = SEL_BLOCK; st2.sp = 0;
-      st2.privBase = stackOverflow; st2.privBits = stackOverflow + BVH8_STACK_PRIV;
-      const uint32_t octinv = rayOctInv(r.idir);
-      NodeGroup      G      = rootGroup(octinv);
-      for(;;)
-      {
-        if((G.bits >> 8) == 0u)
-        {
-          if(st2.sp == 0)
-            break;
-          G = st2.pop();
-        }
-        const uint32_t child = groupPopChild(G, octinv);
-        if(G.bits >> 8)
-          st2.push(G);
-        uint32_t tBase, tMask;
-        bvh8Visit(sc, r, bestT, octinv, child, G, tBase, tMask, nullptr, 0u);
-        while(leafPending(tMask))
-        {
-          const int k = int(leafPop(tMask, 0u));  // (offset from the node's first triangle)
-          testTri(int(tBase) + k);
-        }
-      }
-    }
-    else
-    {
-      LaneStack st;
-      int       stackOverflow[BVH_STACK_PRIV];
-      st.lds = s_stack; st.tid = int(threadIdx.x); st.stride = SEL_BLOCK; st.sp = 0; st.priv = stackOverflow;
-      bvhWalk(sc, r, bestT, st, [&](int triIndex, float) -> float {
-        testTri(triIndex);
-        return bestT;
-      });
-    }
-  }
+    laneWalk<WIDE, false, SEL_BLOCK>(sc, r, bestT, s_stack, testTri, [&] { return bestT; });
   selection[size_t(py) * size_t(fc.width) + size_t(px)] = (bestRnode != 0xffffffffu) ? bestRnode + 1u : 0u;
 }
 

@@ -1,7 +1,10 @@
 // Ray queries against the resident scene (mi_pt_query_rays / mi_pt_query_rays_device / mi_pt_pick, include/mi_pt.h): everything per ray that
-// is not the walk -- ray validation, the acceptance test, the closest-hit rule and the hit record.  Plain PT_DEV code: query.hip runs it per
-// lane, tests/host_shim/query_on_host.cpp compiles it for the CPU.  The second half is the per-ray work of the _ex entry points (face culling, the
-// alpha decision, the sorted list of the K nearest distinct triangles): tests/host_shim/query_ex_on_host.cpp.
+// is not the walk (pt_lane_walk.h) -- ray validation, the acceptance test, the closest-hit rule and the hit record.  Plain PT_DEV code: query.hip
+// runs it per lane, tests/host_shim/query_on_host.cpp compiles it for the CPU.  The second half is the per-ray work of the _ex entry points (face
+// culling, the alpha decision, the sorted list of the K nearest distinct triangles): tests/host_shim/query_ex_on_host.cpp.
+// The two candidate tests (queryTestTri, queryTestTriEx) still open with the same intersect / accept / decode lines, and queryOne / queryOneEx
+// (query.hip) with the same validation and setup, which the shims' `brute` functions re-type: folding either moved the register counts of the
+// compiled kernels (LABNOTES.md, "One per-lane walk for the query calls and the selection pass"), so they stay as they are.
 #pragma once
 #include "pt_bvh.h"
 #include "pt_shading.h"  // getOpacityFast
@@ -108,6 +111,9 @@ struct QueryRules
   float    blendThreshold;
   uint32_t seed;
 };
+// The rules of the plain entry points -- every triangle opaque, no culling, one record per ray: the plain kernels serve them (query.hip), and a
+// pick under them needs no ray scratch (mi_pt_api.hip).
+inline bool queryRulesPlain(const QueryRules& q) { return q.alpha == MI_PT_QUERY_ALPHA_OPAQUE && q.cull == MI_PT_QUERY_CULL_NONE && q.maxHits == 1; }
 // The frames' camera-ray rule (pt_kernels.hip, triRoundFinish): a triangle that shows the ray the back of its OBJECT-space winding is culled unless
 // its instance disables culling.  worldFront: TriHit::front.
 PT_DEV bool queryCullPasses(uint32_t instFlags, bool worldFront, int32_t cull)
