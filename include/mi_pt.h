@@ -449,13 +449,14 @@ MI_PT_API int mi_pt_denoise_temporal(MiPt* pt, const MiPtTemporalParams* params,
 MI_PT_API int mi_pt_reset_history(MiPt* pt);
 
 /* Vertex motion: carries skinned and morphed vertices in the motion image (our own; the reference moves a mesh hit with its render node alone).
- * Off by default, and inert until mi_pt_set_temporal AND mi_pt_set_deformation are in force too -- the three may be called in any order; while it is not
+ * Off by default, and inert until mi_pt_set_temporal AND mi_pt_set_deformation (or mi_pt_set_vertex_updates) are in force too -- in any order; while it is not
  * in force nothing is allocated and every image, read-back and byte of memory is what it is without it.  In force:
  *   - every MI_PT_FIRST_FRAME batch records, next to the first hit, its triangle (16 B per owned pixel slot, in rendererBytes);
  *   - the object-space positions of the pose rendered before are kept for every deforming render primitive (12 B per vertex, each primitive's array
  *     padded to 16 B, + 32 B per render primitive of the scene + 4 B per deforming one, in sceneBytes), initialised to the resident positions here and by
  *     every mi_pt_set_deformation, and copied from the resident positions on the batch's stream after the motion kernel of a MI_PT_FIRST_FRAME batch --
- *     only when mi_pt_update_deformation ran since the last copy: they follow the RENDERED pose, not the update calls;
+ *     only when mi_pt_update_deformation (or mi_pt_update_vertices[_device]) ran since the last copy: they follow the RENDERED pose, not the update calls.
+ *     The primitives declared by mi_pt_set_vertex_updates count as deforming ones here;
  *   - a mesh hit on such a primitive gets, as its previous world position, prevObjectToWorld x (b0 p0 + b1 p1 + b2 p2): p the previous positions of the
  *     hit triangle's vertices, b the hit's barycentrics.  A triangle whose nine previous floats equal its nine current ones BIT FOR BIT takes the rigid
  *     path instead (a still character, the first pose, an update with unchanged tables), so zero motion stays exactly zero; so do hits on primitives
@@ -468,8 +469,60 @@ MI_PT_API int mi_pt_set_vertex_motion(MiPt* pt, int enable);
  * owns.  MI_PT_ERR_STATE while vertex motion is not in force or before the first such batch after it came into force. */
 MI_PT_API int mi_pt_read_first_hit_triangle(MiPt* pt, uint32_t* hostPrimTriB1B2);
 /* The previous-pose positions of a deforming render primitive (vertexCount x 3 floats).  MI_PT_ERR_STATE while vertex motion is not in force,
- * MI_PT_ERR_ARGUMENT for a render primitive the deformation tables do not deform. */
+ * MI_PT_ERR_ARGUMENT for a render primitive that neither the deformation tables deform nor mi_pt_set_vertex_updates declares. */
 MI_PT_API int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Caller-driven vertices: new positions (and normals, tangents) for resident render primitives, from host or device memory -- a cloth or
+ * soft-body step, a vertex cache, a procedural wave, a mesh a model moves on the same GPU (our own; the reference re-uploads the buffers of a
+ * changed primitive).  The counterpart of mi_pt_read_vertices, and the front of the pipeline mi_pt_update_deformation feeds: the in-place
+ * refit, the deferred build, the previous positions of vertex motion, queries that see the current pose.
+ * A vertex write is exactly the bytes mi_pt_create would upload for the same arrays: the separate position / normal / tangent streams and the
+ * interleaved record the shade kernels read.  A stream that is not supplied (and not rebuilt) keeps its bytes.  The frames and queries that
+ * follow return, bit for bit, what a fresh instance created from the same tables with these vertices returns. */
+enum { MI_PT_VERTICES_RECOMPUTE_NORMALS = 1 }; /* mi_pt_set_vertex_updates flags */
+typedef struct MiPtVertexUpdate
+{
+  int32_t      renderPrimID;
+  uint32_t     vertexCount; /* must equal the resident primitive's */
+  const float* positions;   /* 3 / vertex, tightly packed, required */
+  const float* normals;     /* 3 / vertex or NULL = keep (or rebuild, see flags) */
+  const float* tangents;    /* 4 / vertex or NULL = keep */
+  uint32_t     reserved[2]; /* 0 */
+} MiPtVertexUpdate;
+/* Declares, once, which render primitives the caller drives (count 0 or NULL releases the declaration and its tables).  Ids out of range or
+ * repeated, a primitive of the deformation tables, a primitive without positions, unknown flag bits: MI_PT_ERR_ARGUMENT, nothing changed
+ * (mi_pt_set_deformation in turn refuses a primitive declared here).  With MI_PT_VERTICES_RECOMPUTE_NORMALS the vertex-to-incident-corner
+ * table of every declared primitive that has a normal stream is built from the resident index buffer and uploaded: 4 B per corner + 4 B per
+ * vertex, in MiPtMemory::sceneBytes, reported as tableBytes (the task tables of the update calls, some tens of bytes per declared primitive
+ * + 4 B per 256 vertices, are in sceneBytes too).  Flushes the frame queue and synchronises like mi_pt_set_deformation; nothing moves yet. */
+MI_PT_API int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, int flags);
+/* New vertices for some or all of the declared primitives; the stream pointers are host memory.  MI_PT_ERR_STATE without a declaration.
+ * MI_PT_ERR_ARGUMENT, with nothing changed: an undeclared or repeated primitive, a wrong vertexCount, NULL positions, normals / tangents for
+ * a stream the primitive does not have, a non-zero reserved word, flag bits other than MI_PT_DEFORM_DEFER_BUILD, a non-finite component in
+ * any supplied array.  All primitives of a call are written by ONE launch.  The arrays are staged through a device buffer allocated by the
+ * first call and grown, never shrunk (in rendererBytes from then on).  A primitive declared with MI_PT_VERTICES_RECOMPUTE_NORMALS that has a
+ * normal stream and gets normals == NULL has its normals rebuilt by a second launch: per vertex the float32 sum of cross(p1 - p0, p2 - p0) over
+ * its incident corners (ascending triangle, then corner; unnormalised, so weighted by area) divided by its length; a vertex whose sum has zero
+ * or non-finite length keeps its normal.  Tangents are never rebuilt: a caller whose normal-mapped surface bends supplies them.
+ * Then the acceleration structure follows as after mi_pt_update_deformation (mi_pt_set_accel_update) -- unless flags holds
+ * MI_PT_DEFORM_DEFER_BUILD, for a caller that calls mi_pt_update_render_nodes next.  Synchronises with the work in flight (queued frames
+ * render the old vertices); the caller restarts accumulation. */
+MI_PT_API int mi_pt_update_vertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpdates, int flags);
+/* The same over device memory: `updates` itself is host memory, its stream pointers device memory of pt's device (4-byte aligned).  Allocates
+ * nothing and makes no host copy of the streams.  The call's device synchronisation covers whatever stream produced the arrays: no stream
+ * argument.  The host cannot validate device data, so the kernel rejects per vertex: a vertex with any non-finite supplied component keeps
+ * ALL its resident values and is counted (MiPtVertexUpdateInfo::verticesRejected); the call succeeds.  A non-finite position never reaches
+ * the refit or the builder. */
+MI_PT_API int mi_pt_update_vertices_device(MiPt* pt, const MiPtVertexUpdate* updates, int numUpdates, int flags);
+typedef struct MiPtVertexUpdateInfo
+{
+  uint64_t calls;            /* successful update calls of this instance, both forms */
+  uint64_t verticesWritten;  /* vertices they wrote, in total */
+  uint64_t verticesRejected; /* vertices the LAST call rejected (always 0 for the host form, which refuses the whole call instead) */
+  uint64_t tableBytes;       /* the incident-corner tables of the declaration in force */
+} MiPtVertexUpdateInfo;
+MI_PT_API int mi_pt_get_vertex_update_info(MiPt* pt, MiPtVertexUpdateInfo* info);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Ray queries and picking against the resident scene (replaces nvvk::RayPicker over the TLAS: reference src/ui_renderer.cpp:95-150).
@@ -630,7 +683,8 @@ MI_PT_API const char* mi_pt_version(void);
  *    mi_pt_reset_history).  (Still 9: mi_pt_set_vertex_motion, mi_pt_read_first_hit_triangle, mi_pt_read_previous_positions -- new entry points, no
  *    struct a caller allocates changed.  Still 9: MiPtRay / MiPtRayHit and mi_pt_query_rays, mi_pt_query_rays_device, mi_pt_pick -- new types and
  *    entry points, no struct a caller already allocates changed.  Still 9: MiPtQueryOptions and mi_pt_default_query_options, mi_pt_query_rays_ex,
- *    mi_pt_query_rays_device_ex, mi_pt_pick_ex -- again new types and entry points only.) */
+ *    mi_pt_query_rays_device_ex, mi_pt_pick_ex -- again new types and entry points only.  Still 9: MiPtVertexUpdate / MiPtVertexUpdateInfo and
+ *    mi_pt_set_vertex_updates, mi_pt_update_vertices, mi_pt_update_vertices_device, mi_pt_get_vertex_update_info -- new types and entry points only.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

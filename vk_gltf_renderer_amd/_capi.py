@@ -172,6 +172,15 @@ class MiPtQueryOptions(C.Structure):
     _fields_ = [("mode", i32), ("alpha", i32), ("cull", i32), ("maxHits", i32), ("blendThreshold", f32), ("seed", u32), ("reserved", i32 * 2)]
 
 
+class MiPtVertexUpdate(C.Structure):
+    _fields_ = [("renderPrimID", i32), ("vertexCount", u32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("tangents", C.c_void_p),
+                ("reserved", u32 * 2)]
+
+
+class MiPtVertexUpdateInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "verticesWritten", "verticesRejected", "tableBytes")]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -187,9 +196,12 @@ assert C.sizeof(MiPtAccelResidentInfo) == 40
 assert C.sizeof(MiPtRay) == 32
 assert C.sizeof(MiPtRayHit) == 64
 assert C.sizeof(MiPtQueryOptions) == 32
+assert C.sizeof(MiPtVertexUpdate) == 40
+assert C.sizeof(MiPtVertexUpdateInfo) == 32
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
+MI_PT_VERTICES_RECOMPUTE_NORMALS = 1
 # mi_scene_animation_changes (include/mi_host.h)
 (MI_SCENE_CHANGED_NODES, MI_SCENE_CHANGED_LIGHTS, MI_SCENE_CHANGED_DEFORMATION, MI_SCENE_CHANGED_MATERIALS, MI_SCENE_CHANGED_CAMERAS,
  MI_SCENE_CHANGED_VISIBILITY) = 1, 2, 4, 8, 16, 32
@@ -336,6 +348,10 @@ PT_SYMBOLS = {
     "mi_pt_query_rays_ex": (i32, [VP, P(MiPtRay), i32, P(MiPtQueryOptions), P(MiPtRayHit)]),
     "mi_pt_query_rays_device_ex": (i32, [VP, VP, i32, P(MiPtQueryOptions), VP, VP]),
     "mi_pt_pick_ex": (i32, [VP, P(f32), i32, P(MiPtQueryOptions), P(MiPtRayHit)]),
+    "mi_pt_set_vertex_updates": (i32, [VP, P(i32), i32, i32]),
+    "mi_pt_update_vertices": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
+    "mi_pt_update_vertices_device": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
+    "mi_pt_get_vertex_update_info": (i32, [VP, P(MiPtVertexUpdateInfo)]),
 }
 
 

@@ -20,6 +20,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_deform.h"
+#include "pt_vertex_update.h"
 #include "pt_kernels.h"
 #include "pt_query.h"
 
@@ -209,6 +210,18 @@ struct MiPt
   uint32_t                      deformBlocks = 0;
   bool                          deformSet = false;
   std::vector<int>              deformPrimIDs;  // the render primitives the deformation tables deform
+  // caller-driven vertices (mi_pt_set_vertex_updates): everything below exists only while primitives are declared
+  bool                          vuSet = false;
+  std::vector<int>              vuPrimIDs;      // the declared render primitives
+  std::vector<uint8_t>          vuDeclared;     // per render primitive: declared
+  std::vector<size_t>           vuCornerEnd, vuCorners;  // per render primitive: word offsets of its incident-corner table in vuTable, SIZE_MAX = none
+  DevBuf<uint32_t>              vuTable;        // the incident-corner tables (MI_PT_VERTICES_RECOMPUTE_NORMALS): per primitive V run ends, then 3 T corners
+  DevBuf<pt::VertexUpdateTask>  vuTasks;        // task tables of an update call, sized for a call that carries every declared primitive
+  DevBuf<pt::NormalRebuildTask> vuNormalTasks;
+  DevBuf<uint32_t>              vuBlockTask;    // [0, vuBlockCap): the ingest's blocks, [vuBlockCap, 2 vuBlockCap): the rebuild's; the last word: rejected vertices
+  size_t                        vuBlockCap = 0;
+  DevBuf<uint8_t>               vuStaging;      // the host form's arrays: allocated by the first such call and grown (rendererBytes)
+  uint64_t                      vuCalls = 0, vuWritten = 0, vuRejected = 0;
   int                           bvhBuilder = 0;
   // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
   int                           accelMode = MI_PT_ACCEL_REBUILD;
@@ -272,7 +285,7 @@ struct MiPt
   DevBuf<float4>          motion, history;       // history: 2 sets x 3 records x pixels
   DevBuf<float>           prevObjectToWorld;     // 16 floats per render node: the matrices of the pose rendered before
   std::vector<uint32_t>   ownedTilesHost;        // host copy of ownedTiles (mi_pt_read_first_hit)
-  // vertex motion (mi_pt_set_vertex_motion): in force while temporal and deformSet are too (vertexMotionActive); everything below exists only then
+  // vertex motion (mi_pt_set_vertex_motion): in force while temporal and deformSet (or vuSet) are too (vertexMotionActive); everything below exists only then
   bool                    vertexMotion = false;  // as requested
   bool                    haveFirstHitTri = false;  // a first-frame batch wrote firstHitTri
   bool                    vmPoseDirty = false;   // mi_pt_update_deformation ran since the last snapshot of the positions
@@ -329,7 +342,7 @@ namespace {
 
 size_t align16(size_t v) { return (v + 15u) & ~size_t(15); }
 
-bool vertexMotionActive(const MiPt* pt) { return pt->vertexMotion && pt->temporal && pt->deformSet; }
+bool vertexMotionActive(const MiPt* pt) { return pt->vertexMotion && pt->temporal && (pt->deformSet || pt->vuSet); }
 
 // The first-hit triangle records of vertex motion, at the current number of pixel slots; none while the feature is not in force.
 int allocFirstHitTri(MiPt* pt)
@@ -364,7 +377,9 @@ int allocVertexMotion(MiPt* pt)
   pt->vmPrevOffset.assign(numPrims, SIZE_MAX);
   size_t                bytes = 0;
   std::vector<uint32_t> ids;
-  for(int id : pt->deformPrimIDs)
+  std::vector<int> moving = pt->deformPrimIDs;  // (the two lists are disjoint: each call refuses a primitive of the other)
+  moving.insert(moving.end(), pt->vuPrimIDs.begin(), pt->vuPrimIDs.end());
+  for(int id : moving)
   {
     pt->vmPrevOffset[size_t(id)] = bytes;
     bytes += align16(size_t(pt->primVertices[size_t(id)]) * 12);
@@ -1676,6 +1691,8 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " out of range");
     if(seen[size_t(d.renderPrimID)]++)
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " listed twice");
+    if(pt->vuSet && pt->vuDeclared[size_t(d.renderPrimID)])
+      return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " is driven by the caller (mi_pt_set_vertex_updates)");
     const pt::DevPrim& rp = pt->hostPrims[size_t(d.renderPrimID)];
     if(d.vertexCount != pt->primVertices[size_t(d.renderPrimID)])
       return fail(MI_PT_ERR_ARGUMENT, who + "vertexCount differs from the resident primitive's");
@@ -1836,6 +1853,273 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
   if(flags & MI_PT_DEFORM_DEFER_BUILD)
     return MI_PT_OK;
   return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
+}
+
+static void releaseVertexUpdates(MiPt* pt)
+{
+  pt->vuTable.release();
+  pt->vuTasks.release();
+  pt->vuNormalTasks.release();
+  pt->vuBlockTask.release();
+  pt->vuBlockCap = 0;
+  pt->vuSet      = false;
+  pt->vuPrimIDs.clear();
+  pt->vuDeclared.clear();
+  pt->vuCornerEnd.clear();
+  pt->vuCorners.clear();
+}
+
+int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, int flags)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_vertex_updates: null instance");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if(count < 0 || (flags & ~MI_PT_VERTICES_RECOMPUTE_NORMALS))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_vertex_updates: negative count or unknown flag bits");
+  if(count == 0 || !renderPrimIDs)
+  {
+    releaseVertexUpdates(pt);
+    return allocVertexMotion(pt);
+  }
+  // ---- validation: the kernels index everything below without further checks
+  const int            numPrims = int(pt->primVertices.size());
+  std::vector<uint8_t> declared(size_t(numPrims), 0);
+  uint64_t             blocks = 0, tableWords = 0;
+  for(int k = 0; k < count; ++k)
+  {
+    const int         id  = renderPrimIDs[k];
+    const std::string who = "mi_pt_set_vertex_updates: render primitive " + std::to_string(id);
+    if(id < 0 || id >= numPrims)
+      return fail(MI_PT_ERR_ARGUMENT, who + " out of range");
+    if(declared[size_t(id)]++)
+      return fail(MI_PT_ERR_ARGUMENT, who + " listed twice");
+    if(std::find(pt->deformPrimIDs.begin(), pt->deformPrimIDs.end(), id) != pt->deformPrimIDs.end())
+      return fail(MI_PT_ERR_ARGUMENT, who + " is deformed by the deformation tables (mi_pt_set_deformation)");
+    const pt::DevPrim& rp = pt->hostPrims[size_t(id)];
+    if(!rp.positions || pt->primVertices[size_t(id)] == 0)
+      return fail(MI_PT_ERR_ARGUMENT, who + " has no positions");
+    blocks += (uint64_t(pt->primVertices[size_t(id)]) + pt::VERTEX_UPDATE_BLOCK - 1) / pt::VERTEX_UPDATE_BLOCK;
+    if((flags & MI_PT_VERTICES_RECOMPUTE_NORMALS) && rp.normals && rp.indices && pt->primTriangles[size_t(id)] > 0)
+      tableWords += uint64_t(pt->primVertices[size_t(id)]) + uint64_t(pt->primTriangles[size_t(id)]) * 3;
+  }
+  if(blocks > 0x3fffffffull || tableWords > 0xffffffffull)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_vertex_updates: too many vertices or corners");
+  // ---- the incident-corner tables (CSR, triangles in ascending order), from the resident index buffers
+  std::vector<uint32_t> table;
+  table.reserve(size_t(tableWords));
+  std::vector<size_t> cornerEnd(size_t(numPrims), SIZE_MAX), corners(size_t(numPrims), SIZE_MAX);
+  for(int k = 0; k < count && tableWords; ++k)
+  {
+    const size_t       id = size_t(renderPrimIDs[k]);
+    const pt::DevPrim& rp = pt->hostPrims[id];
+    const size_t       nv = pt->primVertices[id], nc = size_t(pt->primTriangles[id]) * 3;
+    if(!rp.normals || !rp.indices || nc == 0)
+      continue;
+    std::vector<uint32_t> idx(nc);
+    HIP_TRY(hipMemcpy(idx.data(), rp.indices, nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    cornerEnd[id] = table.size();
+    corners[id]   = table.size() + nv;
+    table.resize(table.size() + nv + nc, 0u);
+    uint32_t* end = table.data() + cornerEnd[id];
+    uint32_t* out = table.data() + corners[id];
+    for(size_t c = 0; c < nc; ++c)  // (mi_pt_create checked every index against vertexCount)
+      ++end[idx[c]];
+    for(size_t v = 1; v < nv; ++v)
+      end[v] += end[v - 1];
+    std::vector<uint32_t> cursor(nv);
+    for(size_t v = 0; v < nv; ++v)
+      cursor[v] = v ? end[v - 1] : 0u;
+    for(size_t c = 0; c < nc; ++c)
+      out[cursor[idx[c]]++] = uint32_t(c);
+  }
+  // ---- commit
+  DevBuf<uint32_t>              newTable, newBlockTask;
+  DevBuf<pt::VertexUpdateTask>  newTasks;
+  DevBuf<pt::NormalRebuildTask> newNormalTasks;
+  HIP_TRY(newTable.upload(table.data(), table.size()));
+  HIP_TRY(newTasks.alloc(size_t(count)));
+  HIP_TRY(newNormalTasks.alloc(size_t(count)));
+  HIP_TRY(newBlockTask.alloc(size_t(blocks) * 2 + 1));
+  releaseVertexUpdates(pt);
+  pt->vuTable       = std::move(newTable);
+  pt->vuTasks       = std::move(newTasks);
+  pt->vuNormalTasks = std::move(newNormalTasks);
+  pt->vuBlockTask   = std::move(newBlockTask);
+  pt->vuBlockCap    = size_t(blocks);
+  pt->vuSet         = true;
+  pt->vuPrimIDs.assign(renderPrimIDs, renderPrimIDs + count);
+  pt->vuDeclared  = std::move(declared);
+  pt->vuCornerEnd = std::move(cornerEnd);
+  pt->vuCorners   = std::move(corners);
+  return allocVertexMotion(pt);  // (the declared primitives' previous-pose positions start from the resident ones)
+}
+
+// Both forms of an update call.  `device`: the stream pointers are device memory, read by the kernel where they lie.
+static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpdates, int flags, bool device, const char* name)
+{
+  const std::string fn = name;
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": null instance");
+  if(!pt->vuSet)
+    return fail(MI_PT_ERR_STATE, fn + ": no primitives declared (mi_pt_set_vertex_updates)");
+  if(numUpdates < 0 || (numUpdates > 0 && !updates) || (flags & ~MI_PT_DEFORM_DEFER_BUILD))
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": negative count, null table or unknown flag bits");
+  // ---- validation: nothing changes when any primitive of the call is refused
+  std::vector<uint8_t> seen(pt->vuDeclared.size(), 0);
+  size_t               stagingBytes = 0;
+  for(int k = 0; k < numUpdates; ++k)
+  {
+    const MiPtVertexUpdate& u   = updates[k];
+    const std::string       who = fn + ": update " + std::to_string(k) + ": ";
+    if(u.renderPrimID < 0 || size_t(u.renderPrimID) >= pt->vuDeclared.size() || !pt->vuDeclared[size_t(u.renderPrimID)])
+      return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(u.renderPrimID) + " is not declared");
+    if(seen[size_t(u.renderPrimID)]++)
+      return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(u.renderPrimID) + " listed twice");
+    const pt::DevPrim& rp = pt->hostPrims[size_t(u.renderPrimID)];
+    if(u.vertexCount != pt->primVertices[size_t(u.renderPrimID)])
+      return fail(MI_PT_ERR_ARGUMENT, who + "vertexCount differs from the resident primitive's");
+    if(!u.positions)
+      return fail(MI_PT_ERR_ARGUMENT, who + "no positions");
+    if((u.normals && !rp.normals) || (u.tangents && !rp.tangents))
+      return fail(MI_PT_ERR_ARGUMENT, who + "a stream the resident primitive does not have");
+    if(u.reserved[0] || u.reserved[1])
+      return fail(MI_PT_ERR_ARGUMENT, who + "reserved words must be 0");
+    const size_t nv = u.vertexCount;
+    if(device)
+    {
+      if((reinterpret_cast<uintptr_t>(u.positions) | reinterpret_cast<uintptr_t>(u.normals) | reinterpret_cast<uintptr_t>(u.tangents)) & 3u)
+        return fail(MI_PT_ERR_ARGUMENT, who + "a device pointer that is not 4-byte aligned");
+      continue;
+    }
+    auto finite = [](const float* a, size_t n) {
+      for(size_t i = 0; i < n; ++i)
+        if(!std::isfinite(a[i]))
+          return false;
+      return true;
+    };
+    if(!finite(u.positions, nv * 3) || (u.normals && !finite(u.normals, nv * 3)) || (u.tangents && !finite(u.tangents, nv * 4)))
+      return fail(MI_PT_ERR_ARGUMENT, who + "a non-finite component");
+    stagingBytes += align16(nv * 12) + (u.normals ? align16(nv * 12) : 0) + (u.tangents ? align16(nv * 16) : 0);
+  }
+  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old vertices; the caller's streams have produced the device arrays
+  const auto t0 = std::chrono::steady_clock::now();
+  if(stagingBytes > pt->vuStaging.count)
+    HIP_TRY(pt->vuStaging.alloc(stagingBytes));
+  // ---- task tables: every primitive's vertex range padded to whole blocks, one launch (and one for the normals that are rebuilt)
+  std::vector<uint8_t>               staging(stagingBytes);
+  std::vector<pt::VertexUpdateTask>  tasks;
+  std::vector<pt::NormalRebuildTask> normalTasks;
+  std::vector<uint32_t>              blockTask, normalBlockTask;
+  size_t                             off = 0;
+  uint64_t                           vertices = 0;
+  auto                               stage = [&](const float* src, size_t bytes) -> const float* {
+    if(!src)
+      return nullptr;
+    if(device)
+      return src;
+    memcpy(staging.data() + off, src, bytes);
+    const uint8_t* d = pt->vuStaging.ptr + off;
+    off += align16(bytes);
+    return reinterpret_cast<const float*>(d);
+  };
+  for(int k = 0; k < numUpdates; ++k)
+  {
+    const MiPtVertexUpdate& u  = updates[k];
+    const size_t            id = size_t(u.renderPrimID);
+    const pt::DevPrim&      rp = pt->hostPrims[id];
+    const size_t            nv = u.vertexCount;
+    const size_t            nb = (nv + pt::VERTEX_UPDATE_BLOCK - 1) / pt::VERTEX_UPDATE_BLOCK;
+    pt::VertexUpdateTask    t{};
+    t.positions    = stage(u.positions, nv * 12);
+    t.normals      = stage(u.normals, nv * 12);
+    t.tangents     = stage(u.tangents, nv * 16);
+    t.outPositions = const_cast<float*>(rp.positions);
+    t.outNormals   = const_cast<float*>(rp.normals);
+    t.outTangents  = const_cast<float*>(rp.tangents);
+    t.outVerts     = const_cast<float4*>(rp.verts);
+    t.vertexCount  = uint32_t(nv);
+    t.firstBlock   = uint32_t(blockTask.size());
+    t.flags        = (u.normals ? pt::VU_NORMALS : 0u) | (u.tangents ? pt::VU_TANGENTS : 0u);
+    blockTask.insert(blockTask.end(), nb, uint32_t(tasks.size()));
+    tasks.push_back(t);
+    vertices += nv;
+    if(!u.normals && pt->vuCornerEnd[id] != SIZE_MAX)
+    {
+      pt::NormalRebuildTask n{};
+      n.positions   = rp.positions;
+      n.indices     = rp.indices;
+      n.cornerEnd   = pt->vuTable.ptr + pt->vuCornerEnd[id];
+      n.corners     = pt->vuTable.ptr + pt->vuCorners[id];
+      n.outNormals  = const_cast<float*>(rp.normals);
+      n.outVerts    = const_cast<float4*>(rp.verts);
+      n.vertexCount = uint32_t(nv);
+      n.firstBlock  = uint32_t(normalBlockTask.size());
+      normalBlockTask.insert(normalBlockTask.end(), nb, uint32_t(normalTasks.size()));
+      normalTasks.push_back(n);
+    }
+  }
+  uint32_t* rejectedDev = pt->vuBlockTask.ptr + 2 * pt->vuBlockCap;
+  uint32_t  rejected    = 0;
+  if(!tasks.empty())
+  {
+    if(stagingBytes)
+      HIP_TRY(hipMemcpy(pt->vuStaging.ptr, staging.data(), stagingBytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->vuTasks.ptr, tasks.data(), tasks.size() * sizeof(pt::VertexUpdateTask), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->vuBlockTask.ptr, blockTask.data(), blockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(rejectedDev, 0, sizeof(uint32_t)));
+    pt::launchVertexIngest(pt->vuTasks.ptr, pt->vuBlockTask.ptr, uint32_t(blockTask.size()), rejectedDev, nullptr);
+    HIP_TRY(hipGetLastError());
+    if(!normalTasks.empty())  // (after the ingest, on the same stream: it reads resident positions, which are always finite)
+    {
+      HIP_TRY(hipMemcpy(pt->vuNormalTasks.ptr, normalTasks.data(), normalTasks.size() * sizeof(pt::NormalRebuildTask), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(pt->vuBlockTask.ptr + pt->vuBlockCap, normalBlockTask.data(), normalBlockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      pt::launchNormalRebuild(pt->vuNormalTasks.ptr, pt->vuBlockTask.ptr + pt->vuBlockCap, uint32_t(normalBlockTask.size()), nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&rejected, rejectedDev, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if(buildTiming)
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "vertex update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  ++pt->vuCalls;
+  pt->vuWritten += vertices - rejected;
+  pt->vuRejected = rejected;
+  if(tasks.empty())
+    return MI_PT_OK;
+  pt->vmPoseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
+  for(int k = 0; k < numUpdates; ++k)  // (what the next acceleration update refits; sized by a build that kept refit data)
+    if(size_t(updates[k].renderPrimID) < pt->primDirty.size())
+      pt->primDirty[size_t(updates[k].renderPrimID)] = pt->primDeformed[size_t(updates[k].renderPrimID)] = 1;
+  if(flags & MI_PT_DEFORM_DEFER_BUILD)
+    return MI_PT_OK;
+  return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
+}
+
+int mi_pt_update_vertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpdates, int flags)
+{
+  FLUSH_PENDING(pt);
+  return updateVertices(pt, updates, numUpdates, flags, false, "mi_pt_update_vertices");
+}
+
+int mi_pt_update_vertices_device(MiPt* pt, const MiPtVertexUpdate* updates, int numUpdates, int flags)
+{
+  FLUSH_PENDING(pt);
+  return updateVertices(pt, updates, numUpdates, flags, true, "mi_pt_update_vertices_device");
+}
+
+int mi_pt_get_vertex_update_info(MiPt* pt, MiPtVertexUpdateInfo* out)
+{
+  if(!pt || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_vertex_update_info: null argument");
+  out->calls            = pt->vuCalls;
+  out->verticesWritten  = pt->vuWritten;
+  out->verticesRejected = pt->vuRejected;
+  out->tableBytes       = pt->vuTable.bytes();
+  return MI_PT_OK;
 }
 
 int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
@@ -2896,9 +3180,9 @@ int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions)
   if(!pt || !positions)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: bad arguments");
   if(!vertexMotionActive(pt))
-    return fail(MI_PT_ERR_STATE, "mi_pt_read_previous_positions: vertex motion is not in force (mi_pt_set_vertex_motion, mi_pt_set_temporal, mi_pt_set_deformation)");
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_previous_positions: vertex motion is not in force (mi_pt_set_vertex_motion, mi_pt_set_temporal, mi_pt_set_deformation or mi_pt_set_vertex_updates)");
   if(renderPrimID < 0 || size_t(renderPrimID) >= pt->vmPrevOffset.size() || pt->vmPrevOffset[size_t(renderPrimID)] == SIZE_MAX)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: render primitive " + std::to_string(renderPrimID) + " does not deform");
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: render primitive " + std::to_string(renderPrimID) + " neither deforms nor is driven by the caller");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t nv = pt->primVertices[size_t(renderPrimID)];
@@ -2976,12 +3260,12 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                          + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->alphaTris.bytes()
                          + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deformPool.bytes() + pt->deformTasks.bytes()
                          + pt->deformBlockTask.bytes() + pt->deformJoints.bytes() + pt->deformWeights.bytes() + refitBytes(pt) + pt->vmPrevPositions.bytes() + pt->vmPrims.bytes()
-                         + pt->vmDeformIDs.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
+                         + pt->vmDeformIDs.bytes() + pt->vuTable.bytes() + pt->vuTasks.bytes() + pt->vuNormalTasks.bytes() + pt->vuBlockTask.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
   const uint64_t pathState = pt->pathArrays.bytes() + pt->optThroughput.bytes() + pt->optMisc.bytes() + pt->optMedium.bytes() + pt->optPixelSum.bytes() + pt->optGuides.bytes()
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
                             + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));

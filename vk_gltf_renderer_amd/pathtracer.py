@@ -250,6 +250,60 @@ class PathTracer:
         jm, mw = keep(joint_matrices), keep(morph_weights)
         _check_pt(self._l.mi_pt_update_deformation(self._p, ptr(jm), ptr(mw), capi.MI_PT_DEFORM_DEFER_BUILD if defer_build else 0))
 
+    def set_vertex_updates(self, prims, recompute_normals=False):
+        """Declares the render primitives whose vertices the caller drives (mi_pt_set_vertex_updates); None or an empty list releases the
+        declaration.  recompute_normals: an update that brings no normals for a primitive with a normal stream rebuilds them on the device
+        (area-weighted face normals; tangents are never rebuilt -- supply them where a normal map needs them)."""
+        ids = [int(p) for p in (prims if prims is not None else [])]
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        _check_pt(self._l.mi_pt_set_vertex_updates(self._p, arr, len(ids), capi.MI_PT_VERTICES_RECOMPUTE_NORMALS if recompute_normals else 0))
+
+    def update_vertices(self, updates, defer_build=False):
+        """New vertices for declared primitives (mi_pt_update_vertices / mi_pt_update_vertices_device): {prim: positions} or
+        {prim: (positions, normals, tangents)} with None for a stream that keeps its values.  Float32 numpy arrays (anything np.asarray takes)
+        go through the host form; contiguous float32 torch tensors on this instance's device through the device form, read where they lie.
+        Mixing the two in one call is an error.  The acceleration structure follows unless defer_build (update_render_nodes comes next)."""
+        def is_device(a):
+            return hasattr(a, "data_ptr") and hasattr(a, "is_contiguous")
+        table = (capi.MiPtVertexUpdate * max(len(updates), 1))()
+        keep, forms = [], set()
+        for k, (prim, streams) in enumerate(updates.items()):
+            streams = tuple(streams) if isinstance(streams, (tuple, list)) else (streams,)
+            if not 1 <= len(streams) <= 3 or streams[0] is None:
+                raise ValueError(f"update_vertices: primitive {prim}: positions, or (positions, normals, tangents)")
+            streams = streams + (None,) * (3 - len(streams))
+            u = table[k]
+            u.renderPrimID = int(prim)
+            for name, a, width in zip(("positions", "normals", "tangents"), streams, (3, 3, 4)):
+                if a is None:
+                    continue
+                forms.add(is_device(a))
+                if is_device(a):
+                    if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.device.type != "cuda":
+                        raise ValueError(f"update_vertices: primitive {prim}: {name} must be a contiguous float32 tensor on the device")
+                    count, ptr = a.numel(), a.data_ptr()
+                else:
+                    a = np.ascontiguousarray(a, dtype=np.float32)
+                    count, ptr = a.size, a.ctypes.data
+                keep.append(a)
+                if count % width:
+                    raise ValueError(f"update_vertices: primitive {prim}: {name} holds {count} floats, no multiple of {width}")
+                if name == "positions":
+                    u.vertexCount = count // width
+                elif count // width != u.vertexCount:
+                    raise ValueError(f"update_vertices: primitive {prim}: {name} has {count // width} vertices, positions {u.vertexCount}")
+                setattr(u, name, ptr)
+        if len(forms) > 1:
+            raise ValueError("update_vertices: numpy arrays and device tensors in one call")
+        fn = self._l.mi_pt_update_vertices_device if True in forms else self._l.mi_pt_update_vertices
+        _check_pt(fn(self._p, table, len(updates), capi.MI_PT_DEFORM_DEFER_BUILD if defer_build else 0))
+
+    def vertex_update_info(self):
+        """mi_pt_get_vertex_update_info as a dict: calls, verticesWritten (both in total), verticesRejected (last call), tableBytes."""
+        a = capi.MiPtVertexUpdateInfo()
+        _check_pt(self._l.mi_pt_get_vertex_update_info(self._p, C.byref(a)))
+        return {n: int(getattr(a, n)) for n, _ in a._fields_}
+
     ACCEL_MODES = {"rebuild": 0, "refit": 1, "auto": 2}
 
     def set_accel_update(self, mode, rebuild_cost_ratio=1.5):

@@ -1314,6 +1314,55 @@ def scene_skinned_large(path, seed=11):
     return scene_skinned(path, seed=seed, tess=240)
 
 
+def scene_dynamic(path, tess=12, seed=41, tex_size=32):
+    """A small stage for caller-driven vertices (mi_pt_set_vertex_updates / mi_pt_update_vertices), nothing in it is animated by glTF:
+      cloth     grid(20, 15): 336 vertices (one full 256-thread block and a partial one) with normals, uv0, tangents, a base-colour map and a
+                normal map, double sided;
+      ball      uv_sphere(2 tess, tess): 325 vertices at tess = 12, normals only, drawn by two nodes, one of them mirrored;
+      box       24 vertices, three instances through EXT_mesh_gpu_instancing;
+      triangle  a single one, 3 vertices;
+    over a static floor, with a camera and a directional light."""
+    rng = np.random.default_rng(seed)
+    b = GlbBuilder()
+    smp = b.sampler()
+    base = value_noise(rng, tex_size, 4, 3)
+    base = np.concatenate([0.25 + 0.7 * base, np.ones((tex_size, tex_size, 1))], -1)
+    h = value_noise(rng, tex_size, 5, 1)[..., 0]
+    gx, gy = np.roll(h, -1, 1) - np.roll(h, 1, 1), np.roll(h, -1, 0) - np.roll(h, 1, 0)
+    nm = np.stack([-gx * 6.0, -gy * 6.0, np.ones_like(gx)], -1)
+    nm = nm / np.linalg.norm(nm, axis=-1, keepdims=True) * 0.5 + 0.5
+    nm = np.concatenate([nm, np.ones((tex_size, tex_size, 1))], -1)
+    to8 = lambda img: (np.clip(img, 0, 1) * 255 + 0.5).astype(np.uint8)
+    fabric = b.material({"pbrMetallicRoughness": {"baseColorTexture": {"index": b.texture(b.image(to8(base)), smp)}, "metallicFactor": 0.0,
+                                                  "roughnessFactor": 0.7},
+                         "normalTexture": {"index": b.texture(b.image(to8(nm)), smp)}, "doubleSided": True})
+    red = b.material(lambert_material((0.8, 0.25, 0.2)))
+    blue = b.material({"pbrMetallicRoughness": {"baseColorFactor": [0.2, 0.3, 0.8, 1], "metallicFactor": 0.6, "roughnessFactor": 0.35}})
+    yellow = b.material(lambert_material((0.85, 0.75, 0.2), doubleSided=True))
+    grey = b.material(lambert_material((0.6, 0.6, 0.6)))
+
+    cp, cn, cuv, ci = grid(20, 15, (2.0, 1.5), axis="z")
+    ct = np.tile(np.array([[1.0, 0.0, 0.0, 1.0]], np.float32), (len(cp), 1))
+    b.node(mesh=b.mesh([b.primitive(cp, ci, normals=cn, uv0=cuv, tangents=ct, material=fabric)]), translation=[-0.2, 0.3, -0.4])
+    sp, sn, _, si = uv_sphere(2 * tess, tess, 0.4)
+    ball = b.mesh([b.primitive(sp, si, normals=sn, material=red)])
+    b.node(mesh=ball, translation=[1.3, -0.1, 0.5])
+    b.node(mesh=ball, translation=[-1.5, -0.2, 0.6], scale=[-0.8, 0.8, 0.8])  # mirrored: the winding flips in world space
+    bp, bn, _, bi = box((0.4, 0.3, 0.35))
+    inst_t = b.accessor(np.asarray([[0.0, -0.55, 1.2], [0.7, -0.55, 1.4], [-0.7, -0.5, 1.3]], np.float32))
+    inst_s = b.accessor(np.asarray([[1, 1, 1], [0.6, 0.6, 0.6], [0.8, 1.3, 0.8]], np.float32))
+    b.node(mesh=b.mesh([b.primitive(bp, bi, normals=bn, material=blue)]),
+           extensions={"EXT_mesh_gpu_instancing": {"attributes": {"TRANSLATION": inst_t, "SCALE": inst_s}}})
+    tp = np.array([[-0.3, 0.0, 0.0], [0.3, 0.0, 0.0], [0.0, 0.5, 0.0]], np.float32)
+    b.node(mesh=b.mesh([b.primitive(tp, np.array([[0, 1, 2]], np.uint32), material=yellow)]), translation=[0.2, -0.6, 2.0])
+    fp, fn, _, fi = grid(4, 4, (8, 8))
+    b.node(mesh=b.mesh([b.primitive(fp, fi, normals=fn, material=grey)]), translation=[0, -0.75, 0])
+    b.camera_node((0.2, 0.6, 4.6), (0.0, -0.05, 0.0), yfov=0.75)
+    b.light({"type": "directional", "intensity": 2.5})
+    b.node(rotation=_quat((1, 0.3, 0), -0.9), extensions={"KHR_lights_punctual": {"light": 0}})
+    return b.save(path)
+
+
 def scene_variants(path, seed=31, tess=12, tex_size=32):
     """A small stage for KHR_materials_variants: three spheres, a brick under EXT_mesh_gpu_instancing (three instances) and a floor nothing
     maps.  Variants "base" (0), "cutout" (1), "glass" (2):
