@@ -144,6 +144,22 @@ MI_PT_API void mi_default_params(MiPathtraceParams* params);
 MI_PT_API void mi_camera_frame_info(const MiCamera* camera, int width, int height, MiSceneFrameInfo* info, float* pixelAngle,
                                     float* focalDistance);
 
+/* Camera rays of a pose under a projection, for mi_pt_set_camera_rays: numSets x height x width MiPtRay records (image order, the sets outermost),
+ * tMin 0, tMax FLT_MAX, unit directions (bind with MI_PT_CAMERA_RAYS_UNIT or without).  Computed in double on the matrices of
+ * mi_camera_frame_info and rounded once to float.  The sample position of pixel (px, py) in set s is (x, y) = (px + jx, py + jy) with
+ * (jx, jy) = jitterXY[2 s], jitterXY[2 s + 1], or (0.5, 0.5) when jitterXY is NULL; row 0 is the top row, as for the built-in camera.  right / up /
+ * forward are columns 0, 1 and -2 of viewInv, the origin is its translation.
+ *  - MI_PROJECTION_PERSPECTIVE: the built-in camera's ray through (x, y) -- orthographic when the camera is -- with no lens.
+ *  - MI_PROJECTION_EQUIRECT: phi = (x / W - 1/2) 2 pi, theta = (1/2 - y / H) pi, d = cos theta sin phi right + sin theta up + cos theta cos phi forward.
+ *  - MI_PROJECTION_FISHEYE (equidistant): R = min(W, H) / 2, u = (x - W / 2) / R, v = (H / 2 - y) / R, r = |(u, v)|; r > 1 is a DEAD ray (zero
+ *    direction: the pixel stays black and transparent); alpha = r fov / 2, d = sin alpha (u right + v up) / r + cos alpha forward (forward at r = 0).
+ *    0 < fisheyeFovDegrees <= 360; ignored by the other projections.
+ * *pixelAngle (may be NULL): what belongs into MiPathtraceParams::pixelAngle -- mi_camera_frame_info's, pi / H, fov / min(W, H).
+ * MI_PT_ERR_ARGUMENT, with nothing written: a NULL camera or output, width / height / numSets < 1, an unknown projection, a fisheye fov out of range. */
+enum { MI_PROJECTION_PERSPECTIVE = 0, MI_PROJECTION_EQUIRECT = 1, MI_PROJECTION_FISHEYE = 2 };
+MI_PT_API int mi_camera_rays(const MiCamera* camera, int projection, float fisheyeFovDegrees, int width, int height, const float* jitterXY, int numSets,
+                             MiPtRay* hostRays, float* pixelAngle);
+
 MI_PT_API const char* mi_host_last_error(void);
 
 #ifdef __cplusplus

@@ -637,6 +637,51 @@ MI_PT_API int mi_pt_query_rays_ex(MiPt* pt, const MiPtRay* hostRays, int numRays
 MI_PT_API int mi_pt_query_rays_device_ex(MiPt* pt, const void* deviceRays, int numRays, const MiPtQueryOptions* options, void* deviceHits, void* hipStream);
 MI_PT_API int mi_pt_pick_ex(MiPt* pt, const float* pixelXY, int numPixels, const MiPtQueryOptions* options, MiPtRayHit* hostHits);
 
+/* ---- caller-supplied camera rays -----------------------------------------------------------------------------------------------------------
+ * Any camera model: the frames that follow a bind start their paths from rays the caller gives (a panorama, a fisheye, a light-field slab,
+ * probes, the output of a torch model) instead of the pinhole / orthographic camera of MiSceneFrameInfo.  Everything after the first ray is
+ * unchanged: shading, next-event estimation, volumes, accumulation, guides, denoise, tonemap, the tile partition, the debug views.
+ *  - Layout: numSets x height x width MiPtRay records in image order (row-major, row 0 the top row), the sets outermost.
+ *  - Which ray: the path of pixel (px, py) in the frame numbered F = params->frameCount + f (as mi_pt_render_frames numbers frames) takes ray
+ *    [(F % numSets) * width * height + py * width + px].  Every sample of a multi-sample frame takes the same ray: anti-aliasing and lens blur
+ *    are the caller's -- bind several jittered sets.
+ *  - Random stream: sample 0 starts from the built-in camera's seed xxhash32(px, py, F) and discards the draws that camera makes before its
+ *    first walk: four (two jitter, two lens) -- two when the current frame info has MI_SCENE_IS_ORTHOGRAPHIC, whose camera has no lens and draws
+ *    no lens sample; a later sample continues the stored seed and discards as many.  Together with MI_PT_CAMERA_RAYS_UNIT: binding what
+ *    mi_pt_make_camera_rays wrote reproduces the built-in camera's single-sample frames bit for bit -- accumulator, guides, depth, first hit --
+ *    on the route that starts frames the same way (the BVH2, or MI_PT_NO_PACKET=1).
+ *  - Direction: normalised once (IEEE division and square root); with MI_PT_CAMERA_RAYS_UNIT the bits are used as given.
+ *  - tMin / tMax are not read: camera paths are unbounded.  mi_pt_make_camera_rays writes 0 and FLT_MAX, so its output is a valid query input.
+ *  - Dead rays: a ray with a non-finite origin or direction component or a zero direction (the queries' invalid-ray rule without its tMin / tMax
+ *    part) starts no path -- usable as a mask, e.g. outside a fisheye circle.  Its pixel takes radiance 0 and alpha 0 for that frame, folded into
+ *    the running mean like any sample; on a first frame also first-hit id 0, selection 0, depth 1 and zero guides.
+ *  - Still MiSceneFrameInfo's: the depth image (first hit through viewProjMatrix), the environment rotation, the backplate, the infinite plane;
+ *    mi_pt_pick stays the built-in camera's pick; params->pixelAngle (ray-cone texture footprint) is the caller's, as always.
+ *  - Selection image of a first frame: from the set of frame params->frameCount, opaque and unculled on the queries' walk -- at every pixel
+ *    renderNode + 1 of mi_pt_query_rays(MI_PT_QUERY_CLOSEST) over the same rays (with tMin 0, tMax FLT_MAX).
+ *  - While bound, frames start with a generator kernel and the per-lane walk on both trees, never with the fused packet kernel
+ *    (MiPtFrameTiming::tracePrimaryLaunches stays 0); unbinding restores it.
+ * mi_pt_set_camera_rays copies the rays (counted in MiPtMemory::rendererBytes: numSets x width x height x 32, freed on unbind / destroy);
+ * mi_pt_set_camera_rays_device borrows them: device memory, 16-byte aligned, valid and unchanged while frames that use it are in flight; it
+ * allocates nothing.  rays == NULL with numSets == 0: back to the built-in camera.  Both flush the frame queue first.
+ * MI_PT_ERR_STATE: before mi_pt_resize; while mi_pt_set_temporal is on (and mi_pt_set_temporal(1) while rays are bound): the motion image
+ * assumes the projective camera.  After an mi_pt_resize that changed the size the render calls return MI_PT_ERR_STATE until the caller binds
+ * or unbinds again -- there is no silent fall back to the built-in camera.
+ * MI_PT_ERR_ARGUMENT, with the binding unchanged: numSets < 1 with a pointer, a pointer with numSets == 0 (or NULL with numSets != 0), unknown flag
+ * bits, a device pointer that is not 16-byte aligned. */
+enum { MI_PT_CAMERA_RAYS_UNIT = 1 }; /* directions are unit vectors already: used bit for bit, not normalised again */
+MI_PT_API int mi_pt_set_camera_rays(MiPt* pt, const MiPtRay* hostRays, int numSets, uint32_t flags);
+MI_PT_API int mi_pt_set_camera_rays_device(MiPt* pt, const void* deviceRays, int numSets, uint32_t flags);
+/* Writes the rays the built-in camera generates for sample 0 of frames params->frameCount + k, k = 0..numSets-1, for EVERY pixel of the image
+ * (whatever the tile partition), from the current frame info and size and params->aperture / focalDistance: origin and direction exactly as the
+ * frame's first walk receives them (after jitter, lens and the final normalise), tMin 0, tMax FLT_MAX.  numSets x height x width records.  The
+ * device form writes 16-byte aligned device memory on hipStream and allocates nothing.  Both run the frames' own generator kernel through the
+ * instance's path queues: order the device form like a render call (the same stream as the frames, or synchronised with them).
+ * MI_PT_ERR_STATE before mi_pt_resize / mi_pt_set_frame_info, and on an instance whose rank of the tile partition owns no tile;
+ * MI_PT_ERR_ARGUMENT: NULL params or output, numSets < 1, an unaligned device pointer. */
+MI_PT_API int mi_pt_make_camera_rays(MiPt* pt, const MiPathtraceParams* params, int numSets, MiPtRay* hostRays);
+MI_PT_API int mi_pt_make_camera_rays_device(MiPt* pt, const MiPathtraceParams* params, int numSets, void* deviceRays, void* hipStream);
+
 /* device address of the last denoise result (NULL before the first), valid until the next denoise / resize */
 MI_PT_API const void* mi_pt_denoised_device_ptr(MiPt* pt);
 
@@ -684,7 +729,8 @@ MI_PT_API const char* mi_pt_version(void);
  *    struct a caller allocates changed.  Still 9: MiPtRay / MiPtRayHit and mi_pt_query_rays, mi_pt_query_rays_device, mi_pt_pick -- new types and
  *    entry points, no struct a caller already allocates changed.  Still 9: MiPtQueryOptions and mi_pt_default_query_options, mi_pt_query_rays_ex,
  *    mi_pt_query_rays_device_ex, mi_pt_pick_ex -- again new types and entry points only.  Still 9: MiPtVertexUpdate / MiPtVertexUpdateInfo and
- *    mi_pt_set_vertex_updates, mi_pt_update_vertices, mi_pt_update_vertices_device, mi_pt_get_vertex_update_info -- new types and entry points only.) */
+ *    mi_pt_set_vertex_updates, mi_pt_update_vertices, mi_pt_update_vertices_device, mi_pt_get_vertex_update_info -- new types and entry points only.
+ *    Still 9: mi_pt_set_camera_rays, mi_pt_set_camera_rays_device, mi_pt_make_camera_rays, mi_pt_make_camera_rays_device -- new entry points only.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

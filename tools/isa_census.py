@@ -23,7 +23,7 @@ def census(flags=(), source="pt_kernels.hip"):
         asm = os.path.join(tmp, "out.s")
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + os.path.join(ROOT, "include"), "-I" + DEVICE,
                "-Wno-unused-function", "--cuda-device-only", "-S", "-o", asm, os.path.join(DEVICE, source), *flags]
-        if source == "pt_kernels.hip":
+        if source in ("pt_kernels.hip", "camera_rays.hip"):
             cmd += ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-freciprocal-math", "-fapprox-func"]  # (csrc/Makefile: PT_KERNELS_FP)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

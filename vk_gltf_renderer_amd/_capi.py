@@ -212,6 +212,8 @@ MI_PT_QUERY_CLOSEST, MI_PT_QUERY_ANY, MI_PT_QUERY_NEAREST_K = 0, 1, 2
 MI_PT_QUERY_ALPHA_OPAQUE, MI_PT_QUERY_ALPHA_CUTOFF, MI_PT_QUERY_ALPHA_STOCHASTIC = 0, 1, 2
 MI_PT_QUERY_CULL_NONE, MI_PT_QUERY_CULL_MATERIAL = 0, 1
 MI_PT_QUERY_MAX_HITS = 8
+MI_PT_CAMERA_RAYS_UNIT = 1
+MI_PROJECTION_PERSPECTIVE, MI_PROJECTION_EQUIRECT, MI_PROJECTION_FISHEYE = 0, 1, 2  # include/mi_host.h
 MI_PT_USE_DLSS, MI_PT_USE_OPTIX_DENOISER, MI_PT_FIRST_FRAME = 1, 2, 4
 MI_SCENE_IS_ORTHOGRAPHIC, MI_SCENE_USE_SOLID_BACKGROUND, MI_SCENE_USE_HDR_ENVIRONMENT = 1, 2, 4
 MI_SCENE_USE_INFINITE_PLANE, MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER = 8, 16
@@ -285,6 +287,7 @@ HOST_SYMBOLS = {
     "mi_default_sky": (None, [P(MiSkyPhysicalParameters)]),
     "mi_default_params": (None, [P(MiPathtraceParams)]),
     "mi_camera_frame_info": (None, [P(MiCamera), i32, i32, P(MiSceneFrameInfo), P(f32), P(f32)]),
+    "mi_camera_rays": (i32, [P(MiCamera), i32, f32, i32, i32, P(f32), i32, P(MiPtRay), P(f32)]),
     "mi_host_last_error": (C.c_char_p, []),
 }
 
@@ -352,6 +355,10 @@ PT_SYMBOLS = {
     "mi_pt_update_vertices": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
     "mi_pt_update_vertices_device": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
     "mi_pt_get_vertex_update_info": (i32, [VP, P(MiPtVertexUpdateInfo)]),
+    "mi_pt_set_camera_rays": (i32, [VP, P(MiPtRay), i32, u32]),
+    "mi_pt_set_camera_rays_device": (i32, [VP, VP, i32, u32]),
+    "mi_pt_make_camera_rays": (i32, [VP, P(MiPathtraceParams), i32, P(MiPtRay)]),
+    "mi_pt_make_camera_rays_device": (i32, [VP, P(MiPathtraceParams), i32, VP, VP]),
 }
 
 

@@ -127,6 +127,7 @@ int main(int argc, char** argv)
     return 1;
   if(!app.createHDR(hdrFile) && app.resources().settings.envSystem == EnvSystem::eHdr)
     return 1;
+  app.pathTracer().setProjectionSets(framesInFlight);  // (--projection: one jittered set of camera rays per frame in flight)
   // frame 0 on its own (the benchmark's warm-up frame, docs/benchmarking.md:40), the rest in batches
   for(int f = 0; f < frames;)
   {

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 PathTracer::PathTracer()
 {
@@ -58,6 +59,9 @@ void PathTracer::registerParameters(ParameterRegistry* r)
   r->add("vertexMotion", "Denoiser: motion vectors follow skinned / morphed vertices (with --temporal 1)", &m_vertexMotion);
   // (our own) resident mode: hidden render nodes stay in the tree, so that visibility and material variants need no build (mi_pt_set_accel_resident, right after --accelUpdate)
   r->add("accelResident", "Keep hidden render nodes in the tree: visibility and material changes refit / patch instead of rebuilding (with --accelUpdate 1 | 2)", &m_accelResident);
+  // (our own) camera models beyond the pinhole: the app makes the rays (mi_camera_rays) and binds them (mi_pt_set_camera_rays)
+  r->add("projection", "Camera model [perspective, equirect (360 degree panorama), fisheye (equidistant)]; not with --temporal 1", &m_projection);
+  r->add("fisheyeFov", "Field of view across the image circle of --projection fisheye, in degrees (0, 360]", &m_fisheyeFov);
   r->add("accelRebuildRatio", "auto: rebuild once the refitted tree's SAH cost exceeds this x the cost after the last build", &m_accelRebuildRatio);
 }
 
@@ -76,6 +80,19 @@ void PathTracer::onSceneInvalidated(Resources& res)
   }
   if(!res.scene)
     return;
+  m_projectionBound = false;
+  if(m_projection != "perspective" && m_projection != "equirect" && m_projection != "fisheye")
+  {
+    m_error = "--projection must be perspective, equirect or fisheye";
+    fprintf(stderr, "PathTracer: %s\n", m_error.c_str());
+    return;
+  }
+  if(m_projection != "perspective" && m_temporal)
+  {
+    m_error = "--projection " + m_projection + " cannot be combined with --temporal 1: the motion vectors assume the perspective camera";
+    fprintf(stderr, "PathTracer: %s\n", m_error.c_str());
+    return;
+  }
   MiPtCreateOptions opt{};
   opt.device = res.device;
   opt.collectCounters = m_collectCounters ? 1 : 0;
@@ -234,6 +251,52 @@ void PathTracer::updateDenoiser(Resources& res)
     m_lastAutoDenoiseFrame = frame;
 }
 
+void PathTracer::projectionJitter(int numSets, float* jitterXY)
+{
+  uint32_t state = 0x9E3779B9u;
+  auto     next  = [&state]() {
+    state               = state * 747796405u + 2891336453u;
+    const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
+    return float(((word >> 22u) ^ word) >> 8) * (1.0f / 16777216.0f);
+  };
+  for(int k = 0; k < numSets; ++k)
+  {
+    const float x = next(), y = next();  // (drawn for set 0 too: set k's jitter does not depend on which set is the centre)
+    jitterXY[2 * k]     = k == 0 ? 0.5f : x;
+    jitterXY[2 * k + 1] = k == 0 ? 0.5f : y;
+  }
+}
+
+// --projection equirect | fisheye: the rays of the current pose and size, bound once per pose (a camera move or a resize restarts the accumulation
+// and makes them again)
+bool PathTracer::bindProjection(Resources& res)
+{
+  const int w = int(res.renderSize.width), h = int(res.renderSize.height);
+  if(m_projectionBound && w == m_projectionSize[0] && h == m_projectionSize[1] && memcmp(&m_projectionCamera, &res.camera, sizeof(MiCamera)) == 0)
+    return true;
+  const int            proj = m_projection == "equirect" ? MI_PROJECTION_EQUIRECT : MI_PROJECTION_FISHEYE;
+  std::vector<float>   jitter(size_t(m_projectionSets) * 2);
+  std::vector<MiPtRay> rays(size_t(m_projectionSets) * size_t(w) * size_t(h));
+  projectionJitter(m_projectionSets, jitter.data());
+  if(mi_camera_rays(&res.camera, proj, m_fisheyeFov, w, h, jitter.data(), m_projectionSets, rays.data(), &m_projectionPixelAngle) != MI_PT_OK)
+  {
+    m_error = mi_host_last_error();
+    fprintf(stderr, "PathTracer: --projection: %s\n", m_error.c_str());
+    return false;
+  }
+  if(mi_pt_set_camera_rays(m_pt, rays.data(), m_projectionSets, MI_PT_CAMERA_RAYS_UNIT) != MI_PT_OK)
+  {
+    m_error = mi_pt_last_error();
+    fprintf(stderr, "PathTracer: --projection: %s\n", m_error.c_str());
+    return false;
+  }
+  m_projectionBound   = true;
+  m_projectionCamera  = res.camera;
+  m_projectionSize[0] = w;
+  m_projectionSize[1] = h;
+  return true;
+}
+
 void PathTracer::updateStatistics()
 {
   m_totalSamplesAccumulated += m_pushConst.numSamples * m_framesLastCall;
@@ -247,6 +310,12 @@ void PathTracer::onRender(StreamHandle cmd, Resources& res)
     denoiseOneShot();  // the pose that just ended: its one temporal pass, before this frame overwrites the images it reads
   updateAdaptiveSampling(res);  // reference order: src/renderer_pathtracer.cpp:552-553, before the push constants are set up
   setupPushConstant(res, res.renderSize);
+  if(m_projection != "perspective")
+  {
+    if(!bindProjection(res))
+      return;
+    m_pushConst.pixelAngle = m_projectionPixelAngle;
+  }
   mi_pt_set_frame_info(m_pt, &res.frameInfo);
   mi_pt_set_sky(m_pt, &res.skyParams);
   if(m_adaptiveSampling)

@@ -55,12 +55,19 @@ public:
   void setFramesThisCall(int n) { m_framesThisCall = n < 1 ? 1 : n; }
   int  framesLastCall() const { return m_framesLastCall; }
 
+  // --projection (our own): sets of caller-supplied camera rays the frames cycle through, one per frame in flight (main.cpp: --framesInFlight)
+  void setProjectionSets(int n) { m_projectionSets = n < 1 ? 1 : (n > 1024 ? 1024 : n); }
+  // jitter of set k of a non-default projection: set 0 is the pixel centre; the others are drawn from the PCG stream (state * 747796405 +
+  // 2891336453, the library's output permutation, top 24 bits / 2^24) that starts at state 0x9E3779B9, x then y, set after set
+  static void projectionJitter(int numSets, float* jitterXY);
+
   MiPathtraceParams m_pushConst{};  // read by benchmarkFrameInfo() in the reference (src/renderer.cpp:526)
 
 private:
   void setupPushConstant(Resources& resources, const Extent2D& renderingSize);  // reference: :1496-1574
   void updateStatistics();                                                      // reference: :1377-1402
   void updateAdaptiveSampling(Resources& resources);                            // reference: :1326-1374
+  bool bindProjection(Resources& resources);                                    // (our own) --projection: mi_camera_rays + mi_pt_set_camera_rays
   void updateDenoiser(Resources& resources);                                    // reference: src/optix_denoiser.cpp:751-805
   // reference: src/renderer_pathtracer.hpp:167-195 (Interactive 60 / Balanced 30 / Quality 15 / MaxQuality 10 frames per second)
   double targetFrameTimeMs() const
@@ -82,6 +89,14 @@ private:
   // pose -- when the next pose starts or the image is saved -- instead of on the auto-denoise cadence
   bool        m_temporal{false};
   bool        m_vertexMotion{false};       // --vertexMotion (our own): mi_pt_set_vertex_motion, effective only with --temporal
+  // --projection / --fisheyeFov (our own): a camera model the built-in camera does not have, through mi_camera_rays + mi_pt_set_camera_rays
+  std::string m_projection{"perspective"};  // perspective | equirect | fisheye
+  float       m_fisheyeFov{180.0f};
+  int         m_projectionSets{32};
+  float       m_projectionPixelAngle{0.0f};
+  bool        m_projectionBound{false};
+  MiCamera    m_projectionCamera{};         // the pose and size the bound rays were made for
+  int         m_projectionSize[2]{0, 0};
   bool        m_poseOpen{false};           // the current pose has frames the temporal pass has not seen
   bool        m_havePoseViewProj{false};
   float       m_poseViewProj[16]{};        // viewProjMatrix of the current pose: the next pose's prevMVP

@@ -303,6 +303,12 @@ struct MiPt
   // ray queries and picking (mi_pt_query_rays, mi_pt_pick): staging of the host forms, allocated by the first such call and grown, never before
   DevBuf<MiPtRay>         queryRays;  // (mi_pt_pick stages its pixel positions here: 8 of the 32 bytes per ray)
   DevBuf<MiPtRayHit>      queryHits;
+  // caller-supplied camera rays (mi_pt_set_camera_rays, mi_pt_set_camera_rays_device): `cameraRays` non-NULL = bound
+  DevBuf<MiPtRay>         cameraRaysOwn;      // the host form's copy; empty under the device form
+  const MiPtRay*          cameraRays = nullptr;
+  int                     cameraRaySets = 0, cameraRaysWidth = 0, cameraRaysHeight = 0;  // the size they were bound at
+  uint32_t                cameraRayFlags = 0;
+  DevBuf<uint32_t>        allTiles;           // every tile of the image, for mi_pt_make_camera_rays under a tile partition (else ownedTiles is that)
   DevBuf<pt::StatCounters> stats;
   bool                    collectCounters = false;
   bool                    timingEnabled   = false;
@@ -562,6 +568,14 @@ int allocFrameResources(MiPt* pt)
   pt->numSlots = int(owned.size()) * T * T;
   HIP_TRY(pt->ownedTiles.upload(owned.data(), owned.size()));
   pt->ownedTilesHost = owned;
+  pt->allTiles.release();
+  if(pt->tileWorld > 1)  // (mi_pt_make_camera_rays writes every pixel whatever the partition, and its device form may not allocate)
+  {
+    std::vector<uint32_t> all;
+    for(int t = 0; t < pt->tilesX * pt->tilesY; ++t)
+      all.push_back(uint32_t((t % pt->tilesX) * T) | (uint32_t((t / pt->tilesX) * T) << 16));
+    HIP_TRY(pt->allTiles.upload(all.data(), all.size()));
+  }
   if(int rc = allocPathResources(pt, pt->framesCap))
     return rc;
   const size_t px = size_t(W) * size_t(H);
@@ -1254,6 +1268,9 @@ const char* mi_pt_last_error(void)
 }
 // Issues the frames mi_pt_render_frame has been holding back (mi_pt_set_frame_queue) as ONE mi_pt_render_frames batch.  Every entry point that
 // reads or changes what those frames depend on calls this first, so a caller never observes the deferral except through time.
+// rays bound at another image size: the render calls refuse until the caller binds or unbinds again
+static bool cameraRaysStale(const MiPt* pt) { return pt->cameraRays && (pt->cameraRaysWidth != pt->width || pt->cameraRaysHeight != pt->height); }
+static const char* const CAMERA_RAYS_STALE = "mi_pt_render_frame: the bound camera rays were bound at another image size -- bind or unbind them again";
 static int flushPending(MiPt* pt)
 {
   if(!pt || pt->pendingFrames == 0)
@@ -2373,6 +2390,8 @@ int mi_pt_render_frame(MiPt* pt, const MiPathtraceParams* params, void* hipStrea
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: numSamples >= 1 and 1 <= maxDepth <= 255 required");
     if(pt->width <= 0 || !pt->haveFrameInfo)
       return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: call mi_pt_resize and mi_pt_set_frame_info first");
+    if(cameraRaysStale(pt))
+      return fail(MI_PT_ERR_STATE, CAMERA_RAYS_STALE);
     pt->pendingFirst  = *params;
     pt->pendingStream = hipStream;
     pt->pendingFrames = 1;
@@ -2397,6 +2416,8 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: numSamples >= 1 and 1 <= maxDepth <= 255 required");
   if((pt->frameInfo.flags & MI_SCENE_USE_HDR_ENVIRONMENT) && !pt->scene.envPixels)
     return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: HDR environment requested but none was set");
+  if(cameraRaysStale(pt))
+    return fail(MI_PT_ERR_STATE, CAMERA_RAYS_STALE);
   HIP_TRY(hipSetDevice(pt->device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hipStream);
   pt->lastStream     = stream;
@@ -2574,13 +2595,17 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     pt::launchResetCounters(c.queues, stream);
     // 8-wide BVH: ONE kernel generates the camera rays, walks them as packets, finishes the paths that leave the scene and queues
     // the hits (k_trace_primary); BVH2 / MI_PT_NO_PACKET: k_generate writes the rays and the per-lane kernel walks them
-    const bool fusedPrimary = c.wide && usePacket && !debugSpans;
+    // bound camera rays: k_generate_rays takes the paths' rays from memory, then the per-lane walk, on both trees
+    const bool boundRays    = pt->cameraRays != nullptr;
+    const bool fusedPrimary = c.wide && usePacket && !debugSpans && !boundRays;
     if(fusedPrimary)
     {
       timed(TK_PRIMARY, [&] { pt::launchTracePrimary(c, s); });
       if(pt->timingEnabled)
         ++pt->accTiming.tracePrimaryLaunches;
     }
+    else if(boundRays)
+      timed(TK_GENERATE, [&] { pt::launchGenerateRays(c, pt->cameraRays, uint32_t(pt->cameraRaySets), (pt->cameraRayFlags & MI_PT_CAMERA_RAYS_UNIT) != 0, s); });
     else
       timed(TK_GENERATE, [&] { pt::launchGenerate(c, s); });
     int cur = 0;
@@ -2678,7 +2703,10 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   }
   if(params->flags & MI_PT_FIRST_FRAME)
   {
-    pt::launchSelection(c, pt->selection.ptr);
+    if(pt->cameraRays)  // (the set of the batch's first frame)
+      pt::launchSelectionRays(c, pt->cameraRays, uint32_t(params->frameCount) % uint32_t(pt->cameraRaySets), pt->selection.ptr);
+    else
+      pt::launchSelection(c, pt->selection.ptr);
     pt->haveFirstHit = true;
     if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
     {
@@ -2942,6 +2970,121 @@ int mi_pt_pick_ex(MiPt* pt, const float* pixelXY, int numPixels, const MiPtQuery
 {
   return queryPixels(pt, queryCallOf("mi_pt_pick_ex", options), pixelXY, numPixels, hostHits);
 }
+// ---- caller-supplied camera rays (camera_rays.hip) -----------------------------------------------------------------------------------------------
+namespace {
+int bindCameraRays(MiPt* pt, const char* who, const void* rays, int numSets, uint32_t flags, bool device)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, std::string(who) + ": null instance");
+  if((rays && numSets < 1) || (!rays && numSets != 0) || (flags & ~uint32_t(MI_PT_CAMERA_RAYS_UNIT)) != 0u)
+    return fail(MI_PT_ERR_ARGUMENT, std::string(who) + ": need numSets >= 1 with rays (NULL and 0 to unbind) and no unknown flag bits");
+  if(rays && device && (reinterpret_cast<uintptr_t>(rays) & 15u))
+    return fail(MI_PT_ERR_ARGUMENT, std::string(who) + ": rays must be 16-byte aligned");
+  if(pt->width <= 0)
+    return fail(MI_PT_ERR_STATE, std::string(who) + ": call mi_pt_resize first");
+  if(rays && pt->temporal)
+    return fail(MI_PT_ERR_STATE, std::string(who) + ": mi_pt_set_temporal is on -- the motion image assumes the projective camera");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight may still read the rays bound before
+  if(rays && !device)
+  {
+    const size_t    n = size_t(numSets) * size_t(pt->width) * size_t(pt->height);
+    DevBuf<MiPtRay> copy;  // (taken over only once it holds the rays: a failed allocation leaves the binding unchanged)
+    HIP_TRY(copy.upload(static_cast<const MiPtRay*>(rays), n));
+    pt->cameraRaysOwn = std::move(copy);
+    pt->cameraRays    = pt->cameraRaysOwn.ptr;
+  }
+  else
+  {
+    pt->cameraRaysOwn.release();
+    pt->cameraRays = static_cast<const MiPtRay*>(rays);
+  }
+  pt->cameraRaySets    = rays ? numSets : 0;
+  pt->cameraRayFlags   = rays ? flags : 0u;
+  pt->cameraRaysWidth  = rays ? pt->width : 0;
+  pt->cameraRaysHeight = rays ? pt->height : 0;
+  return MI_PT_OK;
+}
+// sets [0, numSets) of `out` (device memory) on `stream`.  The rays are the ones k_generate writes (launchExportCameraRays), so the export goes
+// through the instance's own queue 0 in pieces that fit it: some tiles of the image x at most 64 frames per piece.
+int exportCameraRays(MiPt* pt, const char* who, const MiPathtraceParams* params, int numSets, MiPtRay* out, hipStream_t stream)
+{
+  const uint32_t* tiles     = pt->tileWorld > 1 ? pt->allTiles.ptr : pt->ownedTiles.ptr;
+  const size_t    numTiles  = size_t(pt->tilesX) * size_t(pt->tilesY), tileSlots = size_t(pt->tileSize) * size_t(pt->tileSize);
+  if(tileSlots > pt->queueCap)  // (only an instance whose rank owns no tile at all)
+    return fail(MI_PT_ERR_STATE, std::string(who) + ": this rank of the tile partition owns no pixels -- its path queues hold no tile");
+  pt::LaunchCtx c{};
+  c.scene = pt->scene;
+  memset(&c.fc, 0, sizeof(c.fc));
+  c.fc.frameInfo = pt->frameInfo;
+  c.fc.pc        = *params;
+  c.fc.width     = pt->width;
+  c.fc.height    = pt->height;
+  c.fc.tileSize  = pt->tileSize;
+  while((1 << c.fc.tileShift) < pt->tileSize)
+    ++c.fc.tileShift;
+  c.queues = pt->queues;
+  c.stream = stream;
+  for(int done = 0; done < numSets;)
+  {
+    const int frames = int(std::min<size_t>(std::min<size_t>(size_t(numSets - done), 64), pt->queueCap / tileSlots));
+    c.fc.numFrames   = frames;
+    pt::divideMagic(uint32_t(std::max(frames, 2)), c.fc.framesMagic, c.fc.framesShift);
+    c.fc.slotLayout    = frames % 64 == 0 ? 1 : 0;
+    c.fc.pc.frameCount = params->frameCount + done;
+    const size_t perPiece = pt->queueCap / (tileSlots * size_t(frames));
+    for(size_t t = 0; t < numTiles; t += perPiece)
+    {
+      c.ownedTiles  = tiles + t;
+      c.fc.numSlots = int(std::min(perPiece, numTiles - t) * tileSlots);
+      pt::launchExportCameraRays(c, out, uint32_t(done));
+    }
+    done += frames;
+  }
+  HIP_TRY(hipGetLastError());
+  return MI_PT_OK;
+}
+int makeCameraRays(MiPt* pt, const char* who, const MiPathtraceParams* params, int numSets, void* out, bool device, void* hipStream)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !params || !out || numSets < 1)
+    return fail(MI_PT_ERR_ARGUMENT, std::string(who) + ": need params, an output and numSets >= 1");
+  if(device && (reinterpret_cast<uintptr_t>(out) & 15u))
+    return fail(MI_PT_ERR_ARGUMENT, std::string(who) + ": rays must be 16-byte aligned");
+  if(pt->width <= 0 || !pt->haveFrameInfo)
+    return fail(MI_PT_ERR_STATE, std::string(who) + ": call mi_pt_resize and mi_pt_set_frame_info first");
+  HIP_TRY(hipSetDevice(pt->device));
+  if(device)
+    return exportCameraRays(pt, who, params, numSets, static_cast<MiPtRay*>(out), reinterpret_cast<hipStream_t>(hipStream));
+  HIP_TRY(hipDeviceSynchronize());  // (the export goes through the path queues: frames in flight on other streams first)
+  const size_t    n = size_t(numSets) * size_t(pt->width) * size_t(pt->height);
+  DevBuf<MiPtRay> tmp;
+  HIP_TRY(tmp.alloc(n));
+  if(int rc = exportCameraRays(pt, who, params, numSets, tmp.ptr, nullptr))
+    return rc;
+  HIP_TRY(hipMemcpy(out, tmp.ptr, n * sizeof(MiPtRay), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+}  // namespace
+
+int mi_pt_set_camera_rays(MiPt* pt, const MiPtRay* hostRays, int numSets, uint32_t flags)
+{
+  return bindCameraRays(pt, "mi_pt_set_camera_rays", hostRays, numSets, flags, false);
+}
+int mi_pt_set_camera_rays_device(MiPt* pt, const void* deviceRays, int numSets, uint32_t flags)
+{
+  return bindCameraRays(pt, "mi_pt_set_camera_rays_device", deviceRays, numSets, flags, true);
+}
+int mi_pt_make_camera_rays(MiPt* pt, const MiPathtraceParams* params, int numSets, MiPtRay* hostRays)
+{
+  return makeCameraRays(pt, "mi_pt_make_camera_rays", params, numSets, hostRays, false, nullptr);
+}
+int mi_pt_make_camera_rays_device(MiPt* pt, const MiPathtraceParams* params, int numSets, void* deviceRays, void* hipStream)
+{
+  return makeCameraRays(pt, "mi_pt_make_camera_rays_device", params, numSets, deviceRays, true, hipStream);
+}
+
 int mi_pt_read_depth(MiPt* pt, float* host)
 {
   FLUSH_PENDING(pt);
@@ -3046,6 +3189,8 @@ int mi_pt_set_temporal(MiPt* pt, int enable)
   FLUSH_PENDING(pt);
   if(!pt)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_temporal: null instance");
+  if(enable && pt->cameraRays)
+    return fail(MI_PT_ERR_STATE, "mi_pt_set_temporal: camera rays are bound (mi_pt_set_camera_rays) -- the motion image assumes the projective camera");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
   pt->temporal = enable != 0;
@@ -3265,7 +3410,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
                             + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));

@@ -50,6 +50,15 @@ void launchTraceShadow(const LaunchCtx& c, int nxt);  // nxt: active queue the p
 void launchFlushSurvivors(const LaunchCtx& c, int cur);  // cur: the active queue the last shade launch appended to (paths alive when the bounce loop stopped)
 void launchFinishSample(const LaunchCtx& c, int sampleIndex, float4* accum, float* depth, float4* albedo, float4* normal);
 void launchSelection(const LaunchCtx& c, uint32_t* selection);
+// caller-supplied camera rays (camera_rays.hip, pt_camera_rays.h).  rays: numSets x height x width records in device memory, 16-byte aligned.
+// launchGenerateRays stands where launchGenerate does: queue 0 and its counters, ready for launchTraceClosest; unit: MI_PT_CAMERA_RAYS_UNIT.
+// launchSelectionRays: launchSelection over set `set` of the bound rays.  launchExportCameraRays: the built-in camera's sample-0 rays of the
+// c.fc.numFrames frames from c.fc.pc.frameCount on, for the pixels of c.ownedTiles (c.fc.numSlots pixel slots), into sets setBase.. of `out`.  It
+// runs launchGenerate(c, 0) into c.queues first (c.paths all NULL, c.fc.stateInQueue 0, c.collectCounters false: nothing but queue 0 and its
+// counters is written) and needs c.fc.numSlots x c.fc.numFrames <= NSUB x c.queues.subCap.
+void launchGenerateRays(const LaunchCtx& c, const MiPtRay* rays, uint32_t numSets, bool unit, int sampleIndex);
+void launchSelectionRays(const LaunchCtx& c, const MiPtRay* rays, uint32_t set, uint32_t* selection);
+void launchExportCameraRays(const LaunchCtx& c, MiPtRay* out, uint32_t setBase);
 // ray queries and picking (query.hip, pt_query.h): one ray per lane over the resident structure (`wide`: the 8-wide tree) under the rules of a
 // MiPtQueryOptions (pt_query.h: QueryRules -- face culling, alpha mode, q.maxHits records per ray: hits holds numRays x q.maxHits).  any:
 // MI_PT_QUERY_ANY, stop at the first accepted triangle (q.maxHits is 1 then).  The plain entry points are these under queryRulesPlain rules, which

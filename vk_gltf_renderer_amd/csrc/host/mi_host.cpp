@@ -369,4 +369,92 @@ void mi_camera_frame_info(const MiCamera* cam, int width, int height, MiSceneFra
   if(focalDistance)
     *focalDistance = mx::length(eye - center);
 }
+// Camera rays of a pose under a projection (include/mi_host.h): float64 arithmetic on the float matrices of mi_camera_frame_info, rounded once.
+int mi_camera_rays(const MiCamera* cam, int projection, float fisheyeFovDegrees, int width, int height, const float* jitterXY, int numSets, MiPtRay* rays,
+                   float* pixelAngle)
+{
+  const bool knownProjection = projection == MI_PROJECTION_PERSPECTIVE || projection == MI_PROJECTION_EQUIRECT || projection == MI_PROJECTION_FISHEYE;
+  if(!cam || !rays || width <= 0 || height <= 0 || numSets < 1 || !knownProjection
+     || (projection == MI_PROJECTION_FISHEYE && !(fisheyeFovDegrees > 0.0f && fisheyeFovDegrees <= 360.0f)))
+  {
+    g_hostError = "mi_camera_rays: need a camera, an output, width, height, numSets >= 1, a known projection and 0 < fisheyeFovDegrees <= 360";
+    return MI_PT_ERR_ARGUMENT;
+  }
+  MiSceneFrameInfo fi;
+  float            perspectiveAngle = 0.0f;
+  mi_camera_frame_info(cam, width, height, &fi, &perspectiveAngle, nullptr);
+  const float* V = fi.viewInv;
+  const float* Pi = fi.projInv;
+  const double W = double(width), H = double(height), pi = 3.14159265358979323846;
+  const double right[3] = {V[0], V[1], V[2]}, up[3] = {V[4], V[5], V[6]}, forward[3] = {-double(V[8]), -double(V[9]), -double(V[10])};
+  const double eye[3]   = {V[12], V[13], V[14]};
+  const double fovRad   = double(fisheyeFovDegrees) * pi / 180.0;
+  auto mul = [](const float* M, const double v[4], double r[4]) {
+    for(int i = 0; i < 4; ++i)
+      r[i] = double(M[i]) * v[0] + double(M[4 + i]) * v[1] + double(M[8 + i]) * v[2] + double(M[12 + i]) * v[3];
+  };
+  for(int s = 0; s < numSets; ++s)
+  {
+    const double jx = jitterXY ? double(jitterXY[2 * s]) : 0.5, jy = jitterXY ? double(jitterXY[2 * s + 1]) : 0.5;
+    for(int py = 0; py < height; ++py)
+      for(int px = 0; px < width; ++px)
+      {
+        const double x = double(px) + jx, y = double(py) + jy;
+        double       o[3] = {eye[0], eye[1], eye[2]}, d[3] = {0.0, 0.0, 0.0};
+        if(projection == MI_PROJECTION_PERSPECTIVE)
+        {
+          const double clip[4] = {x / W * 2.0 - 1.0, y / H * 2.0 - 1.0, -1.0, 1.0};
+          double       view[4], world[4];
+          mul(Pi, clip, view);
+          for(int i = 0; i < 4; ++i)
+            view[i] /= view[3];  // (view[3] last: it divides itself to 1)
+          if(cam->orthographic)
+          {
+            const double axis[4] = {0.0, 0.0, -1.0, 0.0};
+            mul(V, view, world);
+            for(int i = 0; i < 3; ++i)
+              o[i] = world[i];
+            mul(V, axis, world);
+            for(int i = 0; i < 3; ++i)
+              d[i] = world[i];
+          }
+          else
+          {
+            mul(V, view, world);
+            for(int i = 0; i < 3; ++i)
+              d[i] = world[i] - eye[i];
+          }
+        }
+        else if(projection == MI_PROJECTION_EQUIRECT)
+        {
+          const double phi = (x / W - 0.5) * 2.0 * pi, theta = (0.5 - y / H) * pi;
+          for(int i = 0; i < 3; ++i)
+            d[i] = std::cos(theta) * std::sin(phi) * right[i] + std::sin(theta) * up[i] + std::cos(theta) * std::cos(phi) * forward[i];
+        }
+        else
+        {
+          const double R = std::min(W, H) / 2.0, u = (x - W / 2.0) / R, v = (H / 2.0 - y) / R, r = std::sqrt(u * u + v * v);
+          if(r <= 1.0)  // (outside the image circle: a dead ray, zero direction)
+          {
+            const double alpha = r * fovRad / 2.0;
+            for(int i = 0; i < 3; ++i)
+              d[i] = r > 0.0 ? std::sin(alpha) * (u * right[i] + v * up[i]) / r + std::cos(alpha) * forward[i] : forward[i];
+          }
+        }
+        const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        MiPtRay&     ray = rays[(size_t(s) * size_t(height) + size_t(py)) * size_t(width) + size_t(px)];
+        for(int i = 0; i < 3; ++i)
+        {
+          ray.origin[i]    = float(o[i]);
+          ray.direction[i] = len > 0.0 ? float(d[i] / len) : 0.0f;
+        }
+        ray.tMin = 0.0f;
+        ray.tMax = 3.402823466e+38f;
+      }
+  }
+  if(pixelAngle)
+    *pixelAngle = projection == MI_PROJECTION_PERSPECTIVE ? perspectiveAngle
+                                                          : float(projection == MI_PROJECTION_EQUIRECT ? pi / H : fovRad / std::min(W, H));
+  return MI_PT_OK;
+}
 }

@@ -204,6 +204,25 @@ def camera_frame_info(cam, width, height, visualization=0):
     return fi, pa.value, fd.value
 
 
+_PROJECTIONS = {"perspective": capi.MI_PROJECTION_PERSPECTIVE, "equirect": capi.MI_PROJECTION_EQUIRECT, "fisheye": capi.MI_PROJECTION_FISHEYE}
+
+
+def camera_rays(cam, width, height, projection="equirect", fov=180.0, jitter=None):
+    """Camera rays of the pose of `cam` under a projection (mi_camera_rays, include/mi_host.h): "perspective" (the built-in camera without its
+    lens), "equirect" (a 360 degree panorama) or "fisheye" (equidistant, `fov` degrees across the image circle; outside it the rays are dead).
+    jitter: None (pixel centres, one set) or (K, 2) sample offsets inside the pixel, one set per row.  Returns (rays, pixel_angle): a
+    (K, height, width, 8) float32 array for PathTracer.set_camera_rays -- unit directions -- and the params.pixelAngle of the projection."""
+    proj = _PROJECTIONS[projection] if isinstance(projection, str) else int(projection)
+    jit = None if jitter is None else np.ascontiguousarray(jitter, dtype=np.float32).reshape(-1, 2)
+    k = 1 if jit is None else int(jit.shape[0])
+    rays = np.zeros((k, int(height), int(width), 8), dtype=np.float32)
+    pa = C.c_float()
+    _check_host(capi.host_lib().mi_camera_rays(C.byref(cam), proj, float(fov), int(width), int(height),
+                                               None if jit is None else jit.ctypes.data_as(C.POINTER(C.c_float)), k,
+                                               rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), C.byref(pa)))
+    return rays, pa.value
+
+
 class PathTracer:
     """The HIP path tracer instance (libmi_pt.so)."""
 
@@ -218,6 +237,8 @@ class PathTracer:
         _check_pt(self._l.mi_pt_create(scene.desc, C.byref(opts), C.byref(self._p)))
         self.width = self.height = 0
         self.temporal = False
+        self._camera_rays = None  # the device tensor set_camera_rays borrowed
+        self._device = int(device)
 
     def update_render_nodes(self, render_nodes, count, visible=None):
         """New transforms / materials / visibility for the instances: rebuilds the acceleration structure on the device (or refits and
@@ -410,6 +431,49 @@ class PathTracer:
     def read_selection(self):
         out = np.empty((self.height, self.width), dtype=np.uint32)
         _check_pt(self._l.mi_pt_read_selection(self._p, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def set_camera_rays(self, rays, unit=False):
+        """Start the following frames from the caller's rays instead of the built-in camera (mi_pt_set_camera_rays; include/mi_pt.h has the
+        contract).  `rays`: (K, H, W, 8) or (H, W, 8) float32 rows of origin.xyz, tMin, direction.xyz, tMax at the current size -- frame F takes
+        set F % K.  A numpy array is copied by the library; a contiguous torch tensor on this instance's device is borrowed (the wrapper keeps a
+        reference; do not write to it while frames are in flight); None unbinds.  unit: the directions are unit vectors, used bit for bit."""
+        flags = capi.MI_PT_CAMERA_RAYS_UNIT if unit else 0
+        if rays is None:
+            _check_pt(self._l.mi_pt_set_camera_rays(self._p, None, 0, 0))
+            self._camera_rays = None
+            return
+        torch_form = type(rays).__module__.split(".")[0] == "torch"
+        if not torch_form:
+            rays = np.ascontiguousarray(rays, dtype=np.float32)
+        shape = tuple(rays.shape)
+        if len(shape) == 3:
+            shape = (1,) + shape
+        if len(shape) != 4 or shape[1:] != (self.height, self.width, 8) or shape[0] < 1:
+            raise ValueError("set_camera_rays: a (K, %d, %d, 8) or (%d, %d, 8) float32 array is required" % (self.height, self.width, self.height, self.width))
+        if torch_form:
+            import torch
+            if not (rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous()):
+                raise ValueError("set_camera_rays: a contiguous float32 device tensor is required")
+            _check_pt(self._l.mi_pt_set_camera_rays_device(self._p, C.c_void_p(rays.data_ptr()), int(shape[0]), flags))
+            self._camera_rays = rays
+            return
+        _check_pt(self._l.mi_pt_set_camera_rays(self._p, rays.ctypes.data_as(C.POINTER(capi.MiPtRay)), int(shape[0]), flags))
+        self._camera_rays = None
+
+    def make_camera_rays(self, params, num_sets=1, device=False, stream=None):
+        """The rays the built-in camera generates for sample 0 of frames params.frameCount .. + num_sets - 1, for every pixel
+        (mi_pt_make_camera_rays): (num_sets, H, W, 8) float32, numpy, or with device=True a torch tensor on this instance's device written on
+        `stream` (default: torch's current stream).  Bound with unit=True they reproduce the built-in camera's single-sample frames."""
+        if device:
+            import torch
+            out = torch.empty((int(num_sets), self.height, self.width, 8), dtype=torch.float32, device="cuda:%d" % self._device)
+            if stream is None:
+                stream = torch.cuda.current_stream(out.device).cuda_stream
+            _check_pt(self._l.mi_pt_make_camera_rays_device(self._p, C.byref(params), int(num_sets), C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0)))
+            return out
+        out = np.zeros((int(num_sets), self.height, self.width, 8), dtype=np.float32)
+        _check_pt(self._l.mi_pt_make_camera_rays(self._p, C.byref(params), int(num_sets), out.ctypes.data_as(C.POINTER(capi.MiPtRay))))
         return out
 
     @staticmethod
