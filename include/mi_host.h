@@ -160,6 +160,15 @@ enum { MI_PROJECTION_PERSPECTIVE = 0, MI_PROJECTION_EQUIRECT = 1, MI_PROJECTION_
 MI_PT_API int mi_camera_rays(const MiCamera* camera, int projection, float fisheyeFovDegrees, int width, int height, const float* jitterXY, int numSets,
                              MiPtRay* hostRays, float* pixelAngle);
 
+/* The mip chain the loader gives every image (one LINEAR 2:1 blit per level, the colour channels of an sRGB image filtered in linear light):
+ * levels 1 .. N of a width x height RGBA8 level 0, tightly packed one after the other into outLevels1ToN, level i being max(1,width>>i) x
+ * max(1,height>>i), down to 1 x 1.  What MiPtTexture::levels holds for a loaded image, and what mi_pt_update_textures makes on the device with
+ * MI_PT_TEXTURE_GENERATE_MIPS.  Returns the number of levels written (0 for a 1 x 1 image); MI_PT_ERR_ARGUMENT for a NULL pointer or a
+ * size outside 1 .. 65535.  outLevels1ToN may be NULL to get the count alone. */
+MI_PT_API int mi_build_mip_chain(int width, int height, const uint8_t* rgba8, int srgb, uint8_t* outLevels1ToN);
+/* The loader's linear-to-sRGB encoder (clamp, IEC 61966-2-1, rounded to 8 bits), over an array: what the mip chain of an sRGB image ends in. */
+MI_PT_API void mi_linear_to_srgb8(const float* values, uint64_t count, uint8_t* out);
+
 MI_PT_API const char* mi_host_last_error(void);
 
 #ifdef __cplusplus

@@ -188,7 +188,7 @@ MI_PT_API int mi_pt_update_lights(MiPt* pt, const MiGltfLight* lights, int numLi
 /* replaces the material half of the scene sync of edited and animated scenes: a material marked dirty by the inspector, by undo / redo, by a
  * variant or by a KHR_animation_pointer channel (reference: src/gltf_scene.cpp:1493, src/ui_inspector.cpp:1010) and uploaded record by record by
  * SceneVk (src/gltf_scene_vk.cpp:430-487).  Takes BOTH tables again, complete: numMaterials must be the count at creation, numTextureInfos may
- * differ (slot 0 stays the reserved "no texture" entry).  Textures themselves stay resident: their images and their count cannot change here.
+ * differ (slot 0 stays the reserved "no texture" entry).  Textures themselves stay resident: their images and their count cannot change here (images: mi_pt_update_textures).
  * The call brings everything a build derives from the materials -- the instance-flag word of the triangle records, the alpha records, the
  * per-slot texture records, the scene-wide summaries that select kernels and optional buffers -- to the state mi_pt_create would give it on the
  * new tables: the next frames render bit for bit what a fresh instance renders.  It does so in place, without a build (one launch over the
@@ -525,6 +525,55 @@ typedef struct MiPtVertexUpdateInfo
 MI_PT_API int mi_pt_get_vertex_update_info(MiPt* pt, MiPtVertexUpdateInfo* info);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Texture images of resident textures, from host or device memory -- a video texture, a paint stroke, a texture a model optimises on the same
+ * GPU (our own; the reference re-creates the image).  The shape is fixed: size, level count, sRGB flag, filters and wrap modes are those of
+ * creation, only texels change; another size is a re-create.  Nothing of the acceleration structure is touched.
+ * After a successful call, frames, guides, debug views and queries (the alpha-aware _ex forms included, which read level 0 through the alpha
+ * records) return, bit for bit, what a fresh instance returns that was created from the same tables with these images in
+ * MiPtTexture::levels; mi_pt_read_texture returns the same bytes for every level.  With MI_PT_TEXTURE_GENERATE_MIPS levels 1.. are made on
+ * the device from level 0 and equal, byte for byte, the chain the host loader makes (mi_build_mip_chain, include/mi_host.h).  The bilinear
+ * footprints of every updated level are rebuilt (unless MI_PT_DIAG_NO_QUADS left them unbuilt).
+ * RGBA32F level 0 (only with GENERATE_MIPS) holds linear values: a colour channel of an sRGB texture is encoded as the loader encodes it
+ * (IEC 61966-2-1, rounded to 8 bits), every other channel is round(clamp(v, 0, 1) * 255), halves away from zero; NaN becomes 0.  The mips are
+ * then made from the quantised level 0, exactly as for RGBA8 input. */
+enum { MI_PT_TEXELS_RGBA8 = 0, MI_PT_TEXELS_RGBA32F = 1 }; /* MiPtTextureUpdate::format */
+enum { MI_PT_TEXTURE_GENERATE_MIPS = 1 };                   /* MiPtTextureUpdate::flags */
+typedef struct MiPtTextureUpdate
+{
+  int32_t            texture;       /* index into MiPtSceneDesc::textures */
+  int32_t            width, height; /* must equal the resident texture's */
+  int32_t            numLevels;     /* without GENERATE_MIPS: must equal the resident count, and levels[] is complete; with it: 1, only levels[0] is read */
+  int32_t            format;        /* MI_PT_TEXELS_*; RGBA32F only together with GENERATE_MIPS */
+  uint32_t           flags;
+  const void* const* levels;        /* level i is max(1,width>>i) x max(1,height>>i) texels, tightly packed */
+  uint32_t           reserved[2];   /* 0 */
+} MiPtTextureUpdate;
+/* New images for some of the textures; `updates` and the level pointers are host memory.  MI_PT_ERR_ARGUMENT, with nothing changed: a texture
+ * index out of range or repeated, a wrong size or level count, a NULL level, unknown format or flag bits, RGBA32F without GENERATE_MIPS, a
+ * non-zero reserved word -- and a texture that is the alpha source of a material whose geometry mi_scene_cut_alpha cut at load (the base /
+ * diffuse texture of a non-OPAQUE material, as mi_pt_update_materials finds it, on a render node whose primitive has opaqueTriangleCount > 0):
+ * that classification held for the old alpha; re-cut and re-create.  numUpdates == 0 succeeds.  Level 0 of every texture of the call is
+ * written by ONE launch, then one launch per generated level index (at most 15) covers that level of every texture, then the footprints.
+ * The images are staged through a device buffer allocated by the first call and grown, never shrunk (in rendererBytes from then on).
+ * Flushes the frame queue and synchronises the device like mi_pt_update_materials (queued frames render the old texels); the caller
+ * restarts accumulation. */
+MI_PT_API int mi_pt_update_textures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpdates);
+/* The same over device memory: `updates` and the levels[] arrays are host memory, the level pointers device memory of pt's device, 4-byte
+ * aligned (16 for RGBA32F; anything else: MI_PT_ERR_ARGUMENT).  Allocates nothing beyond the small task tables and makes no host copy of the
+ * images.  The call's device synchronisation covers whatever stream produced the images: no stream argument. */
+MI_PT_API int mi_pt_update_textures_device(MiPt* pt, const MiPtTextureUpdate* updates, int numUpdates);
+/* The resident texels of one level, max(1,width>>level) x max(1,height>>level) RGBA8: the counterpart of mi_pt_read_vertices. */
+MI_PT_API int mi_pt_read_texture(MiPt* pt, int texture, int level, uint8_t* hostRGBA8);
+typedef struct MiPtTextureUpdateInfo
+{
+  uint64_t calls;           /* successful update calls of this instance, both forms */
+  uint64_t texelsWritten;   /* texels they wrote, generated levels included, in total */
+  uint64_t levelsGenerated; /* levels made on the device, in total */
+  uint64_t launches;        /* kernel launches of the LAST call: ingest, mips, footprints */
+} MiPtTextureUpdateInfo;
+MI_PT_API int mi_pt_get_texture_update_info(MiPt* pt, MiPtTextureUpdateInfo* info);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Ray queries and picking against the resident scene (replaces nvvk::RayPicker over the TLAS: reference src/ui_renderer.cpp:95-150).
  * The rays walk the acceleration structure the frames walk, in its CURRENT state: the pose after mi_pt_update_deformation, the tree after
  * a refit, the visibility and material ids of resident mode.
@@ -730,7 +779,9 @@ MI_PT_API const char* mi_pt_version(void);
  *    entry points, no struct a caller already allocates changed.  Still 9: MiPtQueryOptions and mi_pt_default_query_options, mi_pt_query_rays_ex,
  *    mi_pt_query_rays_device_ex, mi_pt_pick_ex -- again new types and entry points only.  Still 9: MiPtVertexUpdate / MiPtVertexUpdateInfo and
  *    mi_pt_set_vertex_updates, mi_pt_update_vertices, mi_pt_update_vertices_device, mi_pt_get_vertex_update_info -- new types and entry points only.
- *    Still 9: mi_pt_set_camera_rays, mi_pt_set_camera_rays_device, mi_pt_make_camera_rays, mi_pt_make_camera_rays_device -- new entry points only.) */
+ *    Still 9: mi_pt_set_camera_rays, mi_pt_set_camera_rays_device, mi_pt_make_camera_rays, mi_pt_make_camera_rays_device -- new entry points only.
+ *    Still 9: MiPtTextureUpdate / MiPtTextureUpdateInfo and mi_pt_update_textures, mi_pt_update_textures_device, mi_pt_read_texture,
+ *    mi_pt_get_texture_update_info -- new types and entry points only.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

@@ -181,6 +181,15 @@ class MiPtVertexUpdateInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "verticesWritten", "verticesRejected", "tableBytes")]
 
 
+class MiPtTextureUpdate(C.Structure):
+    _fields_ = [("texture", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("numLevels", C.c_int32), ("format", C.c_int32), ("flags", u32),
+                ("levels", C.POINTER(C.c_void_p)), ("reserved", u32 * 2)]
+
+
+class MiPtTextureUpdateInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "texelsWritten", "levelsGenerated", "launches")]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -198,10 +207,13 @@ assert C.sizeof(MiPtRayHit) == 64
 assert C.sizeof(MiPtQueryOptions) == 32
 assert C.sizeof(MiPtVertexUpdate) == 40
 assert C.sizeof(MiPtVertexUpdateInfo) == 32
+assert C.sizeof(MiPtTextureUpdate) == 40 and C.sizeof(MiPtTextureUpdateInfo) == 32
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
 MI_PT_VERTICES_RECOMPUTE_NORMALS = 1
+MI_PT_TEXELS_RGBA8, MI_PT_TEXELS_RGBA32F = 0, 1
+MI_PT_TEXTURE_GENERATE_MIPS = 1
 # mi_scene_animation_changes (include/mi_host.h)
 (MI_SCENE_CHANGED_NODES, MI_SCENE_CHANGED_LIGHTS, MI_SCENE_CHANGED_DEFORMATION, MI_SCENE_CHANGED_MATERIALS, MI_SCENE_CHANGED_CAMERAS,
  MI_SCENE_CHANGED_VISIBILITY) = 1, 2, 4, 8, 16, 32
@@ -288,6 +300,8 @@ HOST_SYMBOLS = {
     "mi_default_params": (None, [P(MiPathtraceParams)]),
     "mi_camera_frame_info": (None, [P(MiCamera), i32, i32, P(MiSceneFrameInfo), P(f32), P(f32)]),
     "mi_camera_rays": (i32, [P(MiCamera), i32, f32, i32, i32, P(f32), i32, P(MiPtRay), P(f32)]),
+    "mi_build_mip_chain": (i32, [i32, i32, C.c_void_p, i32, C.c_void_p]),
+    "mi_linear_to_srgb8": (None, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "mi_host_last_error": (C.c_char_p, []),
 }
 
@@ -355,6 +369,10 @@ PT_SYMBOLS = {
     "mi_pt_update_vertices": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
     "mi_pt_update_vertices_device": (i32, [VP, P(MiPtVertexUpdate), i32, i32]),
     "mi_pt_get_vertex_update_info": (i32, [VP, P(MiPtVertexUpdateInfo)]),
+    "mi_pt_update_textures": (i32, [VP, P(MiPtTextureUpdate), i32]),
+    "mi_pt_update_textures_device": (i32, [VP, P(MiPtTextureUpdate), i32]),
+    "mi_pt_read_texture": (i32, [VP, i32, i32, C.c_void_p]),
+    "mi_pt_get_texture_update_info": (i32, [VP, P(MiPtTextureUpdateInfo)]),
     "mi_pt_set_camera_rays": (i32, [VP, P(MiPtRay), i32, u32]),
     "mi_pt_set_camera_rays_device": (i32, [VP, VP, i32, u32]),
     "mi_pt_make_camera_rays": (i32, [VP, P(MiPathtraceParams), i32, P(MiPtRay)]),

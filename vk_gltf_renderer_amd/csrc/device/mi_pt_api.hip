@@ -20,6 +20,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_deform.h"
+#include "pt_texture_update.h"
 #include "pt_vertex_update.h"
 #include "pt_kernels.h"
 #include "pt_query.h"
@@ -221,6 +222,10 @@ struct MiPt
   DevBuf<uint32_t>              vuBlockTask;    // [0, vuBlockCap): the ingest's blocks, [vuBlockCap, 2 vuBlockCap): the rebuild's; the last word: rejected vertices
   size_t                        vuBlockCap = 0;
   DevBuf<uint8_t>               vuStaging;      // the host form's arrays: allocated by the first such call and grown (rendererBytes)
+  // ---- texture image updates (mi_pt_update_textures[_device])
+  DevBuf<uint8_t>               tuStaging;      // the host form's images: allocated by the first such call and grown (rendererBytes)
+  DevBuf<float>                 tuTables;       // decode / encode tables of the mip generator (pt_texture_update.h), made by the first call (sceneBytes)
+  uint64_t                      tuCalls = 0, tuTexels = 0, tuLevels = 0, tuLaunches = 0;
   uint64_t                      vuCalls = 0, vuWritten = 0, vuRejected = 0;
   int                           bvhBuilder = 0;
   // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
@@ -2139,6 +2144,222 @@ int mi_pt_get_vertex_update_info(MiPt* pt, MiPtVertexUpdateInfo* out)
   return MI_PT_OK;
 }
 
+// Both forms of a texture update.  `device`: the level pointers are device memory, read by the kernels where they lie.
+static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpdates, bool device, const char* name)
+{
+  const std::string fn = name;
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": null instance");
+  if(numUpdates < 0 || (numUpdates > 0 && !updates))
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": negative count or null table");
+  // ---- validation: nothing changes when any texture of the call is refused
+  const int            numTextures = int(pt->hostTextures.size());
+  std::vector<uint8_t> seen(size_t(numTextures), 0);
+  size_t               stagingBytes = 0;
+  auto levelTexels = [](const pt::DevTexture& d, int l) { return size_t(std::max(1, int(d.width) >> l)) * size_t(std::max(1, int(d.height) >> l)); };
+  for(int k = 0; k < numUpdates; ++k)
+  {
+    const MiPtTextureUpdate& u   = updates[k];
+    const std::string        who = fn + ": update " + std::to_string(k) + ": ";
+    if(u.texture < 0 || u.texture >= numTextures)
+      return fail(MI_PT_ERR_ARGUMENT, who + "texture " + std::to_string(u.texture) + " out of range");
+    if(seen[size_t(u.texture)]++)
+      return fail(MI_PT_ERR_ARGUMENT, who + "texture " + std::to_string(u.texture) + " listed twice");
+    const pt::DevTexture& d = pt->hostTextures[size_t(u.texture)];
+    if(u.width != int(d.width) || u.height != int(d.height))
+      return fail(MI_PT_ERR_ARGUMENT, who + "the size differs from the resident texture's (a new size is a re-create)");
+    if((u.format != MI_PT_TEXELS_RGBA8 && u.format != MI_PT_TEXELS_RGBA32F) || (u.flags & ~uint32_t(MI_PT_TEXTURE_GENERATE_MIPS)))
+      return fail(MI_PT_ERR_ARGUMENT, who + "unknown format or flag bits");
+    const bool generate = (u.flags & MI_PT_TEXTURE_GENERATE_MIPS) != 0;
+    if(u.format == MI_PT_TEXELS_RGBA32F && !generate)
+      return fail(MI_PT_ERR_ARGUMENT, who + "RGBA32F only together with MI_PT_TEXTURE_GENERATE_MIPS");
+    if(u.numLevels != (generate ? 1 : int(d.numLevels)))
+      return fail(MI_PT_ERR_ARGUMENT, who + "numLevels must be 1 with MI_PT_TEXTURE_GENERATE_MIPS, the resident count without");
+    if(u.reserved[0] || u.reserved[1])
+      return fail(MI_PT_ERR_ARGUMENT, who + "reserved words must be 0");
+    if(!u.levels)
+      return fail(MI_PT_ERR_ARGUMENT, who + "no levels");
+    const size_t texelBytes = u.format == MI_PT_TEXELS_RGBA32F ? 16 : 4;
+    for(int l = 0; l < u.numLevels; ++l)
+    {
+      if(!u.levels[l])
+        return fail(MI_PT_ERR_ARGUMENT, who + "level " + std::to_string(l) + " is NULL");
+      if(device && (reinterpret_cast<uintptr_t>(u.levels[l]) & (texelBytes - 1)))
+        return fail(MI_PT_ERR_ARGUMENT, who + "a device pointer that is not " + std::to_string(texelBytes) + "-byte aligned");
+      if(!device)
+        stagingBytes += align16(levelTexels(d, l) * texelBytes);
+    }
+  }
+  // the OPAQUE class of the load-time alpha cut was found under the old texels: its triangles skip the alpha test for good
+  {
+    const int numMaterials = int(pt->hostMaterials.size()), numPrims = int(pt->hostPrims.size());
+    for(size_t n = 0; n < pt->hostNodes.size() && numMaterials > 0; ++n)
+    {
+      const size_t   m    = size_t(std::max(0, std::min(pt->hostNodes[n].materialID, numMaterials - 1)));
+      const int      prim = pt->hostNodes[n].renderPrimID;
+      const AlphaKey key  = alphaKey(pt->hostMaterials[m], pt->hostTexInfos.data());
+      if(key.alphaMode != MI_ALPHA_OPAQUE && key.slot > 0 && key.index >= 0 && key.index < numTextures && seen[size_t(key.index)] && prim >= 0 && prim < numPrims
+         && pt->hostPrims[size_t(prim)].opaqueTriangles > 0)
+        return fail(MI_PT_ERR_ARGUMENT, fn + ": texture " + std::to_string(key.index) + " is the alpha source of a material whose geometry was cut at load: re-cut and re-create (material "
+                                            + std::to_string(m) + ", render node " + std::to_string(n) + ")");
+    }
+  }
+  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still sample the old texels; the caller's streams have produced the device images
+  const auto t0 = std::chrono::steady_clock::now();
+  if(numUpdates == 0)
+  {
+    ++pt->tuCalls;
+    pt->tuLaunches = 0;
+    return MI_PT_OK;
+  }
+  if(!pt->tuTables.ptr)
+  {
+    std::vector<float> tables(size_t{pt::TU_TABLE_FLOATS});
+    pt::tuBuildTables(tables.data(), pt::tuHostLinearToSrgb8);
+    HIP_TRY(pt->tuTables.upload(tables.data(), tables.size()));
+  }
+  if(stagingBytes > pt->tuStaging.count)
+    HIP_TRY(pt->tuStaging.alloc(stagingBytes));
+  // ---- task tables.  Level 0 of every texture: one ingest launch.  A complete caller-supplied chain: its levels 1.. are ingest tasks of
+  // the same launch.  Generated levels: the tasks of level index l of every texture lie together, one launch per l.
+  std::vector<pt::TextureIngestTask> ingest;
+  std::vector<uint32_t>              ingestBlocks;
+  std::vector<pt::TextureMipTask>    mips[16];
+  std::vector<uint32_t>              mipBlocks[16];
+  size_t                             off = 0;
+  uint64_t                           texels = 0, generated = 0;
+  auto                               blocksOf = [](size_t n) { return (n + pt::TEXTURE_UPDATE_BLOCK - 1) / pt::TEXTURE_UPDATE_BLOCK; };
+  for(int k = 0; k < numUpdates; ++k)
+  {
+    const MiPtTextureUpdate& u = updates[k];
+    const pt::DevTexture&    d = pt->hostTextures[size_t(u.texture)];
+    uint32_t* const          pool = reinterpret_cast<uint32_t*>(pt->texels.ptr);
+    const bool               f32 = u.format == MI_PT_TEXELS_RGBA32F;
+    for(int l = 0; l < u.numLevels; ++l)
+    {
+      const size_t          n = levelTexels(d, l), bytes = n * (f32 ? 16 : 4);
+      pt::TextureIngestTask t{};
+      if(device)
+        t.src = u.levels[l];
+      else
+      {
+        t.src = pt->tuStaging.ptr + off;
+        HIP_TRY(hipMemcpy(pt->tuStaging.ptr + off, u.levels[l], bytes, hipMemcpyHostToDevice));  // (straight from the caller's memory: no host copy)
+        off += align16(bytes);
+      }
+      t.dst        = pool + d.levelOffset[l];
+      t.texelCount = uint32_t(n);
+      t.firstBlock = uint32_t(ingestBlocks.size());
+      t.flags      = (d.srgb ? pt::TU_SRGB : 0u) | (f32 ? pt::TU_FLOAT : 0u);
+      ingestBlocks.insert(ingestBlocks.end(), blocksOf(n), uint32_t(ingest.size()));
+      ingest.push_back(t);
+      texels += n;
+    }
+    if(u.flags & MI_PT_TEXTURE_GENERATE_MIPS)
+      for(int l = 1; l < int(d.numLevels); ++l)
+      {
+        pt::TextureMipTask t{};
+        t.src        = pool + d.levelOffset[l - 1];
+        t.dst        = pool + d.levelOffset[l];
+        t.sw         = uint32_t(std::max(1, int(d.width) >> (l - 1)));
+        t.sh         = uint32_t(std::max(1, int(d.height) >> (l - 1)));
+        t.dw         = uint32_t(std::max(1, int(d.width) >> l));
+        t.dh         = uint32_t(std::max(1, int(d.height) >> l));
+        t.firstBlock = uint32_t(mipBlocks[l].size());
+        t.flags      = d.srgb ? pt::TU_SRGB : 0u;
+        mipBlocks[l].insert(mipBlocks[l].end(), blocksOf(size_t(t.dw) * t.dh), uint32_t(mips[l].size()));
+        mips[l].push_back(t);
+        texels += size_t(t.dw) * t.dh;
+        ++generated;
+      }
+  }
+  std::vector<pt::TextureMipTask> mipTasks;
+  std::vector<uint32_t>           blockTask = ingestBlocks;
+  size_t                          mipTaskAt[16] = {}, mipBlockAt[16] = {};
+  for(int l = 1; l < 16; ++l)
+  {
+    mipTaskAt[l]  = mipTasks.size();
+    mipBlockAt[l] = blockTask.size();
+    mipTasks.insert(mipTasks.end(), mips[l].begin(), mips[l].end());
+    blockTask.insert(blockTask.end(), mipBlocks[l].begin(), mipBlocks[l].end());
+  }
+  DevBuf<pt::TextureIngestTask> devIngest;
+  DevBuf<pt::TextureMipTask>    devMips;
+  DevBuf<uint32_t>              devBlockTask;
+  HIP_TRY(devIngest.upload(ingest.data(), ingest.size()));
+  HIP_TRY(devMips.upload(mipTasks.data(), mipTasks.size()));
+  HIP_TRY(devBlockTask.upload(blockTask.data(), blockTask.size()));
+  uint64_t launches = 0;
+  pt::launchTextureIngest(devIngest.ptr, devBlockTask.ptr, uint32_t(ingestBlocks.size()), pt->tuTables.ptr, nullptr);
+  launches += ingestBlocks.empty() ? 0 : 1;
+  HIP_TRY(hipGetLastError());
+  for(int l = 1; l < 16; ++l)  // (on the one stream: level l reads the quantised level l - 1)
+    if(!mips[l].empty())
+    {
+      pt::launchTextureMips(devMips.ptr + mipTaskAt[l], devBlockTask.ptr + mipBlockAt[l], uint32_t(mipBlocks[l].size()), pt->tuTables.ptr, nullptr);
+      ++launches;
+    }
+  HIP_TRY(hipGetLastError());
+  // ---- the bilinear footprints of every level the call wrote, with the kernel of mi_pt_create
+  if(pt->texQuads.ptr)
+    for(int k = 0; k < numUpdates; ++k)
+    {
+      const pt::DevTexture& d = pt->hostTextures[size_t(updates[k].texture)];
+      for(int l = 0; l < int(d.numLevels); ++l)
+      {
+        pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], std::max(1, int(d.width) >> l), std::max(1, int(d.height) >> l), d.wrapS, d.wrapT, nullptr);
+        ++launches;
+      }
+    }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());  // (the task tables are released on return)
+  if(buildTiming)
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "texture update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  ++pt->tuCalls;
+  pt->tuTexels += texels;
+  pt->tuLevels += generated;
+  pt->tuLaunches = launches;
+  return MI_PT_OK;
+}
+
+int mi_pt_update_textures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpdates)
+{
+  FLUSH_PENDING(pt);
+  return updateTextures(pt, updates, numUpdates, false, "mi_pt_update_textures");
+}
+
+int mi_pt_update_textures_device(MiPt* pt, const MiPtTextureUpdate* updates, int numUpdates)
+{
+  FLUSH_PENDING(pt);
+  return updateTextures(pt, updates, numUpdates, true, "mi_pt_update_textures_device");
+}
+
+int mi_pt_read_texture(MiPt* pt, int texture, int level, uint8_t* hostRGBA8)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !hostRGBA8 || texture < 0 || texture >= int(pt->hostTextures.size()) || level < 0 || level >= int(pt->hostTextures[size_t(texture)].numLevels))
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_texture: no such texture or level, or a null destination");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const pt::DevTexture& d = pt->hostTextures[size_t(texture)];
+  const size_t          n = size_t(std::max(1, int(d.width) >> level)) * size_t(std::max(1, int(d.height) >> level));
+  HIP_TRY(hipMemcpy(hostRGBA8, pt->texels.ptr + d.levelOffset[level], n * 4, hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+
+int mi_pt_get_texture_update_info(MiPt* pt, MiPtTextureUpdateInfo* out)
+{
+  if(!pt || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_texture_update_info: null argument");
+  out->calls           = pt->tuCalls;
+  out->texelsWritten   = pt->tuTexels;
+  out->levelsGenerated = pt->tuLevels;
+  out->launches        = pt->tuLaunches;
+  return MI_PT_OK;
+}
+
 int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
 {
   FLUSH_PENDING(pt);
@@ -3405,12 +3626,12 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                          + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->alphaTris.bytes()
                          + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deformPool.bytes() + pt->deformTasks.bytes()
                          + pt->deformBlockTask.bytes() + pt->deformJoints.bytes() + pt->deformWeights.bytes() + refitBytes(pt) + pt->vmPrevPositions.bytes() + pt->vmPrims.bytes()
-                         + pt->vmDeformIDs.bytes() + pt->vuTable.bytes() + pt->vuTasks.bytes() + pt->vuNormalTasks.bytes() + pt->vuBlockTask.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
+                         + pt->vmDeformIDs.bytes() + pt->vuTable.bytes() + pt->vuTasks.bytes() + pt->vuNormalTasks.bytes() + pt->vuBlockTask.bytes() + pt->tuTables.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
   const uint64_t pathState = pt->pathArrays.bytes() + pt->optThroughput.bytes() + pt->optMisc.bytes() + pt->optMedium.bytes() + pt->optPixelSum.bytes() + pt->optGuides.bytes()
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
                             + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));

@@ -457,4 +457,37 @@ int mi_camera_rays(const MiCamera* cam, int projection, float fisheyeFovDegrees,
                                                           : float(projection == MI_PROJECTION_EQUIRECT ? pi / H : fovRad / std::min(W, H));
   return MI_PT_OK;
 }
+// The loader's mip chain of one image (include/mi_host.h): buildMipChain, levels 1.. packed one after the other.
+int mi_build_mip_chain(int width, int height, const uint8_t* rgba8, int srgb, uint8_t* outLevels1ToN)
+{
+  if(!rgba8 || width < 1 || height < 1 || width > 65535 || height > 65535)
+  {
+    g_hostError = "mi_build_mip_chain: need level 0 and a size of 1 .. 65535";
+    return MI_PT_ERR_ARGUMENT;
+  }
+  if(!outLevels1ToN)
+  {
+    int n = 0;
+    for(int w = width, h = height; w > 1 || h > 1; w = std::max(1, w / 2), h = std::max(1, h / 2))
+      ++n;
+    return n;
+  }
+  mihost::Image base;
+  base.width  = width;
+  base.height = height;
+  base.rgba.assign(rgba8, rgba8 + size_t(width) * size_t(height) * 4);
+  std::vector<std::vector<uint8_t>> levels;
+  mihost::buildMipChain(base, srgb != 0, levels);
+  for(size_t l = 1; l < levels.size(); ++l)
+  {
+    memcpy(outLevels1ToN, levels[l].data(), levels[l].size());
+    outLevels1ToN += levels[l].size();
+  }
+  return int(levels.size()) - 1;
+}
+void mi_linear_to_srgb8(const float* values, uint64_t count, uint8_t* out)
+{
+  for(uint64_t i = 0; values && out && i < count; ++i)
+    out[i] = mihost::linearToSrgb8(values[i]);
+}
 }

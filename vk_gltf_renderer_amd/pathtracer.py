@@ -325,6 +325,71 @@ class PathTracer:
         _check_pt(self._l.mi_pt_get_vertex_update_info(self._p, C.byref(a)))
         return {n: int(getattr(a, n)) for n, _ in a._fields_}
 
+    def update_textures(self, updates, generate_mips=True):
+        """New images for resident textures (mi_pt_update_textures / mi_pt_update_textures_device): {texture index: image}.  An image is an
+        H x W x 4 array of the resident size: numpy uint8 (RGBA8) or float32 (linear RGBA32F, quantised on the device) through the host form,
+        contiguous torch uint8 / float32 tensors on this instance's device through the device form, read where they lie.  generate_mips:
+        the image is level 0 and the device makes the chain the host loader would; without it the value is the list of ALL levels, uint8.
+        Mixing numpy arrays and device tensors in one call is an error.  Restart the accumulation afterwards."""
+        def is_device(a):
+            return hasattr(a, "data_ptr") and hasattr(a, "is_contiguous")
+        table = (capi.MiPtTextureUpdate * max(len(updates), 1))()
+        keep, forms = [], set()
+        for k, (index, levels) in enumerate(updates.items()):
+            levels = list(levels) if isinstance(levels, (tuple, list)) else [levels]
+            if not levels or (generate_mips and len(levels) != 1):
+                raise ValueError(f"update_textures: texture {index}: one image with generate_mips, the list of all levels without")
+            ptrs = (C.c_void_p * len(levels))()
+            kinds = set()
+            for l, a in enumerate(levels):
+                forms.add(is_device(a))
+                if is_device(a):
+                    if str(a.dtype) not in ("torch.uint8", "torch.float32") or not a.is_contiguous() or a.device.type != "cuda":
+                        raise ValueError(f"update_textures: texture {index}: level {l} must be a contiguous uint8 or float32 tensor on the device")
+                    kinds.add(str(a.dtype) == "torch.float32")
+                    shape, ptrs[l] = tuple(a.shape), a.data_ptr()
+                else:
+                    a = np.asarray(a)
+                    if a.dtype not in (np.uint8, np.float32):
+                        raise ValueError(f"update_textures: texture {index}: level {l} must be uint8 or float32, not {a.dtype}")
+                    a = np.ascontiguousarray(a)
+                    kinds.add(a.dtype == np.float32)
+                    shape, ptrs[l] = a.shape, a.ctypes.data
+                keep.append(a)
+                if len(shape) != 3 or shape[2] != 4:
+                    raise ValueError(f"update_textures: texture {index}: level {l} has shape {shape}, not H x W x 4")
+                if l == 0:
+                    height, width = int(shape[0]), int(shape[1])
+                elif (int(shape[0]), int(shape[1])) != (max(1, height >> l), max(1, width >> l)):
+                    raise ValueError(f"update_textures: texture {index}: level {l} has shape {shape}")
+            if len(kinds) > 1:
+                raise ValueError(f"update_textures: texture {index}: uint8 and float32 levels")
+            keep.append(ptrs)
+            u = table[k]
+            u.texture, u.width, u.height, u.numLevels = int(index), width, height, len(levels)
+            u.format = capi.MI_PT_TEXELS_RGBA32F if True in kinds else capi.MI_PT_TEXELS_RGBA8
+            u.flags = capi.MI_PT_TEXTURE_GENERATE_MIPS if generate_mips else 0
+            u.levels = C.cast(ptrs, C.POINTER(C.c_void_p))
+        if len(forms) > 1:
+            raise ValueError("update_textures: numpy arrays and device tensors in one call")
+        fn = self._l.mi_pt_update_textures_device if True in forms else self._l.mi_pt_update_textures
+        _check_pt(fn(self._p, table, len(updates)))
+
+    def read_texture(self, index, level=0):
+        """The resident texels of one level of texture `index` (mi_pt_read_texture): H x W x 4 uint8."""
+        d = self._scene.desc.contents
+        known = 0 <= int(index) < int(d.numTextures) and 0 <= int(level) < 16  # (the library refuses what is not)
+        h, w = (int(d.textures[int(index)].height), int(d.textures[int(index)].width)) if known else (1, 1)
+        out = np.zeros((max(1, h >> int(level)) if known else 1, max(1, w >> int(level)) if known else 1, 4), np.uint8)
+        _check_pt(self._l.mi_pt_read_texture(self._p, int(index), int(level), out.ctypes.data))
+        return out
+
+    def texture_update_info(self):
+        """mi_pt_get_texture_update_info as a dict: calls, texelsWritten, levelsGenerated (all in total), launches (last call)."""
+        a = capi.MiPtTextureUpdateInfo()
+        _check_pt(self._l.mi_pt_get_texture_update_info(self._p, C.byref(a)))
+        return {n: int(getattr(a, n)) for n, _ in a._fields_}
+
     ACCEL_MODES = {"rebuild": 0, "refit": 1, "auto": 2}
 
     def set_accel_update(self, mode, rebuild_cost_ratio=1.5):
