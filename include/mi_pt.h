@@ -574,6 +574,56 @@ typedef struct MiPtTextureUpdateInfo
 MI_PT_API int mi_pt_get_texture_update_info(MiPt* pt, MiPtTextureUpdateInfo* info);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The HDR environment from raw texels, host or device memory -- a video dome, a sky baked per frame, a map a model optimises on the same
+ * GPU (our own; the reference re-creates the HdrIbl).  mi_pt_set_environment takes a FINISHED environment: pdf in alpha, alias table,
+ * integral, all made by one host thread (mi_hdr_from_pixels).  These calls take the texels alone and make the rest on the device.
+ * Resident state after a successful call: rgb = the caller's values, alpha = the sampling pdf, one alias entry per texel, with the host's
+ * formulas (HdrEnvironment::buildAccel): importance_i = float(area_row * double(max(r,g,b))), the row areas computed in double on the host
+ * and uploaded; total = the double sum of the importances; integral = float(total); alpha = max(r,g,b) * float(1.0 / total).  A map with
+ * total <= 0 gets the uniform table: q = 1, alias = i, alpha = float(1 / (4 pi)), integral = 0.
+ * The alias table is a prefix-sum construction in double (csrc/device/pt_env_update.h), not Vose's loop: it is a valid table of
+ * the same distribution -- the slots q_i + sum of (1 - q_j) over alias_j = i reproduce importance_i / total to float rounding of q --
+ * but not the host's table entry by entry; rgb equals the host route's bit for bit, integral within 1 float ulp, alpha within 2.
+ * Every floating sum runs in one fixed order: the same texels give the same bytes, from either form, on every call.
+ * A size equal to the resident environment's is written in place, nothing is allocated; another size, or no environment, allocates like
+ * mi_pt_set_environment.  The scratch (about 12 bytes per texel: the index lists and prefix arrays) is allocated by the first call, grown,
+ * never shrunk (in rendererBytes; MiPtEnvironmentUpdateInfo::scratchBytes).
+ * Flushes the frame queue and synchronises the device like mi_pt_update_textures (queued frames render the old map; the synchronisation
+ * covers whatever stream produced a device image: no stream argument); the caller restarts accumulation. */
+typedef struct MiPtEnvironmentUpdate
+{
+  int32_t     width, height; /* >= 1; width*height <= 2^26 */
+  int32_t     channels;      /* 3 (RGB32F) or 4 (RGBA32F, input alpha ignored) */
+  uint32_t    flags;         /* 0 */
+  const void* pixels;        /* lat-long, row 0 = +Y pole, tightly packed */
+  uint32_t    reserved[2];   /* 0 */
+} MiPtEnvironmentUpdate;
+/* pixels: host memory.  MI_PT_ERR_ARGUMENT, with nothing changed: a NULL pointer, a size or channel count out of range, unknown flags, a
+ * non-zero reserved word, a component (alpha apart) that is not finite or is negative.  The texels are staged inside the scratch and the
+ * resident map, then the device form's kernels run: both forms leave the same bytes. */
+MI_PT_API int mi_pt_update_environment(MiPt* pt, const MiPtEnvironmentUpdate* update);
+/* pixels: device memory of pt's device, 4-byte aligned (16 for channels == 4; anything else: MI_PT_ERR_ARGUMENT), read where it lies.  The
+ * values cannot be validated: the ingest kernel replaces a non-finite or negative component by 0 and counts the texel in texelsSanitised; a
+ * NaN never reaches the sum. */
+MI_PT_API int mi_pt_update_environment_device(MiPt* pt, const MiPtEnvironmentUpdate* update);
+/* The resident environment, however it was set: width*height RGBA32F texels, as many alias entries, the size, the integral.  Any pointer may
+ * be NULL.  MI_PT_ERR_STATE when no environment is resident. */
+MI_PT_API int mi_pt_read_environment(MiPt* pt, float* hostRGBA, MiEnvAccel* hostAccel, int* width, int* height, float* integral);
+typedef struct MiPtEnvironmentUpdateInfo
+{
+  uint64_t calls;           /* successful update calls of this instance, both forms */
+  uint64_t texelsWritten;   /* texels they wrote, in total */
+  uint64_t texelsSanitised; /* LAST call: texels with a component replaced by 0 (device form) */
+  uint64_t launches;        /* LAST call: kernel launches */
+  uint64_t lightTexels;     /* LAST call: texels with q < 1 (0 for the uniform table) */
+  uint64_t heavyTexels;     /* LAST call: texels with q >= 1 (0 for the uniform table) */
+  uint64_t scratchBytes;    /* the scratch as it stands */
+  float    integral;        /* LAST call */
+  uint32_t reserved;
+} MiPtEnvironmentUpdateInfo;
+MI_PT_API int mi_pt_get_environment_update_info(MiPt* pt, MiPtEnvironmentUpdateInfo* info);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Ray queries and picking against the resident scene (replaces nvvk::RayPicker over the TLAS: reference src/ui_renderer.cpp:95-150).
  * The rays walk the acceleration structure the frames walk, in its CURRENT state: the pose after mi_pt_update_deformation, the tree after
  * a refit, the visibility and material ids of resident mode.
@@ -781,7 +831,9 @@ MI_PT_API const char* mi_pt_version(void);
  *    mi_pt_set_vertex_updates, mi_pt_update_vertices, mi_pt_update_vertices_device, mi_pt_get_vertex_update_info -- new types and entry points only.
  *    Still 9: mi_pt_set_camera_rays, mi_pt_set_camera_rays_device, mi_pt_make_camera_rays, mi_pt_make_camera_rays_device -- new entry points only.
  *    Still 9: MiPtTextureUpdate / MiPtTextureUpdateInfo and mi_pt_update_textures, mi_pt_update_textures_device, mi_pt_read_texture,
- *    mi_pt_get_texture_update_info -- new types and entry points only.) */
+ *    mi_pt_get_texture_update_info -- new types and entry points only.  Still 9: MiPtEnvironmentUpdate / MiPtEnvironmentUpdateInfo and
+ *    mi_pt_update_environment, mi_pt_update_environment_device, mi_pt_read_environment, mi_pt_get_environment_update_info -- new types and
+ *    entry points only.) */
 #define MI_PT_ABI_VERSION 9
 MI_PT_API int mi_pt_abi_version(void);
 

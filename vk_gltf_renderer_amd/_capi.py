@@ -190,6 +190,15 @@ class MiPtTextureUpdateInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "texelsWritten", "levelsGenerated", "launches")]
 
 
+class MiPtEnvironmentUpdate(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("flags", u32), ("pixels", C.c_void_p), ("reserved", u32 * 2)]
+
+
+class MiPtEnvironmentUpdateInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "texelsWritten", "texelsSanitised", "launches", "lightTexels", "heavyTexels", "scratchBytes")] + [
+        ("integral", f32), ("reserved", u32)]
+
+
 class MiCamera(C.Structure):
     _fields_ = [("eye", f32 * 3), ("center", f32 * 3), ("up", f32 * 3), ("fovDegrees", f32), ("znear", f32),
                 ("zfar", f32), ("orthographic", i32), ("xmag", f32), ("ymag", f32)]
@@ -208,6 +217,7 @@ assert C.sizeof(MiPtQueryOptions) == 32
 assert C.sizeof(MiPtVertexUpdate) == 40
 assert C.sizeof(MiPtVertexUpdateInfo) == 32
 assert C.sizeof(MiPtTextureUpdate) == 40 and C.sizeof(MiPtTextureUpdateInfo) == 32
+assert C.sizeof(MiPtEnvironmentUpdate) == 32 and C.sizeof(MiPtEnvironmentUpdateInfo) == 64
 
 MI_PT_ABI_VERSION = 9  # include/mi_pt.h
 MI_PT_DEFORM_DEFER_BUILD = 1
@@ -373,6 +383,10 @@ PT_SYMBOLS = {
     "mi_pt_update_textures_device": (i32, [VP, P(MiPtTextureUpdate), i32]),
     "mi_pt_read_texture": (i32, [VP, i32, i32, C.c_void_p]),
     "mi_pt_get_texture_update_info": (i32, [VP, P(MiPtTextureUpdateInfo)]),
+    "mi_pt_update_environment": (i32, [VP, P(MiPtEnvironmentUpdate)]),
+    "mi_pt_update_environment_device": (i32, [VP, P(MiPtEnvironmentUpdate)]),
+    "mi_pt_read_environment": (i32, [VP, C.c_void_p, C.c_void_p, P(i32), P(i32), P(f32)]),
+    "mi_pt_get_environment_update_info": (i32, [VP, P(MiPtEnvironmentUpdateInfo)]),
     "mi_pt_set_camera_rays": (i32, [VP, P(MiPtRay), i32, u32]),
     "mi_pt_set_camera_rays_device": (i32, [VP, VP, i32, u32]),
     "mi_pt_make_camera_rays": (i32, [VP, P(MiPathtraceParams), i32, P(MiPtRay)]),

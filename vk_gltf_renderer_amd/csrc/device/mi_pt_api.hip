@@ -20,6 +20,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_deform.h"
+#include "pt_env_update.h"
 #include "pt_texture_update.h"
 #include "pt_vertex_update.h"
 #include "pt_kernels.h"
@@ -226,6 +227,11 @@ struct MiPt
   DevBuf<uint8_t>               tuStaging;      // the host form's images: allocated by the first such call and grown (rendererBytes)
   DevBuf<float>                 tuTables;       // decode / encode tables of the mip generator (pt_texture_update.h), made by the first call (sceneBytes)
   uint64_t                      tuCalls = 0, tuTexels = 0, tuLevels = 0, tuLaunches = 0;
+  // ---- environment updates (mi_pt_update_environment[_device])
+  DevBuf<uint8_t>               euScratch;      // header, row areas, tile sums, prefix arrays, index lists (pt_env_update.h): grown, never shrunk (rendererBytes)
+  float                         envIntegral = 0.0f;  // of the resident environment (mi_pt_read_environment)
+  uint64_t                      euCalls = 0, euTexels = 0, euSanitised = 0, euLaunches = 0, euLight = 0, euHeavy = 0;
+  float                         euIntegral = 0.0f;
   uint64_t                      vuCalls = 0, vuWritten = 0, vuRejected = 0;
   int                           bvhBuilder = 0;
   // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
@@ -2360,6 +2366,175 @@ int mi_pt_get_texture_update_info(MiPt* pt, MiPtTextureUpdateInfo* out)
   return MI_PT_OK;
 }
 
+// Both forms of an environment update.  `device`: u->pixels is device memory, read by the ingest kernel where it lies.
+static int updateEnvironment(MiPt* pt, const MiPtEnvironmentUpdate* u, bool device, const char* name)
+{
+  const std::string fn = name;
+  if(!pt || !u)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": null instance or update");
+  // ---- validation: nothing changes when the call is refused
+  if(!u->pixels)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": null pixels");
+  if(u->width < 1 || u->height < 1 || uint64_t(u->width) * uint64_t(u->height) > uint64_t(pt::ENV_MAX_TEXELS))
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": need width, height >= 1 and width * height <= 2^26");
+  if(u->channels != 3 && u->channels != 4)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": channels must be 3 or 4");
+  if(u->flags)
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": unknown flag bits");
+  if(u->reserved[0] || u->reserved[1])
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": reserved words must be 0");
+  const uint32_t n        = uint32_t(u->width) * uint32_t(u->height);
+  const size_t   channels = size_t(u->channels);
+  if(device && (reinterpret_cast<uintptr_t>(u->pixels) & (channels == 4 ? 15u : 3u)))
+    return fail(MI_PT_ERR_ARGUMENT, fn + ": a device pointer that is not " + std::to_string(channels == 4 ? 16 : 4) + "-byte aligned");
+  if(!device)
+  {
+    const float* px = static_cast<const float*>(u->pixels);
+    for(size_t i = 0; i < n; ++i)
+      for(size_t c = 0; c < 3; ++c)
+      {
+        const float v = px[i * channels + c];
+        if(!(v >= 0.0f && v <= FLT_MAX))
+          return fail(MI_PT_ERR_ARGUMENT, fn + ": texel " + std::to_string(i) + " has a component that is not finite or is negative");
+      }
+  }
+  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old map; the caller's streams have produced the device image
+  const auto t0 = std::chrono::steady_clock::now();
+  // ---- memory: the scratch grows, the map and the table are replaced only when the texel count differs
+  const pt::EnvScratchLayout L = pt::euScratchLayout(n, uint32_t(u->height));
+  if(L.bytes > pt->euScratch.count)
+    HIP_TRY(pt->euScratch.alloc(L.bytes));
+  if(pt->envPixels.count != n || pt->envAccel.count != n)
+  {
+    DevBuf<float4>     pixels;
+    DevBuf<MiEnvAccel> accel;
+    HIP_TRY(pixels.alloc(n));
+    HIP_TRY(accel.alloc(n));
+    pt->envPixels = std::move(pixels);
+    pt->envAccel  = std::move(accel);
+  }
+  pt->scene.envPixels = pt->envPixels.ptr;
+  pt->scene.envAccel  = pt->envAccel.ptr;
+  pt->scene.envWidth  = u->width;
+  pt->scene.envHeight = u->height;
+  pt->sceneDevDirty   = true;
+  uint8_t* const  base = pt->euScratch.ptr;
+  pt::EnvArgs     A{};
+  A.n          = n;
+  A.width      = uint32_t(u->width);
+  A.channels   = uint32_t(channels);
+  A.numTiles   = pt::euNumTiles(n);
+  A.pixels     = pt->envPixels.ptr;
+  A.accel      = pt->envAccel.ptr;
+  A.rowArea    = reinterpret_cast<const double*>(base + L.rowArea);
+  A.header     = reinterpret_cast<pt::EnvHeader*>(base + L.header);
+  A.tileImp    = reinterpret_cast<double*>(base + L.tileImp);
+  A.tiles      = reinterpret_cast<pt::EnvTriple*>(base + L.tiles);
+  A.prefix     = reinterpret_cast<double*>(base + L.prefix);
+  A.index      = reinterpret_cast<uint32_t*>(base + L.index);
+  A.uniformPdf = pt::euUniformPdf();
+  if(device)
+    A.src = static_cast<const float*>(u->pixels);
+  else
+  {
+    // RGBA32F goes straight into the resident map, which the ingest then rewrites texel by texel; RGB32F into the prefix and index arrays
+    // (12 bytes per texel), which nothing writes before the ingest has read them
+    void* const stage = channels == 4 ? static_cast<void*>(pt->envPixels.ptr) : static_cast<void*>(base + L.prefix);
+    HIP_TRY(hipMemcpy(stage, u->pixels, size_t(n) * channels * sizeof(float), hipMemcpyHostToDevice));
+    A.src = static_cast<const float*>(stage);
+  }
+  {
+    std::vector<double> area(size_t(u->height));
+    pt::euRowAreas(u->width, u->height, area.data());
+    HIP_TRY(hipMemcpy(base + L.rowArea, area.data(), area.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemset(base + L.header, 0, sizeof(pt::EnvHeader)));
+  struct Timing
+  {
+    std::chrono::steady_clock::time_point last;
+    hipError_t                            error = hipSuccess;
+  } timing{std::chrono::steady_clock::now()};
+  auto passDone = [](const char* pass, void* user) {
+    Timing&          T = *static_cast<Timing*>(user);
+    const hipError_t e = hipDeviceSynchronize();
+    T.error            = T.error != hipSuccess ? T.error : e;
+    const auto now     = std::chrono::steady_clock::now();
+    fprintf(stderr, "[mi_pt build] %-28s %8.3f ms\n", pass, std::chrono::duration<double, std::milli>(now - T.last).count());
+    T.last = now;
+  };
+  pt::launchEnvUpdate(A, nullptr, buildTiming ? +passDone : nullptr, &timing);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(timing.error);
+  pt::EnvHeader header{};
+  HIP_TRY(hipMemcpy(&header, base + L.header, sizeof(header), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  if(buildTiming)
+    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "environment update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  const bool lit  = header.total > 0.0;
+  pt->envIntegral = float(header.total);
+  ++pt->euCalls;
+  pt->euTexels += n;
+  pt->euSanitised = header.sanitised;
+  pt->euLaunches  = uint64_t(pt::ENV_UPDATE_LAUNCHES);
+  pt->euLight     = lit ? header.numLight : 0u;
+  pt->euHeavy     = lit ? n - header.numLight : 0u;
+  pt->euIntegral  = pt->envIntegral;
+  return MI_PT_OK;
+}
+
+int mi_pt_update_environment(MiPt* pt, const MiPtEnvironmentUpdate* update)
+{
+  FLUSH_PENDING(pt);
+  return updateEnvironment(pt, update, false, "mi_pt_update_environment");
+}
+
+int mi_pt_update_environment_device(MiPt* pt, const MiPtEnvironmentUpdate* update)
+{
+  FLUSH_PENDING(pt);
+  return updateEnvironment(pt, update, true, "mi_pt_update_environment_device");
+}
+
+int mi_pt_read_environment(MiPt* pt, float* hostRGBA, MiEnvAccel* hostAccel, int* width, int* height, float* integral)
+{
+  FLUSH_PENDING(pt);
+  if(!pt)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_environment: null instance");
+  if(!pt->envPixels.ptr || !pt->envAccel.ptr)
+    return fail(MI_PT_ERR_STATE, "mi_pt_read_environment: no environment is resident");
+  HIP_TRY(hipSetDevice(pt->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t n = size_t(pt->scene.envWidth) * size_t(pt->scene.envHeight);
+  if(hostRGBA)
+    HIP_TRY(hipMemcpy(hostRGBA, pt->envPixels.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+  if(hostAccel)
+    HIP_TRY(hipMemcpy(hostAccel, pt->envAccel.ptr, n * sizeof(MiEnvAccel), hipMemcpyDeviceToHost));
+  if(width)
+    *width = pt->scene.envWidth;
+  if(height)
+    *height = pt->scene.envHeight;
+  if(integral)
+    *integral = pt->envIntegral;
+  return MI_PT_OK;
+}
+
+int mi_pt_get_environment_update_info(MiPt* pt, MiPtEnvironmentUpdateInfo* out)
+{
+  if(!pt || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_environment_update_info: null argument");
+  *out                 = MiPtEnvironmentUpdateInfo{};
+  out->calls           = pt->euCalls;
+  out->texelsWritten   = pt->euTexels;
+  out->texelsSanitised = pt->euSanitised;
+  out->launches        = pt->euLaunches;
+  out->lightTexels     = pt->euLight;
+  out->heavyTexels     = pt->euHeavy;
+  out->scratchBytes    = pt->euScratch.bytes();
+  out->integral        = pt->euIntegral;
+  return MI_PT_OK;
+}
+
 int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
 {
   FLUSH_PENDING(pt);
@@ -2491,6 +2666,7 @@ int mi_pt_set_environment(MiPt* pt, const MiPtEnvironment* env)
   pt->scene.envAccel  = pt->envAccel.ptr;
   pt->scene.envWidth  = env->width;
   pt->scene.envHeight = env->height;
+  pt->envIntegral     = env->integral;
   pt->sceneDevDirty   = true;
   return MI_PT_OK;
 }
@@ -3631,7 +3807,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->euScratch.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
                             + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));

@@ -390,6 +390,44 @@ class PathTracer:
         _check_pt(self._l.mi_pt_get_texture_update_info(self._p, C.byref(a)))
         return {n: int(getattr(a, n)) for n, _ in a._fields_}
 
+    def update_environment(self, pixels):
+        """A new HDR environment from its texels alone (mi_pt_update_environment / mi_pt_update_environment_device): an H x W x 3 or H x W x 4
+        lat-long image, row 0 at the +Y pole; the input alpha is ignored.  A numpy float32 array (anything np.asarray takes) goes through the
+        host form, which refuses non-finite and negative components; a contiguous float32 torch tensor on this instance's device through the
+        device form, read where it lies, with such components replaced by 0.  The pdf and the alias table are made on the device; a size equal
+        to the resident one is written in place.  Restart the accumulation afterwards."""
+        device = hasattr(pixels, "data_ptr") and hasattr(pixels, "is_contiguous")
+        if device:
+            if str(pixels.dtype) != "torch.float32" or not pixels.is_contiguous() or pixels.device.type != "cuda":
+                raise ValueError("update_environment: the tensor must be a contiguous float32 tensor on the device")
+            shape, ptr = tuple(pixels.shape), pixels.data_ptr()
+        else:
+            pixels = np.ascontiguousarray(pixels, dtype=np.float32)
+            shape, ptr = pixels.shape, pixels.ctypes.data
+        if len(shape) != 3 or shape[2] not in (3, 4) or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"update_environment: the image has shape {shape}, not H x W x 3 or H x W x 4")
+        u = capi.MiPtEnvironmentUpdate()
+        u.width, u.height, u.channels, u.pixels = int(shape[1]), int(shape[0]), int(shape[2]), ptr
+        fn = self._l.mi_pt_update_environment_device if device else self._l.mi_pt_update_environment
+        _check_pt(fn(self._p, C.byref(u)))
+
+    def read_environment(self):
+        """The resident environment (mi_pt_read_environment): (rgba, alias, q, integral) -- H x W x 4 float32 with the pdf in alpha, H x W uint32
+        and float32 of the alias table, the integral.  MiError (rc=-4) when none is resident."""
+        w, h, integral = C.c_int32(), C.c_int32(), C.c_float()
+        _check_pt(self._l.mi_pt_read_environment(self._p, None, None, C.byref(w), C.byref(h), C.byref(integral)))
+        rgba = np.empty((h.value, w.value, 4), np.float32)
+        accel = np.empty((h.value, w.value), np.dtype([("alias", "<u4"), ("q", "<f4")]))
+        _check_pt(self._l.mi_pt_read_environment(self._p, rgba.ctypes.data, accel.ctypes.data, None, None, None))
+        return rgba, np.ascontiguousarray(accel["alias"]), np.ascontiguousarray(accel["q"]), float(integral.value)
+
+    def environment_update_info(self):
+        """mi_pt_get_environment_update_info as a dict: calls, texelsWritten (in total); texelsSanitised, launches, lightTexels, heavyTexels,
+        integral (last call); scratchBytes."""
+        a = capi.MiPtEnvironmentUpdateInfo()
+        _check_pt(self._l.mi_pt_get_environment_update_info(self._p, C.byref(a)))
+        return {n: (float(a.integral) if n == "integral" else int(getattr(a, n))) for n, _ in a._fields_ if n != "reserved"}
+
     ACCEL_MODES = {"rebuild": 0, "refit": 1, "auto": 2}
 
     def set_accel_update(self, mode, rebuild_cost_ratio=1.5):
