@@ -202,37 +202,46 @@ struct MiPt
   std::vector<uint32_t>         primTriangles;  // per render primitive: triangle count, 0 when it has no usable geometry
   std::vector<pt::DevPrim>      hostPrims;      // the device addresses of every primitive's streams (mi_pt_read_vertices, deformation)
   std::vector<uint32_t>         primVertices;   // per render primitive: vertex count
+  // ---- the state that exists only while a feature is in force: one struct per feature, reset by assigning a fresh value (a DevBuf's move
+  // assignment releases what it held, in the order of the members), summed by its own bytes()
   // skins and morph targets (mi_pt_set_deformation): static tables, allocated only for a scene that deforms something
-  DevBuf<uint8_t>               deformPool;     // base poses, influences, deltas (16-byte aligned sub-allocations)
-  DevBuf<pt::DeformTask>        deformTasks;
-  DevBuf<uint32_t>              deformBlockTask;
-  DevBuf<float4>                deformJoints;   // 6 float4 per joint matrix (pt_deform.h)
-  DevBuf<float>                 deformWeights;
-  int                           deformJointCount = 0, deformWeightCount = 0;
-  uint32_t                      deformBlocks = 0;
-  bool                          deformSet = false;
-  std::vector<int>              deformPrimIDs;  // the render primitives the deformation tables deform
-  // caller-driven vertices (mi_pt_set_vertex_updates): everything below exists only while primitives are declared
-  bool                          vuSet = false;
-  std::vector<int>              vuPrimIDs;      // the declared render primitives
-  std::vector<uint8_t>          vuDeclared;     // per render primitive: declared
-  std::vector<size_t>           vuCornerEnd, vuCorners;  // per render primitive: word offsets of its incident-corner table in vuTable, SIZE_MAX = none
-  DevBuf<uint32_t>              vuTable;        // the incident-corner tables (MI_PT_VERTICES_RECOMPUTE_NORMALS): per primitive V run ends, then 3 T corners
-  DevBuf<pt::VertexUpdateTask>  vuTasks;        // task tables of an update call, sized for a call that carries every declared primitive
-  DevBuf<pt::NormalRebuildTask> vuNormalTasks;
-  DevBuf<uint32_t>              vuBlockTask;    // [0, vuBlockCap): the ingest's blocks, [vuBlockCap, 2 vuBlockCap): the rebuild's; the last word: rejected vertices
-  size_t                        vuBlockCap = 0;
-  DevBuf<uint8_t>               vuStaging;      // the host form's arrays: allocated by the first such call and grown (rendererBytes)
+  struct Deformation
+  {
+    DevBuf<uint8_t>        pool;     // base poses, influences, deltas (16-byte aligned sub-allocations)
+    DevBuf<pt::DeformTask> tasks;
+    DevBuf<uint32_t>       blockTask;
+    DevBuf<float4>         joints;   // 6 float4 per joint matrix (pt_deform.h)
+    DevBuf<float>          weights;
+    int                    jointCount = 0, weightCount = 0;
+    uint32_t               blocks = 0;
+    bool                   set = false;
+    std::vector<int>       primIDs;  // the render primitives the deformation tables deform
+    uint64_t               bytes() const { return pool.bytes() + tasks.bytes() + blockTask.bytes() + joints.bytes() + weights.bytes(); }
+  } deform;
+  // caller-driven vertices (mi_pt_set_vertex_updates): exists only while primitives are declared
+  struct VertexUpdates
+  {
+    bool                          set = false;
+    std::vector<int>              primIDs;      // the declared render primitives
+    std::vector<uint8_t>          declared;     // per render primitive: declared
+    std::vector<size_t>           cornerEnd, corners;  // per render primitive: word offsets of its incident-corner table in `table`, SIZE_MAX = none
+    DevBuf<uint32_t>              table;        // the incident-corner tables (MI_PT_VERTICES_RECOMPUTE_NORMALS): per primitive V run ends, then 3 T corners
+    DevBuf<pt::VertexUpdateTask>  tasks;        // task tables of an update call, sized for a call that carries every declared primitive
+    DevBuf<pt::NormalRebuildTask> normalTasks;
+    DevBuf<uint32_t>              blockTask;    // [0, blockCap): the ingest's blocks, [blockCap, 2 blockCap): the rebuild's; the last word: rejected vertices
+    size_t                        blockCap = 0;
+    uint64_t                      bytes() const { return table.bytes() + tasks.bytes() + normalTasks.bytes() + blockTask.bytes(); }
+  } vu;
+  DevBuf<uint8_t>               vuStaging;      // the host form's arrays: allocated by the first such call and grown (rendererBytes); outlives a declaration
+  MiPtVertexUpdateInfo          vuInfo{};       // the counters of mi_pt_get_vertex_update_info (tableBytes is computed there); they outlive a declaration too
   // ---- texture image updates (mi_pt_update_textures[_device])
   DevBuf<uint8_t>               tuStaging;      // the host form's images: allocated by the first such call and grown (rendererBytes)
   DevBuf<float>                 tuTables;       // decode / encode tables of the mip generator (pt_texture_update.h), made by the first call (sceneBytes)
-  uint64_t                      tuCalls = 0, tuTexels = 0, tuLevels = 0, tuLaunches = 0;
+  MiPtTextureUpdateInfo         tuInfo{};       // the counters of mi_pt_get_texture_update_info
   // ---- environment updates (mi_pt_update_environment[_device])
   DevBuf<uint8_t>               euScratch;      // header, row areas, tile sums, prefix arrays, index lists (pt_env_update.h): grown, never shrunk (rendererBytes)
   float                         envIntegral = 0.0f;  // of the resident environment (mi_pt_read_environment)
-  uint64_t                      euCalls = 0, euTexels = 0, euSanitised = 0, euLaunches = 0, euLight = 0, euHeavy = 0;
-  float                         euIntegral = 0.0f;
-  uint64_t                      vuCalls = 0, vuWritten = 0, vuRejected = 0;
+  MiPtEnvironmentUpdateInfo     euInfo{};       // the counters of mi_pt_get_environment_update_info (scratchBytes is computed there)
   int                           bvhBuilder = 0;
   // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
   int                           accelMode = MI_PT_ACCEL_REBUILD;
@@ -241,12 +250,16 @@ struct MiPt
   bool                          switchBuild = false;  // the build of mi_pt_set_accel_update is running
   bool                          refitCapable = false; // the last build went through the device collapse: a build in REFIT / AUTO mode keeps refit data
   uint64_t                      accelRefits = 0, trianglesMoved = 0;
-  double                        sahAtBuild = 0.0, sahNow = 0.0;
-  DevBuf<pt::RefitBox>          refitSlotBox, refitBuiltBox, refitNodeBox;  // per slot: current box, box the build filed; per node: its box
-  DevBuf<float>                 refitSah;         // per node: its SAH term
-  DevBuf<double>                refitSahPartial;  // the cost reduction (pt::REFIT_SAH_PARTIALS + 1)
-  DevBuf<uint8_t>               refitDirty;       // per render node: pt::REFIT_CLEAN / MOVED / HOME
-  std::vector<uint32_t>         refitLevels;      // level starts of the node array + the node count; empty = no refit data
+  struct RefitData  // what a build keeps for the refits after it, and a build or a switch to REBUILD drops
+  {
+    DevBuf<pt::RefitBox>  slotBox, builtBox, nodeBox;  // per slot: current box, box the build filed; per node: its box
+    DevBuf<float>         sah;         // per node: its SAH term
+    DevBuf<double>        sahPartial;  // the cost reduction (pt::REFIT_SAH_PARTIALS + 1)
+    DevBuf<uint8_t>       dirty;       // per render node: pt::REFIT_CLEAN / MOVED / HOME
+    std::vector<uint32_t> levels;      // level starts of the node array + the node count; empty = no refit data
+    double                sahAtBuild = 0.0, sahNow = 0.0;
+    uint64_t              bytes() const { return slotBox.bytes() + builtBox.bytes() + nodeBox.bytes() + sah.bytes() + sahPartial.bytes() + dirty.bytes(); }
+  } refit;
   std::vector<MiGltfRenderNode> builtNodes;       // the node table of the last full build
   std::vector<uint8_t>          primDirty;        // per render primitive: deformed since the last acceleration update ...
   std::vector<uint8_t>          primDeformed;     // ... since the last full build
@@ -289,23 +302,32 @@ struct MiPt
                                                // feed it, so it may lag behind accumFrames -- the SVGF pass then falls back to its spatial variance
   const float4*           denoised = nullptr;  // result of the last mi_pt_denoise (one of denoiseA / denoiseB)
   // motion vectors and temporal reprojection (mi_pt_set_temporal; temporal.hip)
-  bool                    temporal = false;
+  bool                    temporal = false;      // as requested
   bool                    haveFirstHit = false;  // pt->firstHit holds the records of a first-frame batch
-  bool                    haveMotion = false, haveHistory = false;
-  int                     historyCur = 0;        // which of the two history sets the last mi_pt_denoise_temporal wrote
-  DevBuf<float4>          motion, history;       // history: 2 sets x 3 records x pixels
-  DevBuf<float>           prevObjectToWorld;     // 16 floats per render node: the matrices of the pose rendered before
+  struct Temporal  // what allocTemporal makes at the current size while `temporal` is on
+  {
+    DevBuf<float4> motion, history;       // history: 2 sets x 3 records x pixels
+    DevBuf<float>  prevObjectToWorld;     // 16 floats per render node: the matrices of the pose rendered before
+    bool           haveMotion = false, haveHistory = false;
+    int            historyCur = 0;        // which of the two history sets the last mi_pt_denoise_temporal wrote
+    uint64_t       bytes() const { return motion.bytes() + history.bytes() + prevObjectToWorld.bytes(); }
+  } temporalData;
   std::vector<uint32_t>   ownedTilesHost;        // host copy of ownedTiles (mi_pt_read_first_hit)
-  // vertex motion (mi_pt_set_vertex_motion): in force while temporal and deformSet (or vuSet) are too (vertexMotionActive); everything below exists only then
+  // vertex motion (mi_pt_set_vertex_motion): in force while temporal and deform.set (or vu.set) are too (vertexMotionActive); `vm` exists only then.
+  // The first-hit triangle records follow the number of pixel slots as well (allocFirstHitTri): a lifetime of their own
   bool                    vertexMotion = false;  // as requested
   bool                    haveFirstHitTri = false;  // a first-frame batch wrote firstHitTri
-  bool                    vmPoseDirty = false;   // mi_pt_update_deformation ran since the last snapshot of the positions
   DevBuf<uint4>           firstHitTri;           // PathSoA::firstHitTri: per PIXEL slot
-  DevBuf<uint8_t>         vmPrevPositions;       // previous-pose positions of the deforming primitives: 12 B per vertex, each primitive padded to 16 B
-  DevBuf<pt::VertexMotionPrim> vmPrims;          // one record per render primitive
-  DevBuf<uint32_t>        vmDeformIDs;           // the deforming render primitives (k_snapshot_positions)
-  std::vector<size_t>     vmPrevOffset;          // per render primitive: byte offset into vmPrevPositions, SIZE_MAX = does not deform
-  uint32_t                vmMaxVertices = 0;
+  struct VertexMotion
+  {
+    DevBuf<uint8_t>              prevPositions;    // previous-pose positions of the deforming primitives: 12 B per vertex, each primitive padded to 16 B
+    DevBuf<pt::VertexMotionPrim> prims;            // one record per render primitive
+    DevBuf<uint32_t>             deformIDs;        // the deforming render primitives (k_snapshot_positions)
+    std::vector<size_t>          prevOffset;       // per render primitive: byte offset into prevPositions, SIZE_MAX = does not deform
+    uint32_t                     maxVertices = 0;
+    bool                         poseDirty = false;  // mi_pt_update_deformation ran since the last snapshot of the positions
+    uint64_t                     bytes() const { return prevPositions.bytes() + prims.bytes() + deformIDs.bytes(); }
+  } vm;
   DevBuf<uint32_t>        tonemapped, tmHistogram;
   DevBuf<float>           tmAutoState;
   float4*                 accum = nullptr;  // accumOwn.ptr or caller-bound memory
@@ -359,7 +381,103 @@ namespace {
 
 size_t align16(size_t v) { return (v + 15u) & ~size_t(15); }
 
-bool vertexMotionActive(const MiPt* pt) { return pt->vertexMotion && pt->temporal && (pt->deformSet || pt->vuSet); }
+// log2 of the tile size (a power of two: mi_pt_set_tile_partition)
+int tileShiftOf(const MiPt* pt)
+{
+  int shift = 0;
+  while((1 << shift) < pt->tileSize)
+    ++shift;
+  return shift;
+}
+
+// Pixel origin x0 | y0 << 16 of every tile of the image that `rank` of `world` renders (world <= 1: every tile)
+std::vector<uint32_t> tileOrigins(const MiPt* pt, int rank, int world)
+{
+  const int             T = pt->tileSize;
+  std::vector<uint32_t> origins;
+  for(int t = 0; t < pt->tilesX * pt->tilesY; ++t)
+    if(world <= 1 || (t % world) == rank)
+      origins.push_back(uint32_t((t % pt->tilesX) * T) | (uint32_t((t / pt->tilesX) * T) << 16));
+  return origins;
+}
+
+// Width, height and texel count of mip level `l` of a texture (MiPtTexture or pt::DevTexture)
+struct LevelExtent
+{
+  int    w, h;
+  size_t texels;
+};
+template <typename Texture>
+LevelExtent levelExtent(const Texture& d, int l)
+{
+  const int w = std::max(1, int(d.width) >> l), h = std::max(1, int(d.height) >> l);
+  return {w, h, size_t(w) * size_t(h)};
+}
+
+// The resident environment (envPixels / envAccel; empty = none) as the kernels see it
+void publishEnvironment(MiPt* pt, int width, int height)
+{
+  pt->scene.envPixels = pt->envPixels.ptr;
+  pt->scene.envAccel  = pt->envAccel.ptr;
+  pt->scene.envWidth  = width;
+  pt->scene.envHeight = height;
+  pt->sceneDevDirty   = true;
+}
+
+// The host copy of the node table and the visibility flags (NULL = all visible) that the next build or refit reads
+void keepNodeTable(MiPt* pt, const MiGltfRenderNode* renderNodes, int numRenderNodes, const uint8_t* renderNodeVisible)
+{
+  pt->hostNodes.assign(renderNodes, renderNodes + numRenderNodes);
+  if(renderNodeVisible)
+    pt->hostVisible.assign(renderNodeVisible, renderNodeVisible + numRenderNodes);
+  else
+    pt->hostVisible.clear();
+}
+
+// Diagnostics: wall time of the phases of the scene build and of every update on stderr.  The switch is read from the
+// environment once; tools/build_time.py and tools/time_env_update.py parse the lines.
+using BuildClock = std::chrono::steady_clock;
+bool buildTiming()
+{
+  static const bool on = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  return on;
+}
+void printBuildTiming(const char* what, BuildClock::time_point since, int decimals = 2)
+{
+  if(buildTiming())
+    fprintf(stderr, "[mi_pt build] %-28s %8.*f ms\n", what, decimals, std::chrono::duration<double, std::milli>(BuildClock::now() - since).count());
+}
+
+// The "whole image to host" step of the read-backs, behind the caller's refusals: `bytesPerPixel` per pixel of the current size from `src` into
+// `host` (NULL: no copy -- an image of mi_pt_read_guides the caller does not want), after a device synchronisation unless an earlier image of
+// the same call brought it
+int readImage(MiPt* pt, const void* src, size_t bytesPerPixel, void* host, bool synchronise = true)
+{
+  if(synchronise)
+  {
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  if(host)
+    HIP_TRY(hipMemcpy(host, src, size_t(pt->width) * size_t(pt->height) * bytesPerPixel, hipMemcpyDeviceToHost));
+  return MI_PT_OK;
+}
+// The slot-to-pixel scatter of the first-hit read-backs: every byte of the image `fill`, then the 16-byte record of every slot that `keep`
+// accepts and that lies inside the image (the slots of a tile cut by the border do not), at its pixel
+template <typename Keep>
+void scatterSlots(const MiPt* pt, const void* bySlot, size_t numSlots, int fill, void* host, Keep keep)
+{
+  memset(host, fill, size_t(pt->width) * size_t(pt->height) * 16);
+  const int tileShift = tileShiftOf(pt);
+  for(uint32_t slot = 0; slot < uint32_t(numSlots); ++slot)
+  {
+    int px, py;
+    if(keep(slot) && pt::pixelOfSlot(pt->ownedTilesHost.data(), tileShift, pt->width, pt->height, slot, px, py))
+      memcpy(static_cast<uint8_t*>(host) + 16 * (size_t(py) * size_t(pt->width) + size_t(px)), static_cast<const uint8_t*>(bySlot) + 16 * size_t(slot), 16);
+  }
+}
+
+bool vertexMotionActive(const MiPt* pt) { return pt->vertexMotion && pt->temporal && (pt->deform.set || pt->vu.set); }
 
 // The first-hit triangle records of vertex motion, at the current number of pixel slots; none while the feature is not in force.
 int allocFirstHitTri(MiPt* pt)
@@ -380,43 +498,38 @@ int allocFirstHitTri(MiPt* pt)
 // positions initialised to the resident ones.  The caller has synchronised the device.
 int allocVertexMotion(MiPt* pt)
 {
-  pt->vmPrevPositions.release();
-  pt->vmPrims.release();
-  pt->vmDeformIDs.release();
-  pt->vmPrevOffset.clear();
-  pt->vmMaxVertices = 0;
-  pt->vmPoseDirty   = false;
+  pt->vm = MiPt::VertexMotion{};
   if(int rc = allocFirstHitTri(pt))
     return rc;
   if(!vertexMotionActive(pt))
     return MI_PT_OK;
   const size_t numPrims = pt->hostPrims.size();
-  pt->vmPrevOffset.assign(numPrims, SIZE_MAX);
+  pt->vm.prevOffset.assign(numPrims, SIZE_MAX);
   size_t                bytes = 0;
   std::vector<uint32_t> ids;
-  std::vector<int> moving = pt->deformPrimIDs;  // (the two lists are disjoint: each call refuses a primitive of the other)
-  moving.insert(moving.end(), pt->vuPrimIDs.begin(), pt->vuPrimIDs.end());
+  std::vector<int> moving = pt->deform.primIDs;  // (the two lists are disjoint: each call refuses a primitive of the other)
+  moving.insert(moving.end(), pt->vu.primIDs.begin(), pt->vu.primIDs.end());
   for(int id : moving)
   {
-    pt->vmPrevOffset[size_t(id)] = bytes;
+    pt->vm.prevOffset[size_t(id)] = bytes;
     bytes += align16(size_t(pt->primVertices[size_t(id)]) * 12);
-    pt->vmMaxVertices = std::max(pt->vmMaxVertices, pt->primVertices[size_t(id)]);
+    pt->vm.maxVertices = std::max(pt->vm.maxVertices, pt->primVertices[size_t(id)]);
     ids.push_back(uint32_t(id));
   }
-  HIP_TRY(pt->vmPrevPositions.alloc(std::max<size_t>(bytes, 16)));
+  HIP_TRY(pt->vm.prevPositions.alloc(std::max<size_t>(bytes, 16)));
   std::vector<pt::VertexMotionPrim> table(numPrims);
   for(size_t i = 0; i < numPrims; ++i)
   {
     pt::VertexMotionPrim& v = table[i];
-    v.prevPositions = pt->vmPrevOffset[i] != SIZE_MAX ? reinterpret_cast<const float*>(pt->vmPrevPositions.ptr + pt->vmPrevOffset[i]) : nullptr;
+    v.prevPositions = pt->vm.prevOffset[i] != SIZE_MAX ? reinterpret_cast<const float*>(pt->vm.prevPositions.ptr + pt->vm.prevOffset[i]) : nullptr;
     v.positions     = pt->hostPrims[i].positions;
     v.indices       = pt->hostPrims[i].indices;
     v.numTriangles  = i < pt->primTriangles.size() ? pt->primTriangles[i] : 0u;
     v.vertexCount   = pt->primVertices[i];
   }
-  HIP_TRY(pt->vmPrims.upload(table.data(), table.size()));
-  HIP_TRY(pt->vmDeformIDs.upload(ids.data(), ids.size()));
-  pt::launchSnapshotPositions(pt->vmPrims.ptr, pt->vmDeformIDs.ptr, uint32_t(ids.size()), pt->vmMaxVertices, nullptr);
+  HIP_TRY(pt->vm.prims.upload(table.data(), table.size()));
+  HIP_TRY(pt->vm.deformIDs.upload(ids.data(), ids.size()));
+  pt::launchSnapshotPositions(pt->vm.prims.ptr, pt->vm.deformIDs.ptr, uint32_t(ids.size()), pt->vm.maxVertices, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   return MI_PT_OK;
@@ -548,20 +661,16 @@ int ensureOptionalPathArrays(MiPt* pt, bool stateBySlot, bool multiSample, bool 
 // The motion image, the history and the previous matrices of mi_pt_set_temporal, at the current size; nothing is valid afterwards.
 int allocTemporal(MiPt* pt)
 {
-  pt->haveMotion = pt->haveHistory = false;
-  pt->historyCur = 0;
-  pt->motion.release();
-  pt->history.release();
-  pt->prevObjectToWorld.release();
+  pt->temporalData = MiPt::Temporal{};
   if(!pt->temporal)
     return allocVertexMotion(pt);
   const size_t px = size_t(std::max(pt->width, 0)) * size_t(std::max(pt->height, 0));
-  HIP_TRY(pt->motion.alloc(px));
-  HIP_TRY(pt->history.alloc(6 * px));
-  HIP_TRY(pt->prevObjectToWorld.alloc(pt->nodes.count * 16));
+  HIP_TRY(pt->temporalData.motion.alloc(px));
+  HIP_TRY(pt->temporalData.history.alloc(6 * px));
+  HIP_TRY(pt->temporalData.prevObjectToWorld.alloc(pt->nodes.count * 16));
   if(px)
-    HIP_TRY(hipMemset(pt->motion.ptr, 0, px * sizeof(float4)));
-  pt::launchSnapshotTransforms(pt->nodes.ptr, pt->prevObjectToWorld.ptr, int(pt->nodes.count), nullptr);
+    HIP_TRY(hipMemset(pt->temporalData.motion.ptr, 0, px * sizeof(float4)));
+  pt::launchSnapshotTransforms(pt->nodes.ptr, pt->temporalData.prevObjectToWorld.ptr, int(pt->nodes.count), nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   return allocVertexMotion(pt);
@@ -572,19 +681,14 @@ int allocFrameResources(MiPt* pt)
   const int W = pt->width, H = pt->height, T = pt->tileSize;
   pt->tilesX = (W + T - 1) / T;
   pt->tilesY = (H + T - 1) / T;
-  std::vector<uint32_t> owned;  // pixel origin x0 | y0 << 16 of every tile this rank renders
-  for(int t = 0; t < pt->tilesX * pt->tilesY; ++t)
-    if(pt->tileWorld <= 1 || (t % pt->tileWorld) == pt->tileRank)
-      owned.push_back(uint32_t((t % pt->tilesX) * T) | (uint32_t((t / pt->tilesX) * T) << 16));
+  const std::vector<uint32_t> owned = tileOrigins(pt, pt->tileRank, pt->tileWorld);  // the tiles this rank renders
   pt->numSlots = int(owned.size()) * T * T;
   HIP_TRY(pt->ownedTiles.upload(owned.data(), owned.size()));
   pt->ownedTilesHost = owned;
   pt->allTiles.release();
   if(pt->tileWorld > 1)  // (mi_pt_make_camera_rays writes every pixel whatever the partition, and its device form may not allocate)
   {
-    std::vector<uint32_t> all;
-    for(int t = 0; t < pt->tilesX * pt->tilesY; ++t)
-      all.push_back(uint32_t((t % pt->tilesX) * T) | (uint32_t((t / pt->tilesX) * T) << 16));
+    const std::vector<uint32_t> all = tileOrigins(pt, 0, 1);
     HIP_TRY(pt->allTiles.upload(all.data(), all.size()));
   }
   if(int rc = allocPathResources(pt, pt->framesCap))
@@ -631,19 +735,17 @@ hipEvent_t getEvent(MiPt* pt, size_t& cursor)
 // updates of animated scenes (mi_pt_update_render_nodes; reference: TLAS update, src/gltf_scene_transform_vk.cpp:534-639) alike.
 int buildAccelerationUnguarded(MiPt* pt);
 void dropAcceleration(MiPt* pt);
-void releaseRefitData(MiPt* pt);
 // A failed (re)build must not leave the scene descriptor pointing at freed or half-built arrays: mi_pt_update_render_nodes runs
 // this once per animated frame, and the next mi_pt_render_frame would walk them.  On any error the instance falls back to an
 // EMPTY structure (frames render the environment only) and the error is returned to the caller.
 int buildAcceleration(MiPt* pt)
 {
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
-  const auto        t0          = std::chrono::steady_clock::now();
-  const int         rc          = buildAccelerationUnguarded(pt);
-  if(buildTiming && pt->accelBuilds > 1)  // (the first build's phases are printed by mi_pt_create)
+  const auto t0 = BuildClock::now();
+  const int  rc = buildAccelerationUnguarded(pt);
+  if(buildTiming() && pt->accelBuilds > 1)  // (the first build's phases are printed by mi_pt_create)
   {
     (void)hipDeviceSynchronize();
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "rebuild", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    printBuildTiming("rebuild", t0);
   }
   pt->lastUpdate = MI_PT_ACCEL_LAST_BUILD;
   if(rc != MI_PT_OK)
@@ -664,17 +766,15 @@ void publishAcceleration(MiPt* pt)
 // The state a failed build or refit leaves: an EMPTY structure, no refit data, the error message kept.
 void dropAcceleration(MiPt* pt)
 {
-  {
-    const std::string why = g_lastError;  // (the frees below must not disturb the message)
-    releaseRefitData(pt);
-    pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
-    pt->bvh8Planes.release(); pt->shadeTris.release(); pt->alphaTris.release();
-    publishAcceleration(pt);
-    pt::DevScene& S = pt->scene;
-    S.numTris = 0; S.bvh8NumNodes = 0; S.bvhRoot = pt::BVH_EMPTY;
-    pt->staticStats.bvhNodeCount = pt->staticStats.bvhTriangleCount = 0;
-    g_lastError = why;
-  }
+  const std::string why = g_lastError;  // (the frees below must not disturb the message)
+  pt->refit = MiPt::RefitData{};
+  pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
+  pt->bvh8Planes.release(); pt->shadeTris.release(); pt->alphaTris.release();
+  publishAcceleration(pt);
+  pt::DevScene& S = pt->scene;
+  S.numTris = 0; S.bvh8NumNodes = 0; S.bvhRoot = pt::BVH_EMPTY;
+  pt->staticStats.bvhNodeCount = pt->staticStats.bvhTriangleCount = 0;
+  g_lastError = why;
 }
 // Per render node: its material's instance flags, and INST_FLIP_FACING for a mirroring matrix (the triangle records carry them); sets the
 // scene-wide material summaries (hasAlpha, ...) on the way.  The build and the refit both take them from here.
@@ -708,21 +808,24 @@ std::vector<uint8_t> instanceFlags(MiPt* pt)
   return flags;
 }
 
-void releaseRefitData(MiPt* pt)
-{
-  pt->refitSlotBox.release(); pt->refitBuiltBox.release(); pt->refitNodeBox.release(); pt->refitSah.release(); pt->refitSahPartial.release();
-  pt->refitDirty.release();
-  pt->refitLevels.clear();
-  pt->sahAtBuild = pt->sahNow = 0.0;
-}
-
 // The SAH cost of the resident tree from the refit data (the node boxes and terms k_refit_level wrote), read back: one small copy
 int readSahCost(MiPt* pt, double& cost)
 {
-  pt::launchSahCost(pt->refitSah.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->refitNodeBox.ptr, pt->refitSahPartial.ptr, nullptr);
+  pt::launchSahCost(pt->refit.sah.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->refit.nodeBox.ptr, pt->refit.sahPartial.ptr, nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(&cost, pt->refitSahPartial.ptr + pt::REFIT_SAH_PARTIALS, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&cost, pt->refit.sahPartial.ptr + pt::REFIT_SAH_PARTIALS, sizeof(double), hipMemcpyDeviceToHost));
   return MI_PT_OK;
+}
+
+// One refit pass over the `numNodes` nodes of the resident tree: every node from its children, level by level (`levels`: the build's own while it
+// runs, pt->refit.levels afterwards), the packet walk's planes where there are any, the SAH cost into `cost`
+int refitPass(MiPt* pt, uint32_t numNodes, const std::vector<uint32_t>& levels, double& cost)
+{
+  pt::launchRefitLevels(pt->bvh8Nodes.ptr, levels, pt->refit.slotBox.ptr, pt->refit.nodeBox.ptr, pt->refit.sah.ptr, nullptr);
+  if(pt->bvh8Planes.ptr)
+    pt::launchBvh8Planes(pt->bvh8Nodes.ptr, numNodes, pt->bvh8Planes.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  return readSahCost(pt, cost);
 }
 
 // Resident mode is wanted of a build when it is enabled and the build can keep refit data (residentInForce: it then did)
@@ -732,7 +835,7 @@ bool residentWanted(const MiPt* pt)
 }
 bool residentInForce(const MiPt* pt)
 {
-  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refitLevels.empty() && pt->bvh8Nodes.ptr && pt->wide;
+  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refit.levels.empty() && pt->bvh8Nodes.ptr && pt->wide;
 }
 int buildAccelerationOver(MiPt* pt, bool resident);
 int buildAccelerationUnguarded(MiPt* pt)
@@ -742,7 +845,7 @@ int buildAccelerationUnguarded(MiPt* pt)
 // `resident`: over every render node that owns triangles, as if all were visible; the hidden ones are then hidden by one refit pass
 int buildAccelerationOver(MiPt* pt, bool resident)
 {
-  releaseRefitData(pt);
+  pt->refit        = MiPt::RefitData{};
   pt->residentTree = false;
   pt->hiddenTris   = 0;
   uint64_t  hiddenTris = 0;
@@ -823,8 +926,8 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       pt->bvhTris   = std::move(b8.tris);
       pt->bvh8Nodes = std::move(b8.nodes);
       // the refit data (the host collapse keeps none: its updates rebuild)
-      pt->refitSlotBox = std::move(b8.slotBox);
-      pt->refitNodeBox = std::move(b8.nodeBox);
+      pt->refit.slotBox = std::move(b8.slotBox);
+      pt->refit.nodeBox = std::move(b8.nodeBox);
       pt->scene.bvhRoot = 0;
       pt->scene.bvh8NumNodes = int(b8.numNodes);
       pt->staticStats.bvhNodeCount = b8.numNodes;
@@ -835,24 +938,20 @@ int buildAccelerationOver(MiPt* pt, bool resident)
         pt::launchBvh8Planes(pt->bvh8Nodes.ptr, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
         HIP_TRY(hipGetLastError());
       }
-      if(pt->refitSlotBox.ptr && pt->refitNodeBox.ptr)
+      if(pt->refit.slotBox.ptr && pt->refit.nodeBox.ptr)
       {
         // the refit data: the boxes the build filed the references under stay as they are (REFIT_HOME), the SAH cost of the tree as built.
         // The nodes are requantised once from the unions of those boxes (a BVH2 box may be looser than the union below it): the tree an
         // update refits back to the build's pose is then this one, byte for byte.
-        HIP_TRY(pt->refitBuiltBox.alloc(b8.numTris));
-        HIP_TRY(hipMemcpy(pt->refitBuiltBox.ptr, pt->refitSlotBox.ptr, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
-        HIP_TRY(pt->refitSah.alloc(b8.numNodes));
-        HIP_TRY(pt->refitSahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
-        HIP_TRY(pt->refitDirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
-        pt::launchRefitLevels(pt->bvh8Nodes.ptr, b8.levels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
-        if(pt->bvh8Planes.ptr)
-          pt::launchBvh8Planes(pt->bvh8Nodes.ptr, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
-        HIP_TRY(hipGetLastError());
-        if(int rc = readSahCost(pt, pt->sahAtBuild))
+        HIP_TRY(pt->refit.builtBox.alloc(b8.numTris));
+        HIP_TRY(hipMemcpy(pt->refit.builtBox.ptr, pt->refit.slotBox.ptr, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
+        HIP_TRY(pt->refit.sah.alloc(b8.numNodes));
+        HIP_TRY(pt->refit.sahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
+        HIP_TRY(pt->refit.dirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
+        if(int rc = refitPass(pt, b8.numNodes, b8.levels, pt->refit.sahAtBuild))
           return rc;
-        pt->sahNow      = pt->sahAtBuild;
-        pt->refitLevels = std::move(b8.levels);
+        pt->refit.sahNow      = pt->refit.sahAtBuild;
+        pt->refit.levels = std::move(b8.levels);
         pt->builtNodes  = pt->hostNodes;
         pt->primDirty.assign(pt->primTriangles.size(), 0);
         pt->primDeformed.assign(pt->primTriangles.size(), 0);
@@ -861,8 +960,8 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       }
       else
       {
-        pt->refitSlotBox.release();
-        pt->refitNodeBox.release();
+        pt->refit.slotBox.release();
+        pt->refit.nodeBox.release();
       }
     }
     else
@@ -901,14 +1000,10 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     for(size_t n = 0; n < pt->hostNodes.size(); ++n)
       if(!pt->hostVisible[n])
         dirty[n] = pt::REFIT_HIDDEN;
-    HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris.ptr, pt->refitSlotBox.ptr,
+    HIP_TRY(hipMemcpy(pt->refit.dirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refit.dirty.ptr, pt->refit.builtBox.ptr, pt->bvhTris.ptr, pt->refit.slotBox.ptr,
                         uint32_t(S.numTris), nullptr);
-    pt::launchRefitLevels(pt->bvh8Nodes.ptr, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
-    if(pt->bvh8Planes.ptr)
-      pt::launchBvh8Planes(pt->bvh8Nodes.ptr, uint32_t(S.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    if(int rc = readSahCost(pt, pt->sahNow))
+    if(int rc = refitPass(pt, uint32_t(S.bvh8NumNodes), pt->refit.levels, pt->refit.sahNow))
       return rc;
     HIP_TRY(hipDeviceSynchronize());
   }
@@ -924,8 +1019,7 @@ int buildAccelerationOver(MiPt* pt, bool resident)
 // REFIT_HIDDEN, one that stays hidden is clean whatever its matrices do, one that came back is HOME or MOVED by the same comparison.
 int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::vector<uint8_t>* visWas = nullptr)
 {
-  static const bool    buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
-  const auto           t0          = std::chrono::steady_clock::now();
+  const auto           t0       = BuildClock::now();
   const size_t         numNodes = pt->hostNodes.size(), numPrims = pt->primTriangles.size();
   std::vector<uint8_t> dirty(std::max<size_t>(numNodes, 1), pt::REFIT_CLEAN);
   std::vector<uint8_t> visKept;
@@ -962,14 +1056,10 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
   const int                  rc    = [&]() -> int {
     HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * numNodes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->refitDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refitDirty.ptr, pt->refitBuiltBox.ptr, pt->bvhTris.ptr, pt->refitSlotBox.ptr,
+    HIP_TRY(hipMemcpy(pt->refit.dirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refit.dirty.ptr, pt->refit.builtBox.ptr, pt->bvhTris.ptr, pt->refit.slotBox.ptr,
                         uint32_t(pt->scene.numTris), nullptr);
-    pt::launchRefitLevels(pt->bvh8Nodes.ptr, pt->refitLevels, pt->refitSlotBox.ptr, pt->refitNodeBox.ptr, pt->refitSah.ptr, nullptr);
-    if(pt->bvh8Planes.ptr)
-      pt::launchBvh8Planes(pt->bvh8Nodes.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->bvh8Planes.ptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    if(int e = readSahCost(pt, pt->sahNow))
+    if(int e = refitPass(pt, uint32_t(pt->scene.bvh8NumNodes), pt->refit.levels, pt->refit.sahNow))
       return e;
     HIP_TRY(hipDeviceSynchronize());
     return MI_PT_OK;
@@ -981,9 +1071,8 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
   }
   std::fill(pt->primDirty.begin(), pt->primDirty.end(), uint8_t(0));
   pt->sceneDevDirty = true;
-  if(buildTiming)
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "refit", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  if(pt->accelMode == MI_PT_ACCEL_AUTO && pt->sahNow > double(pt->accelRatio) * pt->sahAtBuild)
+  printBuildTiming("refit", t0);
+  if(pt->accelMode == MI_PT_ACCEL_AUTO && pt->refit.sahNow > double(pt->accelRatio) * pt->refit.sahAtBuild)
     return buildAcceleration(pt);
   if(visWas)
   {
@@ -1005,7 +1094,7 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
 // keeps the topology (`sameTopology`: primitives, materials and visibility unchanged), a full build otherwise.
 int updateAcceleration(MiPt* pt, bool sameTopology, const std::vector<uint8_t>& moved)
 {
-  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refitLevels.empty() && pt->bvh8Nodes.ptr && pt->wide)
+  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refit.levels.empty() && pt->bvh8Nodes.ptr && pt->wide)
     return refitAcceleration(pt, moved);
   return buildAcceleration(pt);
 }
@@ -1035,11 +1124,6 @@ AlphaKey alphaKey(const MiGltfShadeMaterial& mat, const MiGltfTextureInfo* infos
     k.texCoord = infos[k.slot].texCoord;
   }
   return k;
-}
-
-uint64_t refitBytes(const MiPt* pt)
-{
-  return pt->refitSlotBox.bytes() + pt->refitBuiltBox.bytes() + pt->refitNodeBox.bytes() + pt->refitSah.bytes() + pt->refitSahPartial.bytes() + pt->refitDirty.bytes();
 }
 
 // What a material bakes into the triangles of the instances that use it (MiPt::matInstFlags; reference: getInstanceFlag, src/gltf_scene_rtx.cpp:271-295) ...
@@ -1231,11 +1315,7 @@ int updateRenderNodesResident(MiPt* pt, const MiGltfRenderNode* renderNodes, int
   HIP_TRY(hipDeviceSynchronize());  // nothing in flight may still walk the old structure
   const bool                 hadTransmissive = pt->hasTransmissive, wasSimple = pt->simpleMaterials;
   const std::vector<uint8_t> flagsWas = matChanged ? instanceFlags(pt) : std::vector<uint8_t>();
-  pt->hostNodes.assign(renderNodes, renderNodes + numRenderNodes);
-  if(renderNodeVisible)
-    pt->hostVisible.assign(renderNodeVisible, renderNodeVisible + numRenderNodes);
-  else
-    pt->hostVisible.clear();
+  keepNodeTable(pt, renderNodes, numRenderNodes, renderNodeVisible);
   if(primChanged || (transmissiveChanged && pt->splitRefs))
   {
     if(int rc = buildAcceleration(pt))
@@ -1343,16 +1423,14 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
         return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render primitive " + std::to_string(i) + " has a vertex index beyond its vertexCount");
   }
 
-  // MI_PT_BUILD_TIMING=1: wall time of the phases of the scene build on stderr (diagnostics)
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
-  auto              tPhase      = std::chrono::steady_clock::now();
-  auto              phase       = [&](const char* what) {
-    if(!buildTiming)
+  // the phases of the scene build under the build-timing switch
+  auto tPhase = BuildClock::now();
+  auto phase  = [&](const char* what) {
+    if(!buildTiming())
       return;
     (void)hipDeviceSynchronize();
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tPhase).count());
-    tPhase = now;
+    printBuildTiming(what, tPhase);
+    tPhase = BuildClock::now();
   };
 
   std::unique_ptr<MiPt> pt(new MiPt());
@@ -1462,7 +1540,7 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
       if(t.numLevels < 1 || t.numLevels > 16 || t.width < 1 || t.height < 1 || t.width > 65535 || t.height > 65535)
         return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: texture dimensions / level count out of range");
       for(int l = 0; l < t.numLevels; ++l)
-        totalTexels += size_t(std::max(1, t.width >> l)) * size_t(std::max(1, t.height >> l));
+        totalTexels += levelExtent(t, l).texels;
     }
     if(totalTexels > 0xffffffffull)
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: texture pool exceeds 2^32 texels");
@@ -1478,7 +1556,7 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
       d.wrapS = uint8_t(t.wrapS); d.wrapT = uint8_t(t.wrapT);
       for(int l = 0; l < t.numLevels; ++l)
       {
-        size_t n         = size_t(std::max(1, t.width >> l)) * size_t(std::max(1, t.height >> l));
+        const size_t n   = levelExtent(t, l).texels;
         d.levelOffset[l] = uint32_t(off);
         memcpy(&pool[off], t.levels[l], n * 4);
         off += n;
@@ -1492,8 +1570,7 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
       HIP_TRY(pt->texQuads.alloc(pool.size()));
       for(const pt::DevTexture& d : dt)
         for(int l = 0; l < d.numLevels; ++l)
-          pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], std::max(1, int(d.width) >> l), std::max(1, int(d.height) >> l), d.wrapS,
-                                 d.wrapT, nullptr);
+          pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], levelExtent(d, l).w, levelExtent(d, l).h, d.wrapS, d.wrapT, nullptr);
       HIP_TRY(hipGetLastError());
     }
     pt->hostTextures = dt;
@@ -1562,11 +1639,7 @@ int mi_pt_update_render_nodes(MiPt* pt, const MiGltfRenderNode* renderNodes, int
       sameTopology = false;
     moved[size_t(n)] = memcmp(was.objectToWorld, now.objectToWorld, sizeof(float) * 32) != 0;
   }
-  pt->hostNodes.assign(renderNodes, renderNodes + numRenderNodes);
-  if(renderNodeVisible)
-    pt->hostVisible.assign(renderNodeVisible, renderNodeVisible + numRenderNodes);
-  else
-    pt->hostVisible.clear();
+  keepNodeTable(pt, renderNodes, numRenderNodes, renderNodeVisible);
   return updateAcceleration(pt, sameTopology, moved);
 }
 
@@ -1679,19 +1752,6 @@ int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int n
   return followSummaries(pt, hadTransmissive, wasSimple);
 }
 
-static void releaseDeformation(MiPt* pt)
-{
-  pt->deformPool.release();
-  pt->deformTasks.release();
-  pt->deformBlockTask.release();
-  pt->deformJoints.release();
-  pt->deformWeights.release();
-  pt->deformJointCount = pt->deformWeightCount = 0;
-  pt->deformBlocks = 0;
-  pt->deformSet    = false;
-  pt->deformPrimIDs.clear();
-}
-
 int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
 {
   FLUSH_PENDING(pt);
@@ -1701,7 +1761,7 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
   HIP_TRY(hipDeviceSynchronize());
   if(!desc)
   {
-    releaseDeformation(pt);
+    pt->deform = MiPt::Deformation{};
     return allocVertexMotion(pt);
   }
   const int numPrims = int(pt->primVertices.size());
@@ -1719,7 +1779,7 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " out of range");
     if(seen[size_t(d.renderPrimID)]++)
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " listed twice");
-    if(pt->vuSet && pt->vuDeclared[size_t(d.renderPrimID)])
+    if(pt->vu.set && pt->vu.declared[size_t(d.renderPrimID)])
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(d.renderPrimID) + " is driven by the caller (mi_pt_set_vertex_updates)");
     const pt::DevPrim& rp = pt->hostPrims[size_t(d.renderPrimID)];
     if(d.vertexCount != pt->primVertices[size_t(d.renderPrimID)])
@@ -1748,24 +1808,24 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
   }
   if(blocks > 0x7fffffffull)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_deformation: too many vertices");
-  releaseDeformation(pt);
+  pt->deform = MiPt::Deformation{};
   if(desc->numPrims == 0)
     return allocVertexMotion(pt);
   // ---- static upload: base poses (in the layout of DevPrim::verts, from the resident record: uv0 and the stream values that are not
   // deformed keep theirs), influences, deltas
-  HIP_TRY(pt->deformPool.alloc(std::max<size_t>(poolBytes, 16)));
+  HIP_TRY(pt->deform.pool.alloc(std::max<size_t>(poolBytes, 16)));
   std::vector<uint8_t>        staging(std::max<size_t>(poolBytes, 16), 0);
   std::vector<pt::DeformTask> tasks(size_t(desc->numPrims));
   std::vector<uint32_t>       blockTask;
   size_t                      off = 0;
   auto                        put = [&](const void* src, size_t bytes) -> const uint8_t* {
     memcpy(staging.data() + off, src, bytes);
-    const uint8_t* d = pt->deformPool.ptr + off;
+    const uint8_t* d = pt->deform.pool.ptr + off;
     off += align16(bytes);
     return d;
   };
-  HIP_TRY(pt->deformJoints.alloc(size_t(std::max(desc->numJointMatrices, 1)) * 6));
-  HIP_TRY(pt->deformWeights.alloc(size_t(std::max(desc->numMorphWeights, 1))));
+  HIP_TRY(pt->deform.joints.alloc(size_t(std::max(desc->numJointMatrices, 1)) * 6));
+  HIP_TRY(pt->deform.weights.alloc(size_t(std::max(desc->numMorphWeights, 1))));
   for(int k = 0; k < desc->numPrims; ++k)
   {
     const MiPtDeformPrimitive& d  = desc->prims[k];
@@ -1789,12 +1849,12 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
       t.weights = reinterpret_cast<const float4*>(put(d.weights, nv * 16));
       t.flags |= pt::DF_SKIN;
       t.numJoints  = d.numJoints;
-      t.jointTable = pt->deformJoints.ptr + size_t(d.jointMatrixOffset) * 6;
+      t.jointTable = pt->deform.joints.ptr + size_t(d.jointMatrixOffset) * 6;
     }
     if(d.numTargets)
     {
       t.numTargets   = d.numTargets;
-      t.morphWeights = pt->deformWeights.ptr + d.morphWeightOffset;
+      t.morphWeights = pt->deform.weights.ptr + d.morphWeightOffset;
       t.posDeltas    = reinterpret_cast<const float*>(put(d.positionDeltas, nv * 12 * d.numTargets));
       if(d.normalDeltas)
       {
@@ -1820,15 +1880,15 @@ int mi_pt_set_deformation(MiPt* pt, const MiPtDeformDesc* desc)
     for(size_t b = 0; b < (nv + pt::DEFORM_BLOCK - 1) / pt::DEFORM_BLOCK; ++b)
       blockTask.push_back(uint32_t(k));
   }
-  HIP_TRY(hipMemcpy(pt->deformPool.ptr, staging.data(), staging.size(), hipMemcpyHostToDevice));
-  HIP_TRY(pt->deformTasks.upload(tasks.data(), tasks.size()));
-  HIP_TRY(pt->deformBlockTask.upload(blockTask.data(), blockTask.size()));
-  pt->deformJointCount  = desc->numJointMatrices;
-  pt->deformWeightCount = desc->numMorphWeights;
-  pt->deformBlocks      = uint32_t(blockTask.size());
-  pt->deformSet         = true;
+  HIP_TRY(hipMemcpy(pt->deform.pool.ptr, staging.data(), staging.size(), hipMemcpyHostToDevice));
+  HIP_TRY(pt->deform.tasks.upload(tasks.data(), tasks.size()));
+  HIP_TRY(pt->deform.blockTask.upload(blockTask.data(), blockTask.size()));
+  pt->deform.jointCount  = desc->numJointMatrices;
+  pt->deform.weightCount = desc->numMorphWeights;
+  pt->deform.blocks      = uint32_t(blockTask.size());
+  pt->deform.set         = true;
   for(int k = 0; k < desc->numPrims; ++k)
-    pt->deformPrimIDs.push_back(desc->prims[k].renderPrimID);
+    pt->deform.primIDs.push_back(desc->prims[k].renderPrimID);
   return allocVertexMotion(pt);  // (new tables: the previous-pose positions of vertex motion start from the resident ones again)
 }
 
@@ -1837,19 +1897,19 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
   FLUSH_PENDING(pt);
   if(!pt)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: null instance");
-  if(!pt->deformSet)
+  if(!pt->deform.set)
     return fail(MI_PT_ERR_STATE, "mi_pt_update_deformation: no deformation set (mi_pt_set_deformation)");
-  if((pt->deformJointCount > 0 && !jointMatrices) || (pt->deformWeightCount > 0 && !morphWeights))
+  if((pt->deform.jointCount > 0 && !jointMatrices) || (pt->deform.weightCount > 0 && !morphWeights))
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: null table");
-  for(size_t i = 0, n = size_t(pt->deformJointCount) * 16; i < n; ++i)
+  for(size_t i = 0, n = size_t(pt->deform.jointCount) * 16; i < n; ++i)
     if(!std::isfinite(jointMatrices[i]))
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: non-finite joint matrix");
-  for(int i = 0; i < pt->deformWeightCount; ++i)
+  for(int i = 0; i < pt->deform.weightCount; ++i)
     if(!std::isfinite(morphWeights[i]))
       return fail(MI_PT_ERR_ARGUMENT, "mi_pt_update_deformation: non-finite morph weight");
   // joint table: rows 0-2 of J (the last row of J [p, 1] is never read) and of N = transpose(inverse(mat3(J))), the cofactor matrix / det
-  std::vector<float4> table(size_t(std::max(pt->deformJointCount, 1)) * 6, make_float4(0, 0, 0, 0));
-  for(int j = 0; j < pt->deformJointCount; ++j)
+  std::vector<float4> table(size_t(std::max(pt->deform.jointCount, 1)) * 6, make_float4(0, 0, 0, 0));
+  for(int j = 0; j < pt->deform.jointCount; ++j)
   {
     const float* M = jointMatrices + size_t(j) * 16;  // column-major: M[c * 4 + r]
     float4*      o = &table[size_t(j) * 6];
@@ -1862,39 +1922,23 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
     o[4] = make_float4(-(b * k - c * i) * id, (a * k - c * h) * id, -(a * i - b * h) * id, 0.0f);
     o[5] = make_float4((b * g - c * f) * id, -(a * g - c * e) * id, (a * f - b * e) * id, 0.0f);
   }
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old pose
-  const auto t0 = std::chrono::steady_clock::now();
-  HIP_TRY(hipMemcpy(pt->deformJoints.ptr, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
-  if(pt->deformWeightCount > 0)
-    HIP_TRY(hipMemcpy(pt->deformWeights.ptr, morphWeights, sizeof(float) * size_t(pt->deformWeightCount), hipMemcpyHostToDevice));
-  pt::launchDeform(pt->deformTasks.ptr, pt->deformBlockTask.ptr, pt->deformBlocks, nullptr);
+  const auto t0 = BuildClock::now();
+  HIP_TRY(hipMemcpy(pt->deform.joints.ptr, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
+  if(pt->deform.weightCount > 0)
+    HIP_TRY(hipMemcpy(pt->deform.weights.ptr, morphWeights, sizeof(float) * size_t(pt->deform.weightCount), hipMemcpyHostToDevice));
+  pt::launchDeform(pt->deform.tasks.ptr, pt->deform.blockTask.ptr, pt->deform.blocks, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  if(buildTiming)
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "deform", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  pt->vmPoseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
-  for(int id : pt->deformPrimIDs)  // (what the next acceleration update refits; sized by a build that kept refit data)
+  printBuildTiming("deform", t0);
+  pt->vm.poseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
+  for(int id : pt->deform.primIDs)  // (what the next acceleration update refits; sized by a build that kept refit data)
     if(size_t(id) < pt->primDirty.size())
       pt->primDirty[size_t(id)] = pt->primDeformed[size_t(id)] = 1;
   if(flags & MI_PT_DEFORM_DEFER_BUILD)
     return MI_PT_OK;
   return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
-}
-
-static void releaseVertexUpdates(MiPt* pt)
-{
-  pt->vuTable.release();
-  pt->vuTasks.release();
-  pt->vuNormalTasks.release();
-  pt->vuBlockTask.release();
-  pt->vuBlockCap = 0;
-  pt->vuSet      = false;
-  pt->vuPrimIDs.clear();
-  pt->vuDeclared.clear();
-  pt->vuCornerEnd.clear();
-  pt->vuCorners.clear();
 }
 
 int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, int flags)
@@ -1908,7 +1952,7 @@ int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, 
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_vertex_updates: negative count or unknown flag bits");
   if(count == 0 || !renderPrimIDs)
   {
-    releaseVertexUpdates(pt);
+    pt->vu = MiPt::VertexUpdates{};
     return allocVertexMotion(pt);
   }
   // ---- validation: the kernels index everything below without further checks
@@ -1923,7 +1967,7 @@ int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, 
       return fail(MI_PT_ERR_ARGUMENT, who + " out of range");
     if(declared[size_t(id)]++)
       return fail(MI_PT_ERR_ARGUMENT, who + " listed twice");
-    if(std::find(pt->deformPrimIDs.begin(), pt->deformPrimIDs.end(), id) != pt->deformPrimIDs.end())
+    if(std::find(pt->deform.primIDs.begin(), pt->deform.primIDs.end(), id) != pt->deform.primIDs.end())
       return fail(MI_PT_ERR_ARGUMENT, who + " is deformed by the deformation tables (mi_pt_set_deformation)");
     const pt::DevPrim& rp = pt->hostPrims[size_t(id)];
     if(!rp.positions || pt->primVertices[size_t(id)] == 0)
@@ -1962,25 +2006,19 @@ int mi_pt_set_vertex_updates(MiPt* pt, const int32_t* renderPrimIDs, int count, 
     for(size_t c = 0; c < nc; ++c)
       out[cursor[idx[c]]++] = uint32_t(c);
   }
-  // ---- commit
-  DevBuf<uint32_t>              newTable, newBlockTask;
-  DevBuf<pt::VertexUpdateTask>  newTasks;
-  DevBuf<pt::NormalRebuildTask> newNormalTasks;
-  HIP_TRY(newTable.upload(table.data(), table.size()));
-  HIP_TRY(newTasks.alloc(size_t(count)));
-  HIP_TRY(newNormalTasks.alloc(size_t(count)));
-  HIP_TRY(newBlockTask.alloc(size_t(blocks) * 2 + 1));
-  releaseVertexUpdates(pt);
-  pt->vuTable       = std::move(newTable);
-  pt->vuTasks       = std::move(newTasks);
-  pt->vuNormalTasks = std::move(newNormalTasks);
-  pt->vuBlockTask   = std::move(newBlockTask);
-  pt->vuBlockCap    = size_t(blocks);
-  pt->vuSet         = true;
-  pt->vuPrimIDs.assign(renderPrimIDs, renderPrimIDs + count);
-  pt->vuDeclared  = std::move(declared);
-  pt->vuCornerEnd = std::move(cornerEnd);
-  pt->vuCorners   = std::move(corners);
+  // ---- commit: the new declaration replaces the old one only once it holds all its buffers
+  MiPt::VertexUpdates fresh;
+  HIP_TRY(fresh.table.upload(table.data(), table.size()));
+  HIP_TRY(fresh.tasks.alloc(size_t(count)));
+  HIP_TRY(fresh.normalTasks.alloc(size_t(count)));
+  HIP_TRY(fresh.blockTask.alloc(size_t(blocks) * 2 + 1));
+  fresh.blockCap = size_t(blocks);
+  fresh.set      = true;
+  fresh.primIDs.assign(renderPrimIDs, renderPrimIDs + count);
+  fresh.declared  = std::move(declared);
+  fresh.cornerEnd = std::move(cornerEnd);
+  fresh.corners   = std::move(corners);
+  pt->vu          = std::move(fresh);
   return allocVertexMotion(pt);  // (the declared primitives' previous-pose positions start from the resident ones)
 }
 
@@ -1990,18 +2028,18 @@ static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpda
   const std::string fn = name;
   if(!pt)
     return fail(MI_PT_ERR_ARGUMENT, fn + ": null instance");
-  if(!pt->vuSet)
+  if(!pt->vu.set)
     return fail(MI_PT_ERR_STATE, fn + ": no primitives declared (mi_pt_set_vertex_updates)");
   if(numUpdates < 0 || (numUpdates > 0 && !updates) || (flags & ~MI_PT_DEFORM_DEFER_BUILD))
     return fail(MI_PT_ERR_ARGUMENT, fn + ": negative count, null table or unknown flag bits");
   // ---- validation: nothing changes when any primitive of the call is refused
-  std::vector<uint8_t> seen(pt->vuDeclared.size(), 0);
+  std::vector<uint8_t> seen(pt->vu.declared.size(), 0);
   size_t               stagingBytes = 0;
   for(int k = 0; k < numUpdates; ++k)
   {
     const MiPtVertexUpdate& u   = updates[k];
     const std::string       who = fn + ": update " + std::to_string(k) + ": ";
-    if(u.renderPrimID < 0 || size_t(u.renderPrimID) >= pt->vuDeclared.size() || !pt->vuDeclared[size_t(u.renderPrimID)])
+    if(u.renderPrimID < 0 || size_t(u.renderPrimID) >= pt->vu.declared.size() || !pt->vu.declared[size_t(u.renderPrimID)])
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(u.renderPrimID) + " is not declared");
     if(seen[size_t(u.renderPrimID)]++)
       return fail(MI_PT_ERR_ARGUMENT, who + "render primitive " + std::to_string(u.renderPrimID) + " listed twice");
@@ -2031,10 +2069,9 @@ static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpda
       return fail(MI_PT_ERR_ARGUMENT, who + "a non-finite component");
     stagingBytes += align16(nv * 12) + (u.normals ? align16(nv * 12) : 0) + (u.tangents ? align16(nv * 16) : 0);
   }
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old vertices; the caller's streams have produced the device arrays
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = BuildClock::now();
   if(stagingBytes > pt->vuStaging.count)
     HIP_TRY(pt->vuStaging.alloc(stagingBytes));
   // ---- task tables: every primitive's vertex range padded to whole blocks, one launch (and one for the normals that are rebuilt)
@@ -2075,13 +2112,13 @@ static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpda
     blockTask.insert(blockTask.end(), nb, uint32_t(tasks.size()));
     tasks.push_back(t);
     vertices += nv;
-    if(!u.normals && pt->vuCornerEnd[id] != SIZE_MAX)
+    if(!u.normals && pt->vu.cornerEnd[id] != SIZE_MAX)
     {
       pt::NormalRebuildTask n{};
       n.positions   = rp.positions;
       n.indices     = rp.indices;
-      n.cornerEnd   = pt->vuTable.ptr + pt->vuCornerEnd[id];
-      n.corners     = pt->vuTable.ptr + pt->vuCorners[id];
+      n.cornerEnd   = pt->vu.table.ptr + pt->vu.cornerEnd[id];
+      n.corners     = pt->vu.table.ptr + pt->vu.corners[id];
       n.outNormals  = const_cast<float*>(rp.normals);
       n.outVerts    = const_cast<float4*>(rp.verts);
       n.vertexCount = uint32_t(nv);
@@ -2090,35 +2127,34 @@ static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpda
       normalTasks.push_back(n);
     }
   }
-  uint32_t* rejectedDev = pt->vuBlockTask.ptr + 2 * pt->vuBlockCap;
+  uint32_t* rejectedDev = pt->vu.blockTask.ptr + 2 * pt->vu.blockCap;
   uint32_t  rejected    = 0;
   if(!tasks.empty())
   {
     if(stagingBytes)
       HIP_TRY(hipMemcpy(pt->vuStaging.ptr, staging.data(), stagingBytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->vuTasks.ptr, tasks.data(), tasks.size() * sizeof(pt::VertexUpdateTask), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->vuBlockTask.ptr, blockTask.data(), blockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->vu.tasks.ptr, tasks.data(), tasks.size() * sizeof(pt::VertexUpdateTask), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->vu.blockTask.ptr, blockTask.data(), blockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(rejectedDev, 0, sizeof(uint32_t)));
-    pt::launchVertexIngest(pt->vuTasks.ptr, pt->vuBlockTask.ptr, uint32_t(blockTask.size()), rejectedDev, nullptr);
+    pt::launchVertexIngest(pt->vu.tasks.ptr, pt->vu.blockTask.ptr, uint32_t(blockTask.size()), rejectedDev, nullptr);
     HIP_TRY(hipGetLastError());
     if(!normalTasks.empty())  // (after the ingest, on the same stream: it reads resident positions, which are always finite)
     {
-      HIP_TRY(hipMemcpy(pt->vuNormalTasks.ptr, normalTasks.data(), normalTasks.size() * sizeof(pt::NormalRebuildTask), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(pt->vuBlockTask.ptr + pt->vuBlockCap, normalBlockTask.data(), normalBlockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      pt::launchNormalRebuild(pt->vuNormalTasks.ptr, pt->vuBlockTask.ptr + pt->vuBlockCap, uint32_t(normalBlockTask.size()), nullptr);
+      HIP_TRY(hipMemcpy(pt->vu.normalTasks.ptr, normalTasks.data(), normalTasks.size() * sizeof(pt::NormalRebuildTask), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(pt->vu.blockTask.ptr + pt->vu.blockCap, normalBlockTask.data(), normalBlockTask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      pt::launchNormalRebuild(pt->vu.normalTasks.ptr, pt->vu.blockTask.ptr + pt->vu.blockCap, uint32_t(normalBlockTask.size()), nullptr);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&rejected, rejectedDev, sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
-  if(buildTiming)
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "vertex update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  ++pt->vuCalls;
-  pt->vuWritten += vertices - rejected;
-  pt->vuRejected = rejected;
+  printBuildTiming("vertex update", t0);
+  ++pt->vuInfo.calls;
+  pt->vuInfo.verticesWritten += vertices - rejected;
+  pt->vuInfo.verticesRejected = rejected;
   if(tasks.empty())
     return MI_PT_OK;
-  pt->vmPoseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
+  pt->vm.poseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
   for(int k = 0; k < numUpdates; ++k)  // (what the next acceleration update refits; sized by a build that kept refit data)
     if(size_t(updates[k].renderPrimID) < pt->primDirty.size())
       pt->primDirty[size_t(updates[k].renderPrimID)] = pt->primDeformed[size_t(updates[k].renderPrimID)] = 1;
@@ -2143,10 +2179,8 @@ int mi_pt_get_vertex_update_info(MiPt* pt, MiPtVertexUpdateInfo* out)
 {
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_vertex_update_info: null argument");
-  out->calls            = pt->vuCalls;
-  out->verticesWritten  = pt->vuWritten;
-  out->verticesRejected = pt->vuRejected;
-  out->tableBytes       = pt->vuTable.bytes();
+  *out            = pt->vuInfo;
+  out->tableBytes = pt->vu.table.bytes();
   return MI_PT_OK;
 }
 
@@ -2162,7 +2196,6 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
   const int            numTextures = int(pt->hostTextures.size());
   std::vector<uint8_t> seen(size_t(numTextures), 0);
   size_t               stagingBytes = 0;
-  auto levelTexels = [](const pt::DevTexture& d, int l) { return size_t(std::max(1, int(d.width) >> l)) * size_t(std::max(1, int(d.height) >> l)); };
   for(int k = 0; k < numUpdates; ++k)
   {
     const MiPtTextureUpdate& u   = updates[k];
@@ -2193,7 +2226,7 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
       if(device && (reinterpret_cast<uintptr_t>(u.levels[l]) & (texelBytes - 1)))
         return fail(MI_PT_ERR_ARGUMENT, who + "a device pointer that is not " + std::to_string(texelBytes) + "-byte aligned");
       if(!device)
-        stagingBytes += align16(levelTexels(d, l) * texelBytes);
+        stagingBytes += align16(levelExtent(d, l).texels * texelBytes);
     }
   }
   // the OPAQUE class of the load-time alpha cut was found under the old texels: its triangles skip the alpha test for good
@@ -2210,14 +2243,13 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
                                             + std::to_string(m) + ", render node " + std::to_string(n) + ")");
     }
   }
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still sample the old texels; the caller's streams have produced the device images
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = BuildClock::now();
   if(numUpdates == 0)
   {
-    ++pt->tuCalls;
-    pt->tuLaunches = 0;
+    ++pt->tuInfo.calls;
+    pt->tuInfo.launches = 0;
     return MI_PT_OK;
   }
   if(!pt->tuTables.ptr)
@@ -2245,7 +2277,7 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
     const bool               f32 = u.format == MI_PT_TEXELS_RGBA32F;
     for(int l = 0; l < u.numLevels; ++l)
     {
-      const size_t          n = levelTexels(d, l), bytes = n * (f32 ? 16 : 4);
+      const size_t          n = levelExtent(d, l).texels, bytes = n * (f32 ? 16 : 4);
       pt::TextureIngestTask t{};
       if(device)
         t.src = u.levels[l];
@@ -2266,18 +2298,19 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
     if(u.flags & MI_PT_TEXTURE_GENERATE_MIPS)
       for(int l = 1; l < int(d.numLevels); ++l)
       {
+        const LevelExtent  from = levelExtent(d, l - 1), to = levelExtent(d, l);
         pt::TextureMipTask t{};
         t.src        = pool + d.levelOffset[l - 1];
         t.dst        = pool + d.levelOffset[l];
-        t.sw         = uint32_t(std::max(1, int(d.width) >> (l - 1)));
-        t.sh         = uint32_t(std::max(1, int(d.height) >> (l - 1)));
-        t.dw         = uint32_t(std::max(1, int(d.width) >> l));
-        t.dh         = uint32_t(std::max(1, int(d.height) >> l));
+        t.sw         = uint32_t(from.w);
+        t.sh         = uint32_t(from.h);
+        t.dw         = uint32_t(to.w);
+        t.dh         = uint32_t(to.h);
         t.firstBlock = uint32_t(mipBlocks[l].size());
         t.flags      = d.srgb ? pt::TU_SRGB : 0u;
-        mipBlocks[l].insert(mipBlocks[l].end(), blocksOf(size_t(t.dw) * t.dh), uint32_t(mips[l].size()));
+        mipBlocks[l].insert(mipBlocks[l].end(), blocksOf(to.texels), uint32_t(mips[l].size()));
         mips[l].push_back(t);
-        texels += size_t(t.dw) * t.dh;
+        texels += to.texels;
         ++generated;
       }
   }
@@ -2315,18 +2348,17 @@ static int updateTextures(MiPt* pt, const MiPtTextureUpdate* updates, int numUpd
       const pt::DevTexture& d = pt->hostTextures[size_t(updates[k].texture)];
       for(int l = 0; l < int(d.numLevels); ++l)
       {
-        pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], std::max(1, int(d.width) >> l), std::max(1, int(d.height) >> l), d.wrapS, d.wrapT, nullptr);
+        pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], levelExtent(d, l).w, levelExtent(d, l).h, d.wrapS, d.wrapT, nullptr);
         ++launches;
       }
     }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());  // (the task tables are released on return)
-  if(buildTiming)
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "texture update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  ++pt->tuCalls;
-  pt->tuTexels += texels;
-  pt->tuLevels += generated;
-  pt->tuLaunches = launches;
+  printBuildTiming("texture update", t0);
+  ++pt->tuInfo.calls;
+  pt->tuInfo.texelsWritten += texels;
+  pt->tuInfo.levelsGenerated += generated;
+  pt->tuInfo.launches = launches;
   return MI_PT_OK;
 }
 
@@ -2350,8 +2382,7 @@ int mi_pt_read_texture(MiPt* pt, int texture, int level, uint8_t* hostRGBA8)
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
   const pt::DevTexture& d = pt->hostTextures[size_t(texture)];
-  const size_t          n = size_t(std::max(1, int(d.width) >> level)) * size_t(std::max(1, int(d.height) >> level));
-  HIP_TRY(hipMemcpy(hostRGBA8, pt->texels.ptr + d.levelOffset[level], n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hostRGBA8, pt->texels.ptr + d.levelOffset[level], levelExtent(d, level).texels * 4, hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
 
@@ -2359,10 +2390,7 @@ int mi_pt_get_texture_update_info(MiPt* pt, MiPtTextureUpdateInfo* out)
 {
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_texture_update_info: null argument");
-  out->calls           = pt->tuCalls;
-  out->texelsWritten   = pt->tuTexels;
-  out->levelsGenerated = pt->tuLevels;
-  out->launches        = pt->tuLaunches;
+  *out = pt->tuInfo;
   return MI_PT_OK;
 }
 
@@ -2398,10 +2426,9 @@ static int updateEnvironment(MiPt* pt, const MiPtEnvironmentUpdate* u, bool devi
           return fail(MI_PT_ERR_ARGUMENT, fn + ": texel " + std::to_string(i) + " has a component that is not finite or is negative");
       }
   }
-  static const bool buildTiming = getenv("MI_PT_BUILD_TIMING") != nullptr;
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still read the old map; the caller's streams have produced the device image
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = BuildClock::now();
   // ---- memory: the scratch grows, the map and the table are replaced only when the texel count differs
   const pt::EnvScratchLayout L = pt::euScratchLayout(n, uint32_t(u->height));
   if(L.bytes > pt->euScratch.count)
@@ -2415,11 +2442,7 @@ static int updateEnvironment(MiPt* pt, const MiPtEnvironmentUpdate* u, bool devi
     pt->envPixels = std::move(pixels);
     pt->envAccel  = std::move(accel);
   }
-  pt->scene.envPixels = pt->envPixels.ptr;
-  pt->scene.envAccel  = pt->envAccel.ptr;
-  pt->scene.envWidth  = u->width;
-  pt->scene.envHeight = u->height;
-  pt->sceneDevDirty   = true;
+  publishEnvironment(pt, u->width, u->height);
   uint8_t* const  base = pt->euScratch.ptr;
   pt::EnvArgs     A{};
   A.n          = n;
@@ -2453,34 +2476,32 @@ static int updateEnvironment(MiPt* pt, const MiPtEnvironmentUpdate* u, bool devi
   HIP_TRY(hipMemset(base + L.header, 0, sizeof(pt::EnvHeader)));
   struct Timing
   {
-    std::chrono::steady_clock::time_point last;
-    hipError_t                            error = hipSuccess;
-  } timing{std::chrono::steady_clock::now()};
+    BuildClock::time_point last;
+    hipError_t             error = hipSuccess;
+  } timing{BuildClock::now()};
   auto passDone = [](const char* pass, void* user) {
     Timing&          T = *static_cast<Timing*>(user);
     const hipError_t e = hipDeviceSynchronize();
     T.error            = T.error != hipSuccess ? T.error : e;
-    const auto now     = std::chrono::steady_clock::now();
-    fprintf(stderr, "[mi_pt build] %-28s %8.3f ms\n", pass, std::chrono::duration<double, std::milli>(now - T.last).count());
-    T.last = now;
+    printBuildTiming(pass, T.last, 3);
+    T.last = BuildClock::now();
   };
-  pt::launchEnvUpdate(A, nullptr, buildTiming ? +passDone : nullptr, &timing);
+  pt::launchEnvUpdate(A, nullptr, buildTiming() ? +passDone : nullptr, &timing);
   HIP_TRY(hipGetLastError());
   HIP_TRY(timing.error);
   pt::EnvHeader header{};
   HIP_TRY(hipMemcpy(&header, base + L.header, sizeof(header), hipMemcpyDeviceToHost));
   HIP_TRY(hipDeviceSynchronize());
-  if(buildTiming)
-    fprintf(stderr, "[mi_pt build] %-28s %8.2f ms\n", "environment update", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  printBuildTiming("environment update", t0);
   const bool lit  = header.total > 0.0;
   pt->envIntegral = float(header.total);
-  ++pt->euCalls;
-  pt->euTexels += n;
-  pt->euSanitised = header.sanitised;
-  pt->euLaunches  = uint64_t(pt::ENV_UPDATE_LAUNCHES);
-  pt->euLight     = lit ? header.numLight : 0u;
-  pt->euHeavy     = lit ? n - header.numLight : 0u;
-  pt->euIntegral  = pt->envIntegral;
+  ++pt->euInfo.calls;
+  pt->euInfo.texelsWritten += n;
+  pt->euInfo.texelsSanitised = header.sanitised;
+  pt->euInfo.launches  = uint64_t(pt::ENV_UPDATE_LAUNCHES);
+  pt->euInfo.lightTexels     = lit ? header.numLight : 0u;
+  pt->euInfo.heavyTexels     = lit ? n - header.numLight : 0u;
+  pt->euInfo.integral  = pt->envIntegral;
   return MI_PT_OK;
 }
 
@@ -2523,15 +2544,8 @@ int mi_pt_get_environment_update_info(MiPt* pt, MiPtEnvironmentUpdateInfo* out)
 {
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_environment_update_info: null argument");
-  *out                 = MiPtEnvironmentUpdateInfo{};
-  out->calls           = pt->euCalls;
-  out->texelsWritten   = pt->euTexels;
-  out->texelsSanitised = pt->euSanitised;
-  out->launches        = pt->euLaunches;
-  out->lightTexels     = pt->euLight;
-  out->heavyTexels     = pt->euHeavy;
-  out->scratchBytes    = pt->euScratch.bytes();
-  out->integral        = pt->euIntegral;
+  *out              = pt->euInfo;
+  out->scratchBytes = pt->euScratch.bytes();
   return MI_PT_OK;
 }
 
@@ -2550,10 +2564,10 @@ int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
   pt->accelRatio = rebuildCostRatio;
   if(mode == MI_PT_ACCEL_REBUILD)
   {
-    releaseRefitData(pt);
+    pt->refit = MiPt::RefitData{};
     return MI_PT_OK;
   }
-  if(!pt->refitLevels.empty() || !pt->refitCapable)
+  if(!pt->refit.levels.empty() || !pt->refitCapable)
     return MI_PT_OK;  // (refit data held already, or the structure can never keep any -- BVH2 walk, host collapse, empty or one-reference scene: no build)
   pt->switchBuild = true;
   const int rc    = buildAcceleration(pt);
@@ -2571,10 +2585,10 @@ int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* out)
   out->rebuildCostRatio = pt->accelRatio;
   out->builds           = uint64_t(std::max(pt->accelBuilds, 0));
   out->refits           = pt->accelRefits;
-  out->sahCostAtBuild   = pt->sahAtBuild;
-  out->sahCost          = pt->sahNow;
+  out->sahCostAtBuild   = pt->refit.sahAtBuild;
+  out->sahCost          = pt->refit.sahNow;
   out->trianglesMoved   = pt->trianglesMoved;
-  out->refitBytes       = refitBytes(pt);
+  out->refitBytes       = pt->refit.bytes();
   return MI_PT_OK;
 }
 
@@ -2653,21 +2667,14 @@ int mi_pt_set_environment(MiPt* pt, const MiPtEnvironment* env)
   {
     pt->envPixels.release();
     pt->envAccel.release();
-    pt->scene.envPixels = nullptr;
-    pt->scene.envAccel  = nullptr;
-    pt->scene.envWidth = pt->scene.envHeight = 0;
-    pt->sceneDevDirty  = true;
+    publishEnvironment(pt, 0, 0);
     return MI_PT_OK;
   }
   const size_t n = size_t(env->width) * size_t(env->height);
   HIP_TRY(pt->envPixels.upload(reinterpret_cast<const float4*>(env->rgba), n));
   HIP_TRY(pt->envAccel.upload(env->accel, n));
-  pt->scene.envPixels = pt->envPixels.ptr;
-  pt->scene.envAccel  = pt->envAccel.ptr;
-  pt->scene.envWidth  = env->width;
-  pt->scene.envHeight = env->height;
-  pt->envIntegral     = env->integral;
-  pt->sceneDevDirty   = true;
+  publishEnvironment(pt, env->width, env->height);
+  pt->envIntegral = env->integral;
   return MI_PT_OK;
 }
 
@@ -2846,9 +2853,7 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   c.fc.width     = pt->width;
   c.fc.height    = pt->height;
   c.fc.tileSize  = pt->tileSize;
-  c.fc.tileShift = 0;
-  while((1 << c.fc.tileShift) < pt->tileSize)
-    ++c.fc.tileShift;
+  c.fc.tileShift = tileShiftOf(pt);
   c.fc.numSlots  = pt->numSlots;
   c.fc.numFrames = numFrames;
   pt::divideMagic(uint32_t(std::max(numFrames, 2)), c.fc.framesMagic, c.fc.framesShift);
@@ -3107,16 +3112,16 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     pt->haveFirstHit = true;
     if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
     {
-      pt::launchMotionVectors(pt->firstHit.ptr, pt->firstHitTri.ptr, pt->vmPrims.ptr, int(pt->vmPrims.count), pt->ownedTiles.ptr, uint32_t(pt->numSlots),
-                              c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr, pt->prevObjectToWorld.ptr, int(pt->nodes.count),
-                              pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->motion.ptr, stream);
-      pt->haveMotion = true;
+      pt::launchMotionVectors(pt->firstHit.ptr, pt->firstHitTri.ptr, pt->vm.prims.ptr, int(pt->vm.prims.count), pt->ownedTiles.ptr, uint32_t(pt->numSlots),
+                              c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr, pt->temporalData.prevObjectToWorld.ptr, int(pt->nodes.count),
+                              pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->temporalData.motion.ptr, stream);
+      pt->temporalData.haveMotion = true;
       if(pt->firstHitTri.ptr)  // vertex motion: the rendered pose's positions become the next pose's previous ones, when an update changed them
       {
         pt->haveFirstHitTri = true;
-        if(pt->vmPoseDirty)
-          pt::launchSnapshotPositions(pt->vmPrims.ptr, pt->vmDeformIDs.ptr, uint32_t(pt->vmDeformIDs.count), pt->vmMaxVertices, stream);
-        pt->vmPoseDirty = false;
+        if(pt->vm.poseDirty)
+          pt::launchSnapshotPositions(pt->vm.prims.ptr, pt->vm.deformIDs.ptr, uint32_t(pt->vm.deformIDs.count), pt->vm.maxVertices, stream);
+        pt->vm.poseDirty = false;
       }
     }
   }
@@ -3149,10 +3154,7 @@ int mi_pt_read_accum(MiPt* pt, float* host)
   FLUSH_PENDING(pt);
   if(!pt || !host || pt->width <= 0)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_accum: bad arguments");
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, pt->accum, size_t(pt->width) * size_t(pt->height) * sizeof(float4), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return readImage(pt, pt->accum, sizeof(float4), host);
 }
 int mi_pt_write_accum(MiPt* pt, const float* host)
 {
@@ -3171,24 +3173,16 @@ int mi_pt_read_guides(MiPt* pt, float* albedo, float* normal)
   FLUSH_PENDING(pt);
   if(!pt || pt->width <= 0)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_guides: bad arguments");
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t bytes = size_t(pt->width) * size_t(pt->height) * sizeof(float4);
-  if(albedo)
-    HIP_TRY(hipMemcpy(albedo, pt->albedoImg(), bytes, hipMemcpyDeviceToHost));
-  if(normal)
-    HIP_TRY(hipMemcpy(normal, pt->normalImg(), bytes, hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  if(int rc = readImage(pt, pt->albedoImg(), sizeof(float4), albedo))
+    return rc;
+  return readImage(pt, pt->normalImg(), sizeof(float4), normal, false);
 }
 int mi_pt_read_selection(MiPt* pt, uint32_t* host)
 {
   FLUSH_PENDING(pt);
   if(!pt || !host || pt->width <= 0)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_selection: bad arguments");
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, pt->selection.ptr, size_t(pt->width) * size_t(pt->height) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return readImage(pt, pt->selection.ptr, sizeof(uint32_t), host);
 }
 // ---- ray queries and picking (query.hip) --------------------------------------------------------------------------------------------------------
 // Six entry points over three internal functions -- rays in host memory, rays in device memory, pixel positions.  A plain entry point is its _ex
@@ -3419,8 +3413,7 @@ int exportCameraRays(MiPt* pt, const char* who, const MiPathtraceParams* params,
   c.fc.width     = pt->width;
   c.fc.height    = pt->height;
   c.fc.tileSize  = pt->tileSize;
-  while((1 << c.fc.tileShift) < pt->tileSize)
-    ++c.fc.tileShift;
+  c.fc.tileShift = tileShiftOf(pt);
   c.queues = pt->queues;
   c.stream = stream;
   for(int done = 0; done < numSets;)
@@ -3487,15 +3480,35 @@ int mi_pt_read_depth(MiPt* pt, float* host)
   FLUSH_PENDING(pt);
   if(!pt || !host || pt->width <= 0)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_depth: bad arguments");
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, pt->depthImg(), size_t(pt->width) * size_t(pt->height) * sizeof(float), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return readImage(pt, pt->depthImg(), sizeof(float), host);
 }
 void* mi_pt_accum_device_ptr(MiPt* pt)
 {
   (void)flushPending(pt);
   return pt ? pt->accum : nullptr;
+}
+
+// The two ping-pong images of the denoise calls, at the current size (dropped by a resize: allocFrameResources)
+static int denoiseScratch(MiPt* pt)
+{
+  const size_t px = size_t(pt->width) * size_t(pt->height);
+  if(pt->denoiseA.count != px)
+  {
+    HIP_TRY(pt->denoiseA.alloc(px));
+    HIP_TRY(pt->denoiseB.alloc(px));
+  }
+  return MI_PT_OK;
+}
+// The "result to host" step of the denoise calls: pt->denoised into `host` when one is given, behind `stream` unless the caller has
+// synchronised it already.  Without a host destination the result stays on the device, in stream order.
+static int denoisedToHost(MiPt* pt, float* host, hipStream_t stream, bool synchronised = false)
+{
+  if(!host)
+    return MI_PT_OK;
+  if(!synchronised)
+    HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(host, pt->denoised, size_t(pt->width) * size_t(pt->height) * sizeof(float4), hipMemcpyDeviceToHost));
+  return MI_PT_OK;
 }
 
 int mi_pt_denoise(MiPt* pt, int iterations, float sigmaColor, float sigmaNormal, float sigmaAlbedo, float* host, void* hipStream)
@@ -3504,13 +3517,9 @@ int mi_pt_denoise(MiPt* pt, int iterations, float sigmaColor, float sigmaNormal,
   if(!pt || pt->width <= 0 || iterations < 1 || iterations > 8)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_denoise: bad arguments");
   HIP_TRY(hipSetDevice(pt->device));
-  hipStream_t  stream = reinterpret_cast<hipStream_t>(hipStream);
-  const size_t px     = size_t(pt->width) * size_t(pt->height);
-  if(pt->denoiseA.count != px)
-  {
-    HIP_TRY(pt->denoiseA.alloc(px));
-    HIP_TRY(pt->denoiseB.alloc(px));
-  }
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hipStream);
+  if(int rc = denoiseScratch(pt))
+    return rc;
   const float4* in  = pt->accum;
   float4*       out = pt->denoiseA.ptr;
   for(int i = 0; i < iterations; ++i)
@@ -3520,11 +3529,9 @@ int mi_pt_denoise(MiPt* pt, int iterations, float sigmaColor, float sigmaNormal,
     out = (out == pt->denoiseA.ptr) ? pt->denoiseB.ptr : pt->denoiseA.ptr;
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipStreamSynchronize(stream));  // (this call always, the other two only for a host destination)
   pt->denoised = in;
-  if(host)
-    HIP_TRY(hipMemcpy(host, in, px * sizeof(float4), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return denoisedToHost(pt, host, stream, true);
 }
 
 int mi_pt_denoise_svgf(MiPt* pt, int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, float* host, void* hipStream)
@@ -3535,25 +3542,16 @@ int mi_pt_denoise_svgf(MiPt* pt, int iterations, float sigmaLuminance, float sig
   if(!(pt->accumFrames >= 1.0f))
     return fail(MI_PT_ERR_STATE, "mi_pt_denoise_svgf: nothing rendered yet");
   HIP_TRY(hipSetDevice(pt->device));
-  hipStream_t  stream = reinterpret_cast<hipStream_t>(hipStream);
-  const size_t px     = size_t(pt->width) * size_t(pt->height);
-  if(pt->denoiseA.count != px)
-  {
-    HIP_TRY(pt->denoiseA.alloc(px));
-    HIP_TRY(pt->denoiseB.alloc(px));
-  }
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hipStream);
+  if(int rc = denoiseScratch(pt))
+    return rc;
   // (mean and second moment must cover the same frames for E[l^2] - E[l]^2 to mean anything: otherwise -- guides switched on
   //  mid-accumulation, or an accumulator written by mi_pt_write_accum -- the pass estimates the variance spatially, as it does below 4 frames)
   const float varianceFrames = pt->momentFrames == pt->accumFrames ? pt->accumFrames : 1.0f;
   pt->denoised = pt::launchSvgf(pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->denoiseA.ptr, pt->denoiseB.ptr, pt->width, pt->height, iterations,
                                 varianceFrames, sigmaLuminance, sigmaNormal, sigmaDepth, stream);
   HIP_TRY(hipGetLastError());
-  if(host)
-  {
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(host, pt->denoised, px * sizeof(float4), hipMemcpyDeviceToHost));
-  }
-  return MI_PT_OK;
+  return denoisedToHost(pt, host, stream);
 }
 
 int mi_pt_read_first_hit(MiPt* pt, float* host)
@@ -3568,16 +3566,7 @@ int mi_pt_read_first_hit(MiPt* pt, float* host)
   std::vector<float4> bySlot(size_t(std::max(pt->numSlots, 0)));
   if(!bySlot.empty())
     HIP_TRY(hipMemcpy(bySlot.data(), pt->firstHit.ptr, bySlot.size() * sizeof(float4), hipMemcpyDeviceToHost));
-  memset(host, 0, size_t(pt->width) * size_t(pt->height) * sizeof(float4));
-  int tileShift = 0;
-  while((1 << tileShift) < pt->tileSize)
-    ++tileShift;
-  for(uint32_t slot = 0; slot < uint32_t(bySlot.size()); ++slot)
-  {
-    int px, py;
-    if(pt::pixelOfSlot(pt->ownedTilesHost.data(), tileShift, pt->width, pt->height, slot, px, py))
-      memcpy(host + 4 * (size_t(py) * size_t(pt->width) + size_t(px)), &bySlot[slot], sizeof(float4));
-  }
+  scatterSlots(pt, bySlot.data(), bySlot.size(), 0, host, [](uint32_t) { return true; });
   return MI_PT_OK;
 }
 
@@ -3599,12 +3588,9 @@ int mi_pt_read_motion(MiPt* pt, float* host)
   FLUSH_PENDING(pt);
   if(!pt || !host || pt->width <= 0)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_motion: bad arguments");
-  if(!pt->temporal || !pt->haveMotion)
+  if(!pt->temporal || !pt->temporalData.haveMotion)
     return fail(MI_PT_ERR_STATE, "mi_pt_read_motion: needs mi_pt_set_temporal and a MI_PT_FIRST_FRAME batch after it");
-  HIP_TRY(hipSetDevice(pt->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, pt->motion.ptr, size_t(pt->width) * size_t(pt->height) * sizeof(float4), hipMemcpyDeviceToHost));
-  return MI_PT_OK;
+  return readImage(pt, pt->temporalData.motion.ptr, sizeof(float4), host);
 }
 
 void mi_pt_default_temporal(MiPtTemporalParams* p)
@@ -3630,36 +3616,28 @@ int mi_pt_denoise_temporal(MiPt* pt, const MiPtTemporalParams* tp, float* host, 
      || !(tp->alpha > 0.0f && tp->alpha <= 1.0f) || !(tp->momentsAlpha > 0.0f && tp->momentsAlpha <= 1.0f) || !(tp->maxHistory >= 1.0f)
      || !(tp->normalCos <= 1.0f) || !(tp->depthTolerance >= 0.0f))
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_denoise_temporal: bad arguments");
-  if(!pt->temporal || !pt->haveMotion || !(pt->accumFrames >= 1.0f))
+  if(!pt->temporal || !pt->temporalData.haveMotion || !(pt->accumFrames >= 1.0f))
     return fail(MI_PT_ERR_STATE, "mi_pt_denoise_temporal: needs mi_pt_set_temporal and a MI_PT_FIRST_FRAME batch after it");
   if(pt->tileWorld > 1)
     return fail(MI_PT_ERR_STATE, "mi_pt_denoise_temporal: not under a tile partition (the history is not reduced across ranks)");
   HIP_TRY(hipSetDevice(pt->device));
   hipStream_t  stream = reinterpret_cast<hipStream_t>(hipStream);
   const size_t px     = size_t(pt->width) * size_t(pt->height);
-  if(pt->denoiseA.count != px)
-  {
-    HIP_TRY(pt->denoiseA.alloc(px));
-    HIP_TRY(pt->denoiseB.alloc(px));
-  }
+  if(int rc = denoiseScratch(pt))
+    return rc;
   auto set = [&](int i) {
-    float4* base = pt->history.ptr + size_t(i) * 3 * px;
+    float4* base = pt->temporalData.history.ptr + size_t(i) * 3 * px;
     return pt::TemporalHistory{base, base + px, base + 2 * px};
   };
   const pt::TemporalConsts tc{tp->alpha, tp->momentsAlpha, tp->maxHistory, tp->normalCos, tp->depthTolerance};
-  pt::launchSvgfReproject(pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->motion.ptr, set(pt->historyCur), set(pt->historyCur ^ 1), pt->denoiseA.ptr,
-                          pt->width, pt->height, tc, pt->haveHistory, stream);
-  pt->historyCur ^= 1;
-  pt->haveHistory = true;
+  pt::launchSvgfReproject(pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->temporalData.motion.ptr, set(pt->temporalData.historyCur), set(pt->temporalData.historyCur ^ 1), pt->denoiseA.ptr,
+                          pt->width, pt->height, tc, pt->temporalData.haveHistory, stream);
+  pt->temporalData.historyCur ^= 1;
+  pt->temporalData.haveHistory = true;
   pt->denoised    = pt::launchSvgfFilter(pt->denoiseA.ptr, pt->denoiseB.ptr, pt->accum, pt->albedoImg(), pt->normalImg(), pt->depthImg(), pt->width, pt->height,
                                          tp->iterations, tp->sigmaLuminance, tp->sigmaNormal, tp->sigmaDepth, stream);
   HIP_TRY(hipGetLastError());
-  if(host)
-  {
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(host, pt->denoised, px * sizeof(float4), hipMemcpyDeviceToHost));
-  }
-  return MI_PT_OK;
+  return denoisedToHost(pt, host, stream);
 }
 
 int mi_pt_reset_history(MiPt* pt)
@@ -3667,7 +3645,7 @@ int mi_pt_reset_history(MiPt* pt)
   FLUSH_PENDING(pt);
   if(!pt)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_reset_history: null instance");
-  pt->haveHistory = false;
+  pt->temporalData.haveHistory = false;
   return MI_PT_OK;
 }
 
@@ -3679,7 +3657,7 @@ int mi_pt_set_vertex_motion(MiPt* pt, int enable)
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
   pt->vertexMotion = enable != 0;
-  pt->haveHistory  = false;  // (the motion the history was reprojected along changes its meaning)
+  pt->temporalData.haveHistory  = false;  // (the motion the history was reprojected along changes its meaning)
   return allocVertexMotion(pt);
 }
 
@@ -3701,18 +3679,11 @@ int mi_pt_read_first_hit_triangle(MiPt* pt, uint32_t* host)
     HIP_TRY(hipMemcpy(hits.data(), pt->firstHit.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(tris.data(), pt->firstHitTri.ptr, n * sizeof(uint4), hipMemcpyDeviceToHost));
   }
-  memset(host, 0xff, size_t(pt->width) * size_t(pt->height) * sizeof(uint4));
-  int tileShift = 0;
-  while((1 << tileShift) < pt->tileSize)
-    ++tileShift;
-  for(uint32_t slot = 0; slot < uint32_t(n); ++slot)
-  {
-    int      px, py;
+  scatterSlots(pt, tris.data(), n, 0xff, host, [&](uint32_t slot) {  // (a record only where the first hit is a surface)
     uint32_t id;
     memcpy(&id, &hits[slot].w, sizeof(id));
-    if(id != 0u && id != pt::TEMPORAL_ID_INVALID && pt::pixelOfSlot(pt->ownedTilesHost.data(), tileShift, pt->width, pt->height, slot, px, py))
-      memcpy(host + 4 * (size_t(py) * size_t(pt->width) + size_t(px)), &tris[slot], sizeof(uint4));
-  }
+    return id != 0u && id != pt::TEMPORAL_ID_INVALID;
+  });
   return MI_PT_OK;
 }
 
@@ -3723,13 +3694,13 @@ int mi_pt_read_previous_positions(MiPt* pt, int renderPrimID, float* positions)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: bad arguments");
   if(!vertexMotionActive(pt))
     return fail(MI_PT_ERR_STATE, "mi_pt_read_previous_positions: vertex motion is not in force (mi_pt_set_vertex_motion, mi_pt_set_temporal, mi_pt_set_deformation or mi_pt_set_vertex_updates)");
-  if(renderPrimID < 0 || size_t(renderPrimID) >= pt->vmPrevOffset.size() || pt->vmPrevOffset[size_t(renderPrimID)] == SIZE_MAX)
+  if(renderPrimID < 0 || size_t(renderPrimID) >= pt->vm.prevOffset.size() || pt->vm.prevOffset[size_t(renderPrimID)] == SIZE_MAX)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_read_previous_positions: render primitive " + std::to_string(renderPrimID) + " neither deforms nor is driven by the caller");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t nv = pt->primVertices[size_t(renderPrimID)];
   if(nv)
-    HIP_TRY(hipMemcpy(positions, pt->vmPrevPositions.ptr + pt->vmPrevOffset[size_t(renderPrimID)], nv * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(positions, pt->vm.prevPositions.ptr + pt->vm.prevOffset[size_t(renderPrimID)], nv * 12, hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
 
@@ -3798,17 +3769,18 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_memory: null argument");
   HIP_TRY(hipSetDevice(pt->device));
+  // The feature groups sum themselves (MiPt::*::bytes()); every other buffer is named here.  Four small ones are in neither total, as they
+  // never were: matDirty, skyPre, tmHistogram and tmAutoState.  Counting them is a change of what the totals report, not of this bookkeeping.
   const uint64_t scene = pt->materials.bytes() + pt->texInfos.bytes() + pt->nodes.bytes() + pt->prims.bytes() + pt->lights.bytes() + pt->textures.bytes() + pt->texels.bytes() + pt->texQuads.bytes()
                          + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->alphaTris.bytes()
-                         + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deformPool.bytes() + pt->deformTasks.bytes()
-                         + pt->deformBlockTask.bytes() + pt->deformJoints.bytes() + pt->deformWeights.bytes() + refitBytes(pt) + pt->vmPrevPositions.bytes() + pt->vmPrims.bytes()
-                         + pt->vmDeformIDs.bytes() + pt->vuTable.bytes() + pt->vuTasks.bytes() + pt->vuNormalTasks.bytes() + pt->vuBlockTask.bytes() + pt->tuTables.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
+                         + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deform.bytes() + pt->refit.bytes() + pt->vm.bytes()
+                         + pt->vu.bytes() + pt->tuTables.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
   const uint64_t pathState = pt->pathArrays.bytes() + pt->optThroughput.bytes() + pt->optMisc.bytes() + pt->optMedium.bytes() + pt->optPixelSum.bytes() + pt->optGuides.bytes()
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
                             + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->euScratch.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
-                            + pt->motion.bytes() + pt->history.bytes() + pt->prevObjectToWorld.bytes() + pt->firstHitTri.bytes();
+                            + pt->temporalData.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
   out->sceneBytes       = scene;
