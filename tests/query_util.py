@@ -66,11 +66,14 @@ def measure_float32_error(st, rays, ref):
 class SceneTris:
     """Every triangle of every visible render node of a scene description, in world space."""
 
-    def __init__(self, scene):
+    def __init__(self, scene, nodes=None):
+        """nodes: the render nodes to take (default: every visible one)."""
         d = scene.desc.contents
         V, V32, node, prim, tri, mat, flip = [], [], [], [], [], [], []
         for n in range(d.numRenderNodes):
             rn = d.renderNodes[n]
+            if nodes is not None and n not in nodes:
+                continue
             if d.renderNodeVisible and not d.renderNodeVisible[n]:
                 continue
             if rn.renderPrimID < 0 or rn.renderPrimID >= d.numRenderPrimitives:
@@ -117,16 +120,21 @@ class SceneTris:
         return t, s
 
 
-def make_rays(st, n=2048, seed=7):
+def make_rays(st, n=2048, seed=7, bounds=None, aim=None):
     """Half of the origins on a sphere of 1.5 x the bounds' radius around their centre, half inside the bounds; every ray aims at a uniform
-    point of the bounds.  Unit directions, tMin 0, no far bound."""
+    point of the bounds.  Unit directions, tMin 0, no far bound.
+    bounds: (lo, hi) to use instead of the scene's; aim(rng, uniform targets) -> the (n, 3) points the rays aim at instead."""
     rng = np.random.default_rng(seed)
-    c = 0.5 * (st.lo + st.hi)
+    lo, hi = (st.lo, st.hi) if bounds is None else (np.asarray(bounds[0], np.float64), np.asarray(bounds[1], np.float64))
+    radius = st.radius if bounds is None else float(0.5 * np.linalg.norm(hi - lo))
+    c = 0.5 * (lo + hi)
     on = rng.normal(size=(n // 2, 3))
-    on = c + 1.5 * st.radius * on / np.linalg.norm(on, axis=1, keepdims=True)
-    inside = rng.uniform(st.lo, st.hi, size=(n - n // 2, 3))
+    on = c + 1.5 * radius * on / np.linalg.norm(on, axis=1, keepdims=True)
+    inside = rng.uniform(lo, hi, size=(n - n // 2, 3))
     o = np.concatenate([on, inside])
-    target = rng.uniform(st.lo, st.hi, size=(n, 3))
+    target = rng.uniform(lo, hi, size=(n, 3))
+    if aim is not None:
+        target = aim(rng, target)
     d = target - o
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     rays = np.zeros(n, RAY_DTYPE)
@@ -237,9 +245,11 @@ class Reference:
             self.normal, self.front = np.zeros((n, 3)), np.zeros(n, bool)
 
 
-def check_hits(st, rays, ref, hits, tol_t, tol_b, what=""):
+def check_hits(st, rays, ref, hits, tol_t, tol_b, what="", position_rounding=0.0):
     """The GPU (or host-shim) records of CLOSEST mode against the reference: exact ids on unambiguous rays within the tolerances, the allowed
-    sets on ambiguous ones.  Returns the largest errors seen (t relative to max(1, t), barycentrics, position, normal)."""
+    sets on ambiguous ones.  Returns the largest errors seen (t relative to max(1, t), barycentrics, position, normal).
+    position_rounding: what the float32 rounding of a hit position itself may add to its error (half an ulp of the largest coordinate: for scenes
+    far from the origin, where that exceeds the share of t's tolerance)."""
     HIT, FRONT, INVALID = 1, 2, 4
     assert not (hits["flags"] & INVALID).any(), what
     got_hit = (hits["flags"] & HIT) != 0
@@ -276,7 +286,7 @@ def check_hits(st, rays, ref, hits, tol_t, tol_b, what=""):
     print("QUERY", what, "rays", len(rays), "hits", int(h.sum()), "ambiguous", int(ref.ambiguous.sum()), "errors", out, "tolerances", tol_t, tol_b,
           "size", st.size)
     assert out["t"] <= tol_t and out["b"] <= tol_b, (what, out)
-    assert out["position"] <= tol_t * max(1.0, st.size) and out["normal"] <= tol_t * max(1.0, st.size), (what, out, st.size)
+    assert out["position"] <= tol_t * max(1.0, st.size) + position_rounding and out["normal"] <= tol_t * max(1.0, st.size), (what, out, st.size)
     assert (np.abs(np.linalg.norm(g["normal"].astype(np.float64), axis=1) - 1.0) < 1e-6).all(), what
     # (the device turns the normal by ITS dot product, a chain of fmas; another summation order may land a last-place unit above zero on a grazing ray)
     assert ((g["normal"].astype(np.float64) * rays["direction"][h].astype(np.float64)).sum(1) <= 1e-7).all(), what

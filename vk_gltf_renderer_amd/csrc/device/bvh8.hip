@@ -559,9 +559,10 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
     if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
     hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
     if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
-    r.numNodes = numNodes8;
-    r.numTris  = n;
-    out        = std::move(r);
+    r.numNodes  = numNodes8;
+    r.numTris   = n;
+    r.numLevels = uint32_t(r.levels.size()) - 1u;
+    out         = std::move(r);
     return true;
   }
   // ---- host collapse (A/B reference, and the one-triangle scene): download the BVH2 -------------------------------------------
@@ -643,6 +644,7 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
   struct Work
   {
     uint32_t          node8;
+    uint32_t          level = 0;  // nodes above it
     std::vector<Cand> cands;  // the (<= 2 at start) children to expand
   };
   std::vector<Work> queue;
@@ -680,7 +682,8 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
   {
     const std::vector<Cand> cands0 = std::move(queue[qi].cands);
     std::vector<Cand>       cands;
-    const uint32_t          self = queue[qi].node8;
+    const uint32_t          self = queue[qi].node8, level = queue[qi].level;
+    r.numLevels = std::max(r.numLevels, level + 1u);
     uint32_t                MAX_LEAF_TRIS = uint32_t(leafTrisOpt);
     for(;;)
     {
@@ -816,6 +819,7 @@ bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, st
         N.imask |= uint8_t(1u << s);
         Work w;
         w.node8 = uint32_t(nodes8.size());
+        w.level = level + 1u;
         for(int k = 0; k < 2; ++k)
         {
           Cand cc;

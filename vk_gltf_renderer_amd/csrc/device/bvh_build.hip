@@ -473,6 +473,21 @@ __global__ void k_re_refit(Bvh2Tree T, unsigned int* arrive)
   if(leaf <= T.numInner)
     reinsertRefit(T, arrive, leaf);
 }
+// The height of the BVH2 -- the largest number of inner nodes above a leaf, which is how many entries a walk that leaves one per level can have
+// pending: one thread per leaf climbs the parent links of k_re_parents (cleared to -1 first, and the climb is bounded by the node count: a broken
+// tree ends it).  O(leaves x height) reads of one int each, no tickets.
+__global__ void k_tree_height(Bvh2Tree T, unsigned int* height)
+{
+  const int    leaf = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned int d    = 0;
+  if(leaf <= T.numInner)
+    for(int cur = T.leafParent[leaf]; cur >= 0 && cur < T.numInner && d <= unsigned(T.numInner); cur = T.parent[cur])
+      ++d;
+  for(int o = 32; o >= 1; o >>= 1)
+    d = max(d, __shfl_xor(d, o));
+  if((threadIdx.x & 63u) == 0u)
+    atomicMax(height, d);
+}
 
 // A failed call records the error and returns false from the builder it is written in; the DevBuf locals free what was allocated.
 #define BUILD_CHECK(x)                                                                                                  \
@@ -541,6 +556,26 @@ static bool reinsertBvh2(float4* nodes, int numInner, int root, int passes, int 
   if(timing)
     fprintf(stderr, "[mi_pt build] reinsertion: %d of %d passes x %d rounds over %d nodes and leaves, %u subtrees moved, %.2f ms\n", passesRun, passes, rounds, ids, movesAll,
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return true;
+}
+
+static bool bvh2Height(float4* nodes, int numInner, int root, hipStream_t stream, std::string& err, uint32_t& height)
+{
+  DevBuf<int>          parent, leafParent;
+  DevBuf<unsigned int> h;
+  const int            B = 256;
+  BUILD_CHECK(parent.alloc(numInner));
+  BUILD_CHECK(leafParent.alloc(numInner + 1));
+  BUILD_CHECK(h.alloc(1));
+  BUILD_CHECK(hipMemsetAsync(parent.ptr, 0xff, sizeof(int) * size_t(numInner), stream));
+  BUILD_CHECK(hipMemsetAsync(leafParent.ptr, 0xff, sizeof(int) * size_t(numInner + 1), stream));
+  BUILD_CHECK(hipMemsetAsync(h.ptr, 0, sizeof(unsigned int), stream));
+  const Bvh2Tree T{nodes, parent.ptr, leafParent.ptr, numInner, root};
+  hipLaunchKernelGGL(k_re_parents, dim3((numInner + B - 1) / B), dim3(B), 0, stream, T);
+  hipLaunchKernelGGL(k_tree_height, dim3((numInner + 1 + B - 1) / B), dim3(B), 0, stream, T, h.ptr);
+  BUILD_CHECK(hipGetLastError());
+  BUILD_CHECK(hipMemcpyAsync(&height, h.ptr, sizeof(height), hipMemcpyDeviceToHost, stream));
+  BUILD_CHECK(hipStreamSynchronize(stream));
   return true;
 }
 
@@ -680,7 +715,9 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
     BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(sortTemp.ptr, sortBytes, keysA.ptr, keysB.ptr, valsA.ptr, valsB.ptr, int(n), 0, 63, stream));
 
     BUILD_CHECK(nodes.alloc(4 * size_t(n - 1)));
-    if(!in.karrasTopology)
+    // the BVH2 over the sorted references, by either topology (both can run again: they read the keys, the boxes and the order only)
+    auto topology = [&](bool karras) -> bool {
+    if(!karras)
     {
       BUILD_CHECK(cidA.alloc(n)); BUILD_CHECK(cidB.alloc(n)); BUILD_CHECK(nn.alloc(n));
       BUILD_CHECK(cloA.alloc(n)); BUILD_CHECK(chiA.alloc(n));
@@ -747,9 +784,42 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
     out.root     = 0;
     out.numNodes = n - 1;
     }
+    return true;
+    };
+    // A walk holds one stack entry per level it descends with another child pending, and drops what its stack cannot hold (pt_bvh.h: LaneStack).
+    // PLOC bounds no height: boxes nested in one another, each the union of itself with any smaller one, merge one pair per round into a tree as
+    // deep as its leaves are many.  With a limit (maxHeight: the caller's stack) a tree taller than that is built again with the Morton-prefix
+    // topology, whose height the key and index bits bound (63 + 32) -- and once more without reinsertion if the passes made it a chain again,
+    // which for nested boxes is what costs the least area.
+    static const bool timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
+    bool              karras = in.karrasTopology;
+    int               passes = in.reinsertPasses;
+    for(;;)
+    {
+      out.reinsertMoves = 0;
+      if(!topology(karras))
+        return false;
+      if(out.numNodes >= 3 && passes > 0 && !reinsertBvh2(nodes.ptr, int(out.numNodes), out.root, passes, in.reinsertRounds, stream, err, &out.reinsertMoves))
+        return false;
+      if(in.maxHeight <= 0)
+        break;
+      if(!bvh2Height(nodes.ptr, int(out.numNodes), out.root, stream, err, out.height))
+        return false;
+      if(timing)
+        fprintf(stderr, "[mi_pt build] BVH2 height %u (limit %d): %s topology, %d reinsertion passes\n", out.height, in.maxHeight, karras ? "Morton-prefix" : "PLOC", passes);
+      if(out.height <= uint32_t(in.maxHeight))
+        break;
+      if(!karras)
+        karras = true;
+      else if(passes > 0)
+        passes = 0;
+      else
+      {
+        err = "the BVH2 is " + std::to_string(out.height) + " levels high, the walk's stack holds " + std::to_string(in.maxHeight);
+        return false;
+      }
+    }
   }
-  if(out.numNodes >= 3 && in.reinsertPasses > 0 && !reinsertBvh2(nodes.ptr, int(out.numNodes), out.root, in.reinsertPasses, in.reinsertRounds, stream, err, &out.reinsertMoves))
-    return false;
   BUILD_CHECK(hipMemcpy(hb, bounds.ptr, sizeof(hb), hipMemcpyDeviceToHost));
   for(int c = 0; c < 3; ++c)
   {

@@ -19,6 +19,7 @@
 #include "material_patch.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
+#include "pt_bvh8.h"
 #include "pt_deform.h"
 #include "pt_env_update.h"
 #include "pt_texture_update.h"
@@ -895,6 +896,10 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     in.splitFactor    = pt->sw.splitFactor;
     in.splitMaxDepth  = pt->sw.splitMaxDepth;
     in.splitMinShare  = pt->sw.splitMinShare;
+    // The BVH2 walk leaves one stack entry per level: its tree is no taller than that stack (buildBvh rebuilds a taller one).  The 8-wide walk
+    // is bounded after the collapse, below.
+    pt->wide     = (pt->bvhBuilder & 1) == 0;
+    in.maxHeight = pt->wide ? 0 : pt::BVH_STACK_LDS + pt::BVH_STACK_PRIV;
     pt::BvhBuildOutput bo;
     std::string        err;
     if(!pt::buildBvh(in, bo, nullptr, err))
@@ -907,7 +912,6 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     pt->splitRefs                    = bo.numTris > bo.sceneTris;
     pt->staticStats.bvhNodeBytes     = 64;
     pt->staticStats.bvhTriangleBytes = sizeof(pt::DevTri);
-    pt->wide = (pt->bvhBuilder & 1) == 0;
     // the triangle rounds of the 8-wide walk pack (triangle index | owner lane << 26) into one word (pt_kernels.hip)
     if(pt->wide && bo.numTris >= (1u << 26))
       return fail(MI_PT_ERR_ARGUMENT, "scene has 2^26 or more triangles: beyond what the 8-wide BVH walk indexes (select the BVH2 walk, bvhBuilder bit 0)");
@@ -920,6 +924,25 @@ int buildAccelerationOver(MiPt* pt, bool resident)
       pt->refitCapable  = !pt->sw.hostCollapse && bo.numNodes > 0;  // (a one-reference scene takes the host collapse: bvh8.hip)
       if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
         return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
+      // A node visit of the 8-wide walk pushes at most one group (the visited node's other hit inner children), and none at a node without inner
+      // children: a tree of L levels needs L - 1 stack slots at most.  One with more levels than the stack covers (LaneStack2 drops what it cannot
+      // hold) is collapsed again from a BVH2 of that height at most -- an 8-wide node spans at least one BVH2 level -- which buildBvh makes with the
+      // Morton-prefix topology or fails.
+      const uint32_t maxLevels = uint32_t(pt::BVH8_STACK_LDS + pt::BVH8_STACK_PRIV) + 1u;
+      if(b8.numLevels > maxLevels)
+      {
+        if(getenv("MI_PT_BUILD_TIMING"))
+          fprintf(stderr, "[mi_pt build] 8-wide tree of %u levels (limit %u): rebuilt from a BVH2 of bounded height\n", b8.numLevels, maxLevels);
+        in.karrasTopology = true;
+        in.maxHeight      = int(maxLevels);
+        b8                = pt::Bvh8Output();
+        if(!pt::buildBvh(in, bo, nullptr, err))
+          return fail(MI_PT_ERR_HIP, "BVH build failed: " + err);
+        if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
+          return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
+        if(b8.numLevels > maxLevels)
+          return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: more levels than the walk's stack covers");
+      }
       // the wide structure owns its own triangle order; the BVH2 arrays are no longer needed
       bo.nodes.release();
       bo.tris.release();

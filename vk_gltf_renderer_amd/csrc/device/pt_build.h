@@ -25,6 +25,8 @@ struct BvhBuildInput
   float                   splitFactor    = 0.0f;   // triangle pre-splitting (bvh_split.h): references for parts whose box area exceeds this x the mean; 0 = off
   int                     splitMaxDepth  = 8;      // ... at most 2^this references per triangle
   float                   splitMinShare  = 0.1f;   // ... and only in scenes where triangles above 64 x the mean hold at least this share of the summed box area (0 = always)
+  int                     maxHeight      = 0;      // inner nodes above any leaf of the BVH2 handed out: what the walk's stack holds (0 = unbounded, unmeasured); a taller
+                                                   // tree is built again with the Morton-prefix topology, then without reinsertion; still taller: the build fails
 };
 struct BvhBuildOutput
 {
@@ -34,6 +36,7 @@ struct BvhBuildOutput
   uint32_t sceneTris = 0;               // triangles the references were made from
   int      root     = 0;
   uint32_t reinsertMoves = 0;   // subtrees the reinsertion passes moved
+  uint32_t height        = 0;   // of the BVH2, measured only under BvhBuildInput::maxHeight
   float    centroidLo[3] = {0, 0, 0}, centroidHi[3] = {0, 0, 0};
 };
 bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, std::string& err);
@@ -46,6 +49,7 @@ struct Bvh8Output
   DevBuf<uint4>  nodes;  // 5 uint4 per node
   DevBuf<DevTri> tris;   // node order (triangles of a node's leaf children are contiguous)
   uint32_t numNodes = 0, numTris = 0;
+  uint32_t numLevels = 0;  // nodes on the longest path from the root
   // the refit data (Bvh8Options::keepRefit, device collapse only): per triangle slot the box the builder
   // filed that reference under, per node room for its box (left for k_refit_level to fill), and the start of every level of the
   // breadth-first node array (+ numNodes at the end)

@@ -227,13 +227,16 @@ class PathTracer:
     """The HIP path tracer instance (libmi_pt.so)."""
 
     def __init__(self, scene, device=0, collect_counters=False, bvh=0):
+        """bvh: MiPtCreateOptions::bvhBuilder, two bits.  Bit 0: the walk -- 0 the 8-wide compressed BVH (default), 1 the plain BVH2.  Bit 1: the
+        topology of the BVH2 both are made from -- 0 PLOC clustering over the Morton order (default), 2 the Karras Morton-prefix hierarchy.  So 0 .. 3;
+        the images and the query records do not depend on it."""
         self._l = capi.pt_lib()
         self._p = C.c_void_p()
         self._scene = scene  # keep host tables alive for the duration of mi_pt_create only (they are copied)
         opts = capi.MiPtCreateOptions()
         opts.device = device
         opts.collectCounters = 1 if collect_counters else 0
-        opts.bvhBuilder = bvh  # 0: 8-wide compressed BVH (default), 1: plain BVH2
+        opts.bvhBuilder = bvh  # bit 0: 0 = 8-wide compressed BVH (default), 1 = plain BVH2; bit 1: 0 = PLOC clustering (default), 1 (bvh = 2, 3) = Karras topology
         _check_pt(self._l.mi_pt_create(scene.desc, C.byref(opts), C.byref(self._p)))
         self.width = self.height = 0
         self.temporal = False
