@@ -144,7 +144,6 @@ struct MiPt
   int device = 0;
   int numCUs = 256;
   RunSwitches sw;
-  int accelBuilds = 0;  // acceleration-structure builds of this instance so far (0 while the first one runs)
   // mi_pt_set_frame_queue: consecutive mi_pt_render_frame calls held back and issued together (flushPending)
   int               frameQueueDepth = 1;
   int               pendingFrames   = 0;
@@ -166,13 +165,6 @@ struct MiPt
   DevBuf<float>               srgbLut;
   DevBuf<float4>              envPixels;
   DevBuf<MiEnvAccel>          envAccel;
-  DevBuf<pt::DevAlphaTri>     alphaTris;
-  DevBuf<pt::DevShadeTri>     shadeTris;
-  DevBuf<float4>              bvhNodes;    // the BVH2 (bvhBuilder bit 0), 4 float4 per node ...
-  DevBuf<uint4>               bvh8Nodes;   // ... or the 8-wide BVH collapsed from it, 5 uint4 per node
-  DevBuf<float>               bvh8Planes;  // the nodes' planes as floats for the packet walk (DevScene::bvh8Planes)
-  DevBuf<pt::DevTri>          bvhTris;     // the triangle records, in the order of whichever of the two is resident
-  bool                        wide      = true;
   pt::DevScene                scene{};
   bool                        hasAlpha = false, hasAlphaTest = false, hasVolumeScatter = false, simpleMaterials = true, hasTransmissive = false;
   // device-resident descriptor copies (see k_shade): the scene struct, re-uploaded when the environment changes, and a ring
@@ -199,7 +191,6 @@ struct MiPt
   std::vector<MiGltfTextureInfo>   hostTexInfos;
   std::vector<pt::DevTexture>      hostTextures;
   DevBuf<uint8_t>               matDirty;       // per render node: pt::MATERIAL_PATCH_* of the material update in progress (k_patch_materials)
-  bool                          splitRefs = false;  // the resident tree holds pre-split references (more triangle slots than scene triangles)
   std::vector<uint32_t>         primTriangles;  // per render primitive: triangle count, 0 when it has no usable geometry
   std::vector<pt::DevPrim>      hostPrims;      // the device addresses of every primitive's streams (mi_pt_read_vertices, deformation)
   std::vector<uint32_t>         primVertices;   // per render primitive: vertex count
@@ -243,32 +234,57 @@ struct MiPt
   DevBuf<uint8_t>               euScratch;      // header, row areas, tile sums, prefix arrays, index lists (pt_env_update.h): grown, never shrunk (rendererBytes)
   float                         envIntegral = 0.0f;  // of the resident environment (mi_pt_read_environment)
   MiPtEnvironmentUpdateInfo     euInfo{};       // the counters of mi_pt_get_environment_update_info (scratchBytes is computed there)
-  int                           bvhBuilder = 0;
-  // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
-  int                           accelMode = MI_PT_ACCEL_REBUILD;
-  float                         accelRatio = 1.5f;
-  int                           lastUpdate = MI_PT_ACCEL_LAST_BUILD;
-  bool                          switchBuild = false;  // the build of mi_pt_set_accel_update is running
-  bool                          refitCapable = false; // the last build went through the device collapse: a build in REFIT / AUTO mode keeps refit data
-  uint64_t                      accelRefits = 0, trianglesMoved = 0;
-  struct RefitData  // what a build keeps for the refits after it, and a build or a switch to REBUILD drops
+  // ---- the acceleration structure: its arrays, the update policy, what the last build left and the counters, with the rules that tie them
+  // together.  What it is built from (nodes, instFlags, hostNodes, hostVisible, primTriangles) and what the kernels see (scene) stay above.
+  struct Accel
   {
-    DevBuf<pt::RefitBox>  slotBox, builtBox, nodeBox;  // per slot: current box, box the build filed; per node: its box
-    DevBuf<float>         sah;         // per node: its SAH term
-    DevBuf<double>        sahPartial;  // the cost reduction (pt::REFIT_SAH_PARTIALS + 1)
-    DevBuf<uint8_t>       dirty;       // per render node: pt::REFIT_CLEAN / MOVED / HOME
-    std::vector<uint32_t> levels;      // level starts of the node array + the node count; empty = no refit data
-    double                sahAtBuild = 0.0, sahNow = 0.0;
-    uint64_t              bytes() const { return slotBox.bytes() + builtBox.bytes() + nodeBox.bytes() + sah.bytes() + sahPartial.bytes() + dirty.bytes(); }
-  } refit;
-  std::vector<MiGltfRenderNode> builtNodes;       // the node table of the last full build
-  std::vector<uint8_t>          primDirty;        // per render primitive: deformed since the last acceleration update ...
-  std::vector<uint8_t>          primDeformed;     // ... since the last full build
-  // resident mode (mi_pt_set_accel_resident): the tree holds the hidden render nodes too, so that visibility is a refit and a material id a patch
-  bool                          accelResident = false;  // as requested
-  bool                          residentTree  = false;  // the resident structure was built over every render node that owns triangles
-  uint64_t                      hiddenTris = 0;         // triangles of the hidden render nodes in it
-  uint64_t                      visibilityRefits = 0, materialPatches = 0;
+    DevBuf<float4>              bvhNodes;    // the BVH2 (bvhBuilder bit 0), 4 float4 per node ...
+    DevBuf<uint4>               bvh8Nodes;   // ... or the 8-wide BVH collapsed from it, 5 uint4 per node
+    DevBuf<float>               bvh8Planes;  // the nodes' planes as floats for the packet walk (DevScene::bvh8Planes)
+    DevBuf<pt::DevTri>          bvhTris;     // the triangle records, in the order of whichever of the two is resident
+    DevBuf<pt::DevShadeTri>     shadeTris;
+    DevBuf<pt::DevAlphaTri>     alphaTris;
+    bool                        wide      = true;
+    bool                        splitRefs = false;  // the resident tree holds pre-split references (more triangle slots than scene triangles)
+    int                         bvhBuilder = 0;
+    // acceleration updates (mi_pt_set_accel_update): the mode, and the refit data a build keeps when it is not REBUILD (bvh_refit.hip)
+    int                         accelMode = MI_PT_ACCEL_REBUILD;
+    float                       accelRatio = 1.5f;
+    int                         lastUpdate = MI_PT_ACCEL_LAST_BUILD;
+    bool                        switchBuild = false;  // the build of mi_pt_set_accel_update / mi_pt_set_accel_resident is running
+    bool                        refitCapable = false; // the last build went through the device collapse: a build in REFIT / AUTO mode keeps refit data
+    struct RefitData  // what a build keeps for the refits after it, and a build or a switch to REBUILD drops
+    {
+      DevBuf<pt::RefitBox>  slotBox, builtBox, nodeBox;  // per slot: current box, box the build filed; per node: its box
+      DevBuf<float>         sah;         // per node: its SAH term
+      DevBuf<double>        sahPartial;  // the cost reduction (pt::REFIT_SAH_PARTIALS + 1)
+      DevBuf<uint8_t>       dirty;       // per render node: pt::REFIT_CLEAN / MOVED / HOME
+      std::vector<uint32_t> levels;      // level starts of the node array + the node count; empty = no refit data
+      double                sahAtBuild = 0.0, sahNow = 0.0;
+      uint64_t              bytes() const { return slotBox.bytes() + builtBox.bytes() + nodeBox.bytes() + sah.bytes() + sahPartial.bytes() + dirty.bytes(); }
+    } refit;
+    std::vector<MiGltfRenderNode> builtNodes;     // the node table of the last full build
+    std::vector<uint8_t>          primDirty;      // per render primitive: deformed since the last acceleration update ...
+    std::vector<uint8_t>          primDeformed;   // ... since the last full build
+    // resident mode (mi_pt_set_accel_resident): the tree holds the hidden render nodes too, so that visibility is a refit and a material id a patch
+    bool                        accelResident = false;  // as requested
+    bool                        residentTree  = false;  // the resident structure was built over every render node that owns triangles
+    uint64_t                    hiddenTris = 0;         // triangles of the hidden render nodes in it
+    int                         accelBuilds = 0;  // acceleration-structure builds of this instance so far (0 while the first one runs)
+    uint64_t                    accelRefits = 0, trianglesMoved = 0;
+    uint64_t                    visibilityRefits = 0, materialPatches = 0;
+
+    uint64_t bytes() const { return bvhNodes.bytes() + bvh8Nodes.bytes() + bvh8Planes.bytes() + bvhTris.bytes() + shadeTris.bytes() + alphaTris.bytes() + refit.bytes(); }
+    // An update can be a refit: the mode allows it and the resident tree is an 8-wide one that kept its refit data
+    bool canRefit() const { return accelMode != MI_PT_ACCEL_REBUILD && !refit.levels.empty() && bvh8Nodes.ptr && wide; }
+    // No build of this instance keeps refit data (the BVH2 walk, the host collapse): its updates build, and resident mode stays inert
+    bool keepsNoRefitData(const RunSwitches& sw) const { return (bvhBuilder & 1) != 0 || sw.hostCollapse; }
+    // What a build releases at its head.  The planes and the shade and alpha records are NOT among it: each is replaced when a build next
+    // allocates it, so after a build over nothing (every node hidden) the old ones are still held, and still counted by bytes().
+    void releaseTree() { bvhNodes.release(); bvhTris.release(); bvh8Nodes.release(); }
+    // ... and what a failed build or refit releases: every array
+    void releaseAll() { releaseTree(); bvh8Planes.release(); shadeTris.release(); alphaTris.release(); }
+  } accel;
   // frame state
   int                     width = 0, height = 0;
   int                     tileRank = 0, tileWorld = 1, tileSize = 64;
@@ -597,7 +613,7 @@ int allocPathResources(MiPt* pt, int frames)
   size_t candCap = qsize * 2;
   if(pt->sw.candPoolSet)
     candCap = pt->sw.candPool;
-  if(pt->hasTransmissive && pt->wide && candCap > 0)
+  if(pt->hasTransmissive && pt->accel.wide && candCap > 0)
   {
     candCap = std::min(candCap, size_t(0x7fffffff));
     HIP_TRY(pt->candPool.alloc(candCap));
@@ -729,37 +745,13 @@ hipEvent_t getEvent(MiPt* pt, size_t& cursor)
 }
 
 
-// Flattens the visible render-node instances to world-space triangles and builds the acceleration structure over them on the
-// device: Morton sort + PLOC -> BVH2 -> (default) 8-wide collapse, then the per-triangle shading / alpha records.  Everything it
-// needs is resident (geometry pool, materials) or kept on the host in MiPt (node matrices, visibility), so it serves the scene
-// build (mi_pt_create; reference: SceneRtx BLAS + TLAS build, src/gltf_scene_rtx.cpp:173-385) and the transform / visibility
-// updates of animated scenes (mi_pt_update_render_nodes; reference: TLAS update, src/gltf_scene_transform_vk.cpp:534-639) alike.
-int buildAccelerationUnguarded(MiPt* pt);
-void dropAcceleration(MiPt* pt);
-// A failed (re)build must not leave the scene descriptor pointing at freed or half-built arrays: mi_pt_update_render_nodes runs
-// this once per animated frame, and the next mi_pt_render_frame would walk them.  On any error the instance falls back to an
-// EMPTY structure (frames render the environment only) and the error is returned to the caller.
-int buildAcceleration(MiPt* pt)
-{
-  const auto t0 = BuildClock::now();
-  const int  rc = buildAccelerationUnguarded(pt);
-  if(buildTiming() && pt->accelBuilds > 1)  // (the first build's phases are printed by mi_pt_create)
-  {
-    (void)hipDeviceSynchronize();
-    printBuildTiming("rebuild", t0);
-  }
-  pt->lastUpdate = MI_PT_ACCEL_LAST_BUILD;
-  if(rc != MI_PT_OK)
-    dropAcceleration(pt);
-  return rc;
-}
 // The structure's arrays as the kernels see them (all null once they are released); the per-triangle shade and alpha records are made from
-// them afterwards (buildAccelerationOver)
+// them afterwards (makeTriangleRecords)
 void publishAcceleration(MiPt* pt)
 {
   pt::DevScene& S = pt->scene;
-  S.bvhNodes = pt->bvhNodes.ptr; S.bvh8Nodes = pt->bvh8Nodes.ptr; S.tris = pt->bvhTris.ptr;
-  S.bvh8Planes = pt->bvh8Nodes.ptr ? pt->bvh8Planes.ptr : nullptr;
+  S.bvhNodes = pt->accel.bvhNodes.ptr; S.bvh8Nodes = pt->accel.bvh8Nodes.ptr; S.tris = pt->accel.bvhTris.ptr;
+  S.bvh8Planes = pt->accel.bvh8Nodes.ptr ? pt->accel.bvh8Planes.ptr : nullptr;
   S.shadeTris = nullptr;
   S.alphaTris = nullptr;
   pt->sceneDevDirty = true;
@@ -768,9 +760,8 @@ void publishAcceleration(MiPt* pt)
 void dropAcceleration(MiPt* pt)
 {
   const std::string why = g_lastError;  // (the frees below must not disturb the message)
-  pt->refit = MiPt::RefitData{};
-  pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
-  pt->bvh8Planes.release(); pt->shadeTris.release(); pt->alphaTris.release();
+  pt->accel.refit = MiPt::Accel::RefitData{};
+  pt->accel.releaseAll();
   publishAcceleration(pt);
   pt::DevScene& S = pt->scene;
   S.numTris = 0; S.bvh8NumNodes = 0; S.bvhRoot = pt::BVH_EMPTY;
@@ -812,50 +803,58 @@ std::vector<uint8_t> instanceFlags(MiPt* pt)
 // The SAH cost of the resident tree from the refit data (the node boxes and terms k_refit_level wrote), read back: one small copy
 int readSahCost(MiPt* pt, double& cost)
 {
-  pt::launchSahCost(pt->refit.sah.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->refit.nodeBox.ptr, pt->refit.sahPartial.ptr, nullptr);
+  pt::launchSahCost(pt->accel.refit.sah.ptr, uint32_t(pt->scene.bvh8NumNodes), pt->accel.refit.nodeBox.ptr, pt->accel.refit.sahPartial.ptr, nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(&cost, pt->refit.sahPartial.ptr + pt::REFIT_SAH_PARTIALS, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&cost, pt->accel.refit.sahPartial.ptr + pt::REFIT_SAH_PARTIALS, sizeof(double), hipMemcpyDeviceToHost));
   return MI_PT_OK;
 }
 
 // One refit pass over the `numNodes` nodes of the resident tree: every node from its children, level by level (`levels`: the build's own while it
-// runs, pt->refit.levels afterwards), the packet walk's planes where there are any, the SAH cost into `cost`
+// runs, pt->accel.refit.levels afterwards), the packet walk's planes where there are any, the SAH cost into `cost`
 int refitPass(MiPt* pt, uint32_t numNodes, const std::vector<uint32_t>& levels, double& cost)
 {
-  pt::launchRefitLevels(pt->bvh8Nodes.ptr, levels, pt->refit.slotBox.ptr, pt->refit.nodeBox.ptr, pt->refit.sah.ptr, nullptr);
-  if(pt->bvh8Planes.ptr)
-    pt::launchBvh8Planes(pt->bvh8Nodes.ptr, numNodes, pt->bvh8Planes.ptr, nullptr);
+  pt::launchRefitLevels(pt->accel.bvh8Nodes.ptr, levels, pt->accel.refit.slotBox.ptr, pt->accel.refit.nodeBox.ptr, pt->accel.refit.sah.ptr, nullptr);
+  if(pt->accel.bvh8Planes.ptr)
+    pt::launchBvh8Planes(pt->accel.bvh8Nodes.ptr, numNodes, pt->accel.bvh8Planes.ptr, nullptr);
   HIP_TRY(hipGetLastError());
   return readSahCost(pt, cost);
 }
 
+// The device part of a refit over the render nodes' `dirty` bytes (pt::REFIT_*): the triangle records and slot boxes of the dirty nodes
+// (k_refit_tris), every node level by level, the planes, the SAH cost into refit.sahNow.  `flags` (an update): the node table and these
+// instance flags are uploaded first; NULL (the hide pass of a build): the build just uploaded both.
+int refitOnDevice(MiPt* pt, const std::vector<uint8_t>& dirty, const std::vector<uint8_t>* flags)
+{
+  if(flags)
+  {
+    HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * pt->hostNodes.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags->data(), flags->size(), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(pt->accel.refit.dirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
+  pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->accel.refit.dirty.ptr, pt->accel.refit.builtBox.ptr, pt->accel.bvhTris.ptr,
+                      pt->accel.refit.slotBox.ptr, uint32_t(pt->scene.numTris), nullptr);
+  if(int rc = refitPass(pt, uint32_t(pt->scene.bvh8NumNodes), pt->accel.refit.levels, pt->accel.refit.sahNow))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return MI_PT_OK;
+}
+
 // Resident mode is wanted of a build when it is enabled and the build can keep refit data (residentInForce: it then did)
-bool residentWanted(const MiPt* pt)
+bool residentWanted(const MiPt* pt) { return pt->accel.accelResident && pt->accel.accelMode != MI_PT_ACCEL_REBUILD && !pt->accel.keepsNoRefitData(pt->sw); }
+bool residentInForce(const MiPt* pt) { return pt->accel.residentTree && pt->accel.canRefit(); }
+
+// The phases of a build follow, in the order buildStructure and buildAccelerationUnguarded run them.  The render-node instances a build is made over, flattened on the host: `entryNode` the render nodes that contribute triangles, `triOffset`
+// where each one's triangles start (+ the total at the end).  `resident`: every render node that owns triangles, as if all were visible.
+struct FlatInstances
 {
-  return pt->accelResident && pt->accelMode != MI_PT_ACCEL_REBUILD && (pt->bvhBuilder & 1) == 0 && !pt->sw.hostCollapse;
-}
-bool residentInForce(const MiPt* pt)
-{
-  return pt->residentTree && pt->accelMode != MI_PT_ACCEL_REBUILD && !pt->refit.levels.empty() && pt->bvh8Nodes.ptr && pt->wide;
-}
-int buildAccelerationOver(MiPt* pt, bool resident);
-int buildAccelerationUnguarded(MiPt* pt)
-{
-  return buildAccelerationOver(pt, residentWanted(pt));
-}
-// `resident`: over every render node that owns triangles, as if all were visible; the hidden ones are then hidden by one refit pass
-int buildAccelerationOver(MiPt* pt, bool resident)
-{
-  pt->refit        = MiPt::RefitData{};
-  pt->residentTree = false;
-  pt->hiddenTris   = 0;
-  uint64_t  hiddenTris = 0;
-  const int numNodes = int(pt->hostNodes.size()), numPrims = int(pt->primTriangles.size());
-  std::vector<uint8_t>  flags = instanceFlags(pt);
   std::vector<uint32_t> triOffset;
   std::vector<int32_t>  entryNode;
-  uint64_t              totalTris = 0;
-  triOffset.push_back(0);
+  uint64_t              totalTris = 0, hiddenTris = 0;  // hiddenTris: of the hidden nodes among them (resident only)
+};
+int flattenInstances(const MiPt* pt, bool resident, FlatInstances& flat)
+{
+  const int numNodes = int(pt->hostNodes.size()), numPrims = int(pt->primTriangles.size());
+  flat.triOffset.push_back(0);
   for(int n = 0; n < numNodes; ++n)
   {
     const MiGltfRenderNode& rn = pt->hostNodes[size_t(n)];
@@ -865,43 +864,51 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     if(rn.renderPrimID < 0 || rn.renderPrimID >= numPrims || pt->primTriangles[size_t(rn.renderPrimID)] == 0)
       continue;
     if(hidden)
-      hiddenTris += pt->primTriangles[size_t(rn.renderPrimID)];
-    totalTris += pt->primTriangles[size_t(rn.renderPrimID)];
-    if(totalTris > 0x7fffffffull)
+      flat.hiddenTris += pt->primTriangles[size_t(rn.renderPrimID)];
+    flat.totalTris += pt->primTriangles[size_t(rn.renderPrimID)];
+    if(flat.totalTris > 0x7fffffffull)
       return fail(MI_PT_ERR_ARGUMENT, "more than 2^31 flattened triangles");
-    entryNode.push_back(n);
-    triOffset.push_back(uint32_t(totalTris));
+    flat.entryNode.push_back(n);
+    flat.triOffset.push_back(uint32_t(flat.totalTris));
   }
-  HIP_TRY(pt->nodes.upload(pt->hostNodes.data(), pt->hostNodes.size()));
-  HIP_TRY(pt->instFlags.upload(flags.data(), flags.size()));
-  pt->scene.nodes = pt->nodes.ptr;
+  return MI_PT_OK;
+}
 
-  // release the previous structure (an update), then build
-  pt->bvhNodes.release(); pt->bvhTris.release(); pt->bvh8Nodes.release();
-  pt->refitCapable = false;
-  if(pt->accelBuilds++ == pt->sw.failBuildAt && pt->sw.failBuildAt > 0)  // test hook (armed at mi_pt_create): this REbuild fails after the old structure is gone
-    return fail(MI_PT_ERR_HIP, "BVH build failed: MI_PT_DIAG_FAIL_BUILD");
-  {
-    DevBuf<uint32_t> dOffset;
-    DevBuf<int32_t>  dEntry;
-    HIP_TRY(dOffset.upload(triOffset.data(), triOffset.size()));
-    HIP_TRY(dEntry.upload(entryNode.data(), entryNode.size()));
-    pt::BvhBuildInput in{pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, dOffset.ptr, dEntry.ptr, int(entryNode.size()), uint32_t(totalTris)};
-    in.karrasTopology = (pt->bvhBuilder & 2) != 0;
-    // (accelBuilds counts this build already.)  The build of a switch to REFIT / AUTO makes the tree the updates then refit: it runs the scene
-    // build's passes, once, at a moment the caller chose.  The fallback and AUTO rebuilds of those modes happen during playback and run the
-    // update's passes like every other rebuild -- 16 passes would add ~160 ms to a 17-ms rebuild at 2.8 M triangles (RunSwitches::reinsertUpdate)
-    in.reinsertPasses = (pt->accelBuilds == 1 || pt->switchBuild) ? pt->sw.reinsert : pt->sw.reinsertUpdate;
-    in.reinsertRounds = pt->sw.reinsertRounds;
-    in.splitFactor    = pt->sw.splitFactor;
-    in.splitMaxDepth  = pt->sw.splitMaxDepth;
-    in.splitMinShare  = pt->sw.splitMinShare;
-    // The BVH2 walk leaves one stack entry per level: its tree is no taller than that stack (buildBvh rebuilds a taller one).  The 8-wide walk
-    // is bounded after the collapse, below.
-    pt->wide     = (pt->bvhBuilder & 1) == 0;
-    in.maxHeight = pt->wide ? 0 : pt::BVH_STACK_LDS + pt::BVH_STACK_PRIV;
-    pt::BvhBuildOutput bo;
-    std::string        err;
+// What a build holds on the device while it runs and releases when it is over (in the reverse of this order)
+struct TreeBuild
+{
+  DevBuf<uint32_t>   dOffset;
+  DevBuf<int32_t>    dEntry;
+  pt::BvhBuildOutput bo;
+  pt::Bvh8Output     b8;  // empty under the BVH2 walk and for a scene without triangles
+};
+// The tree over `flat`: Morton sort + PLOC -> BVH2 -> (default) 8-wide collapse, its arrays into pt->accel, its figures into the scene
+// descriptor and the statistics, the packet walk's planes.  The refit data stays in `t.b8` for keepRefitData.
+int buildTree(MiPt* pt, const FlatInstances& flat, TreeBuild& t)
+{
+  HIP_TRY(t.dOffset.upload(flat.triOffset.data(), flat.triOffset.size()));
+  HIP_TRY(t.dEntry.upload(flat.entryNode.data(), flat.entryNode.size()));
+  pt::BvhBuildInput in{pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, t.dOffset.ptr, t.dEntry.ptr, int(flat.entryNode.size()), uint32_t(flat.totalTris)};
+  in.karrasTopology = (pt->accel.bvhBuilder & 2) != 0;
+  // (accelBuilds counts this build already.)  The build of a switch to REFIT / AUTO makes the tree the updates then refit: it runs the scene
+  // build's passes, once, at a moment the caller chose.  The fallback and AUTO rebuilds of those modes happen during playback and run the
+  // update's passes like every other rebuild -- 16 passes would add ~160 ms to a 17-ms rebuild at 2.8 M triangles (RunSwitches::reinsertUpdate)
+  in.reinsertPasses = (pt->accel.accelBuilds == 1 || pt->accel.switchBuild) ? pt->sw.reinsert : pt->sw.reinsertUpdate;
+  in.reinsertRounds = pt->sw.reinsertRounds;
+  in.splitFactor    = pt->sw.splitFactor;
+  in.splitMaxDepth  = pt->sw.splitMaxDepth;
+  in.splitMinShare  = pt->sw.splitMinShare;
+  // The BVH2 walk leaves one stack entry per level: its tree is no taller than that stack (buildBvh rebuilds a taller one).  The 8-wide walk
+  // is bounded after the collapse, below.
+  pt->accel.wide = (pt->accel.bvhBuilder & 1) == 0;
+  in.maxHeight   = pt->accel.wide ? 0 : pt::BVH_STACK_LDS + pt::BVH_STACK_PRIV;
+  pt::Bvh8Options b8opt;
+  b8opt.sahCollapse = !pt->sw.collapseGreedy; b8opt.hostCollapse = pt->sw.hostCollapse;
+  b8opt.keepRefit   = pt->accel.accelMode != MI_PT_ACCEL_REBUILD;
+  std::string err;
+  // the BVH2 from `in` and, for the 8-wide walk, the tree collapsed from it
+  auto buildPair = [&]() -> int {
+    pt::BvhBuildOutput& bo = t.bo;
     if(!pt::buildBvh(in, bo, nullptr, err))
       return fail(MI_PT_ERR_HIP, "BVH build failed: " + err);
     pt->scene.bvhRoot = bo.root;
@@ -909,128 +916,200 @@ int buildAccelerationOver(MiPt* pt, bool resident)
     pt->scene.bvh8NumNodes = 0;
     pt->staticStats.bvhNodeCount     = bo.numNodes;
     pt->staticStats.bvhTriangleCount = bo.numTris;
-    pt->splitRefs                    = bo.numTris > bo.sceneTris;
+    pt->accel.splitRefs              = bo.numTris > bo.sceneTris;
     pt->staticStats.bvhNodeBytes     = 64;
     pt->staticStats.bvhTriangleBytes = sizeof(pt::DevTri);
     // the triangle rounds of the 8-wide walk pack (triangle index | owner lane << 26) into one word (pt_kernels.hip)
-    if(pt->wide && bo.numTris >= (1u << 26))
+    if(pt->accel.wide && bo.numTris >= (1u << 26))
       return fail(MI_PT_ERR_ARGUMENT, "scene has 2^26 or more triangles: beyond what the 8-wide BVH walk indexes (select the BVH2 walk, bvhBuilder bit 0)");
-    if(pt->wide && bo.numTris > 0)
-    {
-      pt::Bvh8Output b8;
-      pt::Bvh8Options b8opt;
-      b8opt.sahCollapse = !pt->sw.collapseGreedy; b8opt.hostCollapse = pt->sw.hostCollapse;
-      b8opt.keepRefit   = pt->accelMode != MI_PT_ACCEL_REBUILD;
-      pt->refitCapable  = !pt->sw.hostCollapse && bo.numNodes > 0;  // (a one-reference scene takes the host collapse: bvh8.hip)
-      if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
-        return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
-      // A node visit of the 8-wide walk pushes at most one group (the visited node's other hit inner children), and none at a node without inner
-      // children: a tree of L levels needs L - 1 stack slots at most.  One with more levels than the stack covers (LaneStack2 drops what it cannot
-      // hold) is collapsed again from a BVH2 of that height at most -- an 8-wide node spans at least one BVH2 level -- which buildBvh makes with the
-      // Morton-prefix topology or fails.
-      const uint32_t maxLevels = uint32_t(pt::BVH8_STACK_LDS + pt::BVH8_STACK_PRIV) + 1u;
-      if(b8.numLevels > maxLevels)
-      {
-        if(getenv("MI_PT_BUILD_TIMING"))
-          fprintf(stderr, "[mi_pt build] 8-wide tree of %u levels (limit %u): rebuilt from a BVH2 of bounded height\n", b8.numLevels, maxLevels);
-        in.karrasTopology = true;
-        in.maxHeight      = int(maxLevels);
-        b8                = pt::Bvh8Output();
-        if(!pt::buildBvh(in, bo, nullptr, err))
-          return fail(MI_PT_ERR_HIP, "BVH build failed: " + err);
-        if(!pt::buildBvh8(bo, b8, nullptr, err, b8opt))
-          return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
-        if(b8.numLevels > maxLevels)
-          return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: more levels than the walk's stack covers");
-      }
-      // the wide structure owns its own triangle order; the BVH2 arrays are no longer needed
-      bo.nodes.release();
-      bo.tris.release();
-      pt->bvhTris   = std::move(b8.tris);
-      pt->bvh8Nodes = std::move(b8.nodes);
-      // the refit data (the host collapse keeps none: its updates rebuild)
-      pt->refit.slotBox = std::move(b8.slotBox);
-      pt->refit.nodeBox = std::move(b8.nodeBox);
-      pt->scene.bvhRoot = 0;
-      pt->scene.bvh8NumNodes = int(b8.numNodes);
-      pt->staticStats.bvhNodeCount = b8.numNodes;
-      pt->staticStats.bvhNodeBytes = 80;
-      if(!pt->sw.noPlanes)  // A/B switch of the packet walk's float planes
-      {
-        HIP_TRY(pt->bvh8Planes.alloc(size_t(b8.numNodes) * 48));
-        pt::launchBvh8Planes(pt->bvh8Nodes.ptr, b8.numNodes, pt->bvh8Planes.ptr, nullptr);
-        HIP_TRY(hipGetLastError());
-      }
-      if(pt->refit.slotBox.ptr && pt->refit.nodeBox.ptr)
-      {
-        // the refit data: the boxes the build filed the references under stay as they are (REFIT_HOME), the SAH cost of the tree as built.
-        // The nodes are requantised once from the unions of those boxes (a BVH2 box may be looser than the union below it): the tree an
-        // update refits back to the build's pose is then this one, byte for byte.
-        HIP_TRY(pt->refit.builtBox.alloc(b8.numTris));
-        HIP_TRY(hipMemcpy(pt->refit.builtBox.ptr, pt->refit.slotBox.ptr, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
-        HIP_TRY(pt->refit.sah.alloc(b8.numNodes));
-        HIP_TRY(pt->refit.sahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
-        HIP_TRY(pt->refit.dirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
-        if(int rc = refitPass(pt, b8.numNodes, b8.levels, pt->refit.sahAtBuild))
-          return rc;
-        pt->refit.sahNow      = pt->refit.sahAtBuild;
-        pt->refit.levels = std::move(b8.levels);
-        pt->builtNodes  = pt->hostNodes;
-        pt->primDirty.assign(pt->primTriangles.size(), 0);
-        pt->primDeformed.assign(pt->primTriangles.size(), 0);
-        pt->residentTree = resident;
-        pt->hiddenTris   = resident ? hiddenTris : 0;
-      }
-      else
-      {
-        pt->refit.slotBox.release();
-        pt->refit.nodeBox.release();
-      }
-    }
-    else
-    {
-      pt->bvhNodes = std::move(bo.nodes);
-      pt->bvhTris  = std::move(bo.tris);
-    }
-  }
-  if(resident && !pt->residentTree && hiddenTris > 0)  // no refit data came of it (a one-reference scene: bvh8.hip), so nothing could hide them
+    if(!pt->accel.wide || bo.numTris == 0)
+      return MI_PT_OK;
+    pt->accel.refitCapable = !pt->sw.hostCollapse && bo.numNodes > 0;  // (a one-reference scene takes the host collapse: bvh8.hip)
+    if(!pt::buildBvh8(bo, t.b8, nullptr, err, b8opt))
+      return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: " + err);
+    return MI_PT_OK;
+  };
+  if(int rc = buildPair())
+    return rc;
+  // A node visit of the 8-wide walk pushes at most one group (the visited node's other hit inner children), and none at a node without inner
+  // children: a tree of L levels needs L - 1 stack slots at most.  One with more levels than the stack covers (LaneStack2 drops what it cannot
+  // hold) is collapsed again from a BVH2 of that height at most -- an 8-wide node spans at least one BVH2 level -- which buildBvh makes with the
+  // Morton-prefix topology or fails.  (The split references, and so the figures above, do not depend on the topology.)
+  const uint32_t maxLevels = uint32_t(pt::BVH8_STACK_LDS + pt::BVH8_STACK_PRIV) + 1u;
+  if(t.b8.numLevels > maxLevels)
   {
-    --pt->accelBuilds;
-    return buildAccelerationOver(pt, false);
+    if(buildTiming())
+      fprintf(stderr, "[mi_pt build] 8-wide tree of %u levels (limit %u): rebuilt from a BVH2 of bounded height\n", t.b8.numLevels, maxLevels);
+    in.karrasTopology = true;
+    in.maxHeight      = int(maxLevels);
+    t.b8              = pt::Bvh8Output();
+    if(int rc = buildPair())
+      return rc;
+    if(t.b8.numLevels > maxLevels)
+      return fail(MI_PT_ERR_HIP, "BVH8 collapse failed: more levels than the walk's stack covers");
   }
-  publishAcceleration(pt);
+  if(!pt->accel.wide || t.bo.numTris == 0)
+  {
+    pt->accel.bvhNodes = std::move(t.bo.nodes);
+    pt->accel.bvhTris  = std::move(t.bo.tris);
+    return MI_PT_OK;
+  }
+  // the wide structure owns its own triangle order; the BVH2 arrays are no longer needed
+  t.bo.nodes.release();
+  t.bo.tris.release();
+  pt->accel.bvhTris   = std::move(t.b8.tris);
+  pt->accel.bvh8Nodes = std::move(t.b8.nodes);
+  pt->scene.bvhRoot = 0;
+  pt->scene.bvh8NumNodes = int(t.b8.numNodes);
+  pt->staticStats.bvhNodeCount = t.b8.numNodes;
+  pt->staticStats.bvhNodeBytes = 80;
+  if(!pt->sw.noPlanes)  // A/B switch of the packet walk's float planes
+  {
+    HIP_TRY(pt->accel.bvh8Planes.alloc(size_t(t.b8.numNodes) * 48));
+    pt::launchBvh8Planes(pt->accel.bvh8Nodes.ptr, t.b8.numNodes, pt->accel.bvh8Planes.ptr, nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return MI_PT_OK;
+}
+
+// The refit data of the 8-wide tree just built, where its collapse returned any (the host collapse keeps none: its updates rebuild)
+int keepRefitData(MiPt* pt, pt::Bvh8Output& b8, bool resident, uint64_t hiddenTris)
+{
+  pt->accel.refit.slotBox = std::move(b8.slotBox);
+  pt->accel.refit.nodeBox = std::move(b8.nodeBox);
+  if(!pt->accel.refit.slotBox.ptr || !pt->accel.refit.nodeBox.ptr)
+  {
+    pt->accel.refit.slotBox.release();
+    pt->accel.refit.nodeBox.release();
+    return MI_PT_OK;
+  }
+  // the boxes the build filed the references under stay as they are (REFIT_HOME), the SAH cost of the tree as built.
+  // The nodes are requantised once from the unions of those boxes (a BVH2 box may be looser than the union below it): the tree an
+  // update refits back to the build's pose is then this one, byte for byte.
+  HIP_TRY(pt->accel.refit.builtBox.alloc(b8.numTris));
+  HIP_TRY(hipMemcpy(pt->accel.refit.builtBox.ptr, pt->accel.refit.slotBox.ptr, sizeof(pt::RefitBox) * size_t(b8.numTris), hipMemcpyDeviceToDevice));
+  HIP_TRY(pt->accel.refit.sah.alloc(b8.numNodes));
+  HIP_TRY(pt->accel.refit.sahPartial.alloc(pt::REFIT_SAH_PARTIALS + 1));
+  HIP_TRY(pt->accel.refit.dirty.alloc(std::max<size_t>(pt->hostNodes.size(), 1)));
+  if(int rc = refitPass(pt, b8.numNodes, b8.levels, pt->accel.refit.sahAtBuild))
+    return rc;
+  pt->accel.refit.sahNow = pt->accel.refit.sahAtBuild;
+  pt->accel.refit.levels = std::move(b8.levels);
+  pt->accel.builtNodes   = pt->hostNodes;
+  pt->accel.primDirty.assign(pt->primTriangles.size(), 0);
+  pt->accel.primDeformed.assign(pt->primTriangles.size(), 0);
+  pt->accel.residentTree = resident;
+  pt->accel.hiddenTris   = resident ? hiddenTris : 0;
+  return MI_PT_OK;
+}
+
+// Every alpha record into the allocated pt->accel.alphaTris, as a build makes them (patchTriangleData: for a scene that had none)
+int makeAlphaRecords(MiPt* pt)
+{
+  pt::launchBuildAlphaRecords(pt->scene, uint32_t(pt->scene.numTris), pt->accel.alphaTris.ptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  pt->scene.alphaTris = pt->accel.alphaTris.ptr;
+  return MI_PT_OK;
+}
+// The per-triangle shade and alpha records of the published structure
+int makeTriangleRecords(MiPt* pt)
+{
   pt::DevScene& S = pt->scene;
   if(S.numTris > 0)
   {
-    HIP_TRY(pt->shadeTris.alloc(size_t(S.numTris)));
-    pt::launchBuildShadeRecords(S, uint32_t(S.numTris), pt->shadeTris.ptr, nullptr);
+    HIP_TRY(pt->accel.shadeTris.alloc(size_t(S.numTris)));
+    pt::launchBuildShadeRecords(S, uint32_t(S.numTris), pt->accel.shadeTris.ptr, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    S.shadeTris = pt->shadeTris.ptr;
+    S.shadeTris = pt->accel.shadeTris.ptr;
   }
   if(pt->hasAlpha && S.numTris > 0)
   {
-    HIP_TRY(pt->alphaTris.alloc(size_t(S.numTris)));
-    pt::launchBuildAlphaRecords(S, uint32_t(S.numTris), pt->alphaTris.ptr, nullptr);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(pt->accel.alphaTris.alloc(size_t(S.numTris)));
+    if(int rc = makeAlphaRecords(pt))
+      return rc;
     HIP_TRY(hipDeviceSynchronize());
-    S.alphaTris = pt->alphaTris.ptr;
   }
-  if(pt->residentTree && pt->hiddenTris > 0)
+  return MI_PT_OK;
+}
+
+// The structure over the current node table, up to its refit data: the previous one is released on the way.
+// `resident`: over every render node that owns triangles, as if all were visible; `hiddenTris`: the triangles of the hidden ones among them.
+int buildStructure(MiPt* pt, bool resident, uint64_t& hiddenTris)
+{
+  pt->accel.refit        = MiPt::Accel::RefitData{};
+  pt->accel.residentTree = false;
+  pt->accel.hiddenTris   = 0;
+  const std::vector<uint8_t> flags = instanceFlags(pt);
+  FlatInstances              flat;
+  if(int rc = flattenInstances(pt, resident, flat))
+    return rc;
+  hiddenTris = flat.hiddenTris;
+  HIP_TRY(pt->nodes.upload(pt->hostNodes.data(), pt->hostNodes.size()));
+  HIP_TRY(pt->instFlags.upload(flags.data(), flags.size()));
+  pt->scene.nodes = pt->nodes.ptr;
+
+  // release the previous structure (an update), then build
+  pt->accel.releaseTree();
+  pt->accel.refitCapable = false;
+  if(pt->accel.accelBuilds++ == pt->sw.failBuildAt && pt->sw.failBuildAt > 0)  // test hook (armed at mi_pt_create): this REbuild fails after the old structure is gone
+    return fail(MI_PT_ERR_HIP, "BVH build failed: MI_PT_DIAG_FAIL_BUILD");
+  TreeBuild t;
+  if(int rc = buildTree(pt, flat, t))
+    return rc;
+  return pt->accel.wide && pt->scene.numTris > 0 ? keepRefitData(pt, t.b8, resident, flat.hiddenTris) : MI_PT_OK;
+}
+
+// Flattens the visible render-node instances to world-space triangles and builds the acceleration structure over them on the
+// device: Morton sort + PLOC -> BVH2 -> (default) 8-wide collapse, then the per-triangle shading / alpha records.  Everything it
+// needs is resident (geometry pool, materials) or kept on the host in MiPt (node matrices, visibility), so it serves the scene
+// build (mi_pt_create; reference: SceneRtx BLAS + TLAS build, src/gltf_scene_rtx.cpp:173-385) and the transform / visibility
+// updates of animated scenes (mi_pt_update_render_nodes; reference: TLAS update, src/gltf_scene_transform_vk.cpp:534-639) alike.
+// In resident mode (residentWanted) the structure is built over the hidden nodes too, which one refit pass then hides.
+int buildAccelerationUnguarded(MiPt* pt)
+{
+  const bool resident   = residentWanted(pt);
+  uint64_t   hiddenTris = 0;
+  if(int rc = buildStructure(pt, resident, hiddenTris))
+    return rc;
+  if(resident && !pt->accel.residentTree && hiddenTris > 0)
+  {
+    // no refit data came of it (a one-reference scene: bvh8.hip), so nothing could hide them: over the visible nodes, as the same build
+    --pt->accel.accelBuilds;
+    if(int rc = buildStructure(pt, false, hiddenTris))
+      return rc;
+  }
+  publishAcceleration(pt);
+  if(int rc = makeTriangleRecords(pt))
+    return rc;
+  if(pt->accel.residentTree && pt->accel.hiddenTris > 0)
   {
     // the hide pass: the records above were made from the all-visible tree (they hold no geometry); sahAtBuild stays the all-visible cost
     std::vector<uint8_t> dirty(std::max<size_t>(pt->hostNodes.size(), 1), pt::REFIT_CLEAN);
     for(size_t n = 0; n < pt->hostNodes.size(); ++n)
       if(!pt->hostVisible[n])
         dirty[n] = pt::REFIT_HIDDEN;
-    HIP_TRY(hipMemcpy(pt->refit.dirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refit.dirty.ptr, pt->refit.builtBox.ptr, pt->bvhTris.ptr, pt->refit.slotBox.ptr,
-                        uint32_t(S.numTris), nullptr);
-    if(int rc = refitPass(pt, uint32_t(S.bvh8NumNodes), pt->refit.levels, pt->refit.sahNow))
-      return rc;
-    HIP_TRY(hipDeviceSynchronize());
+    return refitOnDevice(pt, dirty, nullptr);
   }
   return MI_PT_OK;
+}
+
+// A failed (re)build must not leave the scene descriptor pointing at freed or half-built arrays: mi_pt_update_render_nodes runs
+// this once per animated frame, and the next mi_pt_render_frame would walk them.  On any error the instance falls back to an
+// EMPTY structure (frames render the environment only) and the error is returned to the caller.
+int buildAcceleration(MiPt* pt)
+{
+  const auto t0 = BuildClock::now();
+  const int  rc = buildAccelerationUnguarded(pt);
+  if(buildTiming() && pt->accel.accelBuilds > 1)  // (the first build's phases are printed by mi_pt_create)
+  {
+    (void)hipDeviceSynchronize();
+    printBuildTiming("rebuild", t0);
+  }
+  pt->accel.lastUpdate = MI_PT_ACCEL_LAST_BUILD;
+  if(rc != MI_PT_OK)
+    dropAcceleration(pt);
+  return rc;
 }
 
 // The refit of an update: `moved` per render node = its matrices changed.  The triangle records and slot boxes of what moved or deformed
@@ -1046,7 +1125,7 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
   const size_t         numNodes = pt->hostNodes.size(), numPrims = pt->primTriangles.size();
   std::vector<uint8_t> dirty(std::max<size_t>(numNodes, 1), pt::REFIT_CLEAN);
   std::vector<uint8_t> visKept;
-  if(!visWas && pt->residentTree && !pt->hostVisible.empty())  // (a deformation update: what is hidden in the resident tree stays hidden)
+  if(!visWas && pt->accel.residentTree && !pt->hostVisible.empty())  // (a deformation update: what is hidden in the resident tree stays hidden)
   {
     visKept = pt->hostVisible;
     visWas  = &visKept;
@@ -1068,48 +1147,37 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
       }
       shown = !(*visWas)[n];
     }
-    if(!shown && !moved[n] && !(ownsPrim && pt->primDirty[size_t(rn.renderPrimID)]))
+    if(!shown && !moved[n] && !(ownsPrim && pt->accel.primDirty[size_t(rn.renderPrimID)]))
       continue;
-    const bool home = memcmp(rn.objectToWorld, pt->builtNodes[n].objectToWorld, sizeof(float) * 32) == 0 && !(ownsPrim && pt->primDeformed[size_t(rn.renderPrimID)]);
+    const bool home = memcmp(rn.objectToWorld, pt->accel.builtNodes[n].objectToWorld, sizeof(float) * 32) == 0 && !(ownsPrim && pt->accel.primDeformed[size_t(rn.renderPrimID)]);
     dirty[n]        = home ? pt::REFIT_HOME : pt::REFIT_MOVED;
     if(ownsPrim && (pt->hostVisible.empty() || pt->hostVisible[n]))
       movedTris += pt->primTriangles[size_t(rn.renderPrimID)];
   }
   const std::vector<uint8_t> flags = instanceFlags(pt);
-  const int                  rc    = [&]() -> int {
-    HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * numNodes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->refit.dirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchRefitTris(pt->nodes.ptr, pt->prims.ptr, pt->instFlags.ptr, pt->refit.dirty.ptr, pt->refit.builtBox.ptr, pt->bvhTris.ptr, pt->refit.slotBox.ptr,
-                        uint32_t(pt->scene.numTris), nullptr);
-    if(int e = refitPass(pt, uint32_t(pt->scene.bvh8NumNodes), pt->refit.levels, pt->refit.sahNow))
-      return e;
-    HIP_TRY(hipDeviceSynchronize());
-    return MI_PT_OK;
-  }();
-  if(rc != MI_PT_OK)
+  if(int rc = refitOnDevice(pt, dirty, &flags))
   {
     dropAcceleration(pt);
     return rc;
   }
-  std::fill(pt->primDirty.begin(), pt->primDirty.end(), uint8_t(0));
+  std::fill(pt->accel.primDirty.begin(), pt->accel.primDirty.end(), uint8_t(0));
   pt->sceneDevDirty = true;
   printBuildTiming("refit", t0);
-  if(pt->accelMode == MI_PT_ACCEL_AUTO && pt->refit.sahNow > double(pt->accelRatio) * pt->refit.sahAtBuild)
+  if(pt->accel.accelMode == MI_PT_ACCEL_AUTO && pt->accel.refit.sahNow > double(pt->accel.accelRatio) * pt->accel.refit.sahAtBuild)
     return buildAcceleration(pt);
   if(visWas)
   {
-    pt->hiddenTris = 0;
+    pt->accel.hiddenTris = 0;
     for(size_t n = 0; n < numNodes; ++n)
     {
       const int prim = pt->hostNodes[n].renderPrimID;
       if(!pt->hostVisible.empty() && !pt->hostVisible[n] && prim >= 0 && size_t(prim) < numPrims)
-        pt->hiddenTris += pt->primTriangles[size_t(prim)];
+        pt->accel.hiddenTris += pt->primTriangles[size_t(prim)];
     }
   }
-  ++pt->accelRefits;
-  pt->lastUpdate     = MI_PT_ACCEL_LAST_REFIT;
-  pt->trianglesMoved = movedTris;
+  ++pt->accel.accelRefits;
+  pt->accel.lastUpdate     = MI_PT_ACCEL_LAST_REFIT;
+  pt->accel.trianglesMoved = movedTris;
   return MI_PT_OK;
 }
 
@@ -1117,9 +1185,17 @@ int refitAcceleration(MiPt* pt, const std::vector<uint8_t>& moved, const std::ve
 // keeps the topology (`sameTopology`: primitives, materials and visibility unchanged), a full build otherwise.
 int updateAcceleration(MiPt* pt, bool sameTopology, const std::vector<uint8_t>& moved)
 {
-  if(pt->accelMode != MI_PT_ACCEL_REBUILD && sameTopology && !pt->refit.levels.empty() && pt->bvh8Nodes.ptr && pt->wide)
+  if(sameTopology && pt->accel.canRefit())
     return refitAcceleration(pt, moved);
   return buildAcceleration(pt);
+}
+// The build of a switch of the mode or of resident mode: the tree the updates then refit, made with the scene build's passes (buildTree)
+int buildForSwitch(MiPt* pt)
+{
+  pt->accel.switchBuild = true;
+  const int rc          = buildAcceleration(pt);
+  pt->accel.switchBuild = false;
+  return rc;
 }
 
 // What makeAlphaRecord (pt_shading.h) reads of a material and its base / diffuse texture info, as it reads it: two materials with equal
@@ -1265,14 +1341,14 @@ int patchTriangleData(MiPt* pt, const std::vector<uint8_t>& flags, std::vector<u
 {
   HIP_TRY(hipMemcpy(pt->instFlags.ptr, flags.data(), flags.size(), hipMemcpyHostToDevice));
   pt::DevScene& S          = pt->scene;
-  const bool    hadRecords = pt->alphaTris.ptr != nullptr;
+  const bool    hadRecords = pt->accel.alphaTris.ptr != nullptr;
   if(!pt->hasAlpha)
   {
-    pt->alphaTris.release();
+    pt->accel.alphaTris.release();
     S.alphaTris = nullptr;
   }
   else if(!hadRecords)
-    HIP_TRY(pt->alphaTris.alloc(size_t(S.numTris)));
+    HIP_TRY(pt->accel.alphaTris.alloc(size_t(S.numTris)));
   bool anyDirty = false;
   for(uint8_t& d : dirty)
   {
@@ -1285,16 +1361,13 @@ int patchTriangleData(MiPt* pt, const std::vector<uint8_t>& flags, std::vector<u
     if(pt->matDirty.count != dirty.size())
       HIP_TRY(pt->matDirty.alloc(dirty.size()));
     HIP_TRY(hipMemcpy(pt->matDirty.ptr, dirty.data(), dirty.size(), hipMemcpyHostToDevice));
-    pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->bvhTris.ptr, hadRecords ? pt->alphaTris.ptr : nullptr, pt->shadeTris.ptr,
+    pt::launchPatchMaterials(S, pt->instFlags.ptr, pt->matDirty.ptr, pt->accel.bvhTris.ptr, hadRecords ? pt->accel.alphaTris.ptr : nullptr, pt->accel.shadeTris.ptr,
                              uint32_t(S.numTris), nullptr);
     HIP_TRY(hipGetLastError());
   }
   if(pt->hasAlpha && !hadRecords)  // the scene had no alpha records: all of them, as a build makes them
-  {
-    pt::launchBuildAlphaRecords(S, uint32_t(S.numTris), pt->alphaTris.ptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    S.alphaTris = pt->alphaTris.ptr;
-  }
+    if(int rc = makeAlphaRecords(pt))
+      return rc;
   HIP_TRY(hipDeviceSynchronize());
   pt->sceneDevDirty = true;
   return MI_PT_OK;
@@ -1339,23 +1412,23 @@ int updateRenderNodesResident(MiPt* pt, const MiGltfRenderNode* renderNodes, int
   const bool                 hadTransmissive = pt->hasTransmissive, wasSimple = pt->simpleMaterials;
   const std::vector<uint8_t> flagsWas = matChanged ? instanceFlags(pt) : std::vector<uint8_t>();
   keepNodeTable(pt, renderNodes, numRenderNodes, renderNodeVisible);
-  if(primChanged || (transmissiveChanged && pt->splitRefs))
+  if(primChanged || (transmissiveChanged && pt->accel.splitRefs))
   {
     if(int rc = buildAcceleration(pt))
       return rc;
     return followSummaries(pt, hadTransmissive, wasSimple);
   }
   bool anyPrimDirty = false;
-  for(uint8_t d : pt->primDirty)
+  for(uint8_t d : pt->accel.primDirty)
     anyPrimDirty |= d != 0;
   if(visChanged || anyMoved || anyPrimDirty || !matChanged)  // (an update that changes nothing refits, as it does outside resident mode)
   {
     if(int rc = refitAcceleration(pt, moved, &visWas))
       return rc;
-    if(pt->lastUpdate == MI_PT_ACCEL_LAST_BUILD)  // AUTO's bound: the build baked the materials
+    if(pt->accel.lastUpdate == MI_PT_ACCEL_LAST_BUILD)  // AUTO's bound: the build baked the materials
       return followSummaries(pt, hadTransmissive, wasSimple);
     if(visChanged)
-      ++pt->visibilityRefits;
+      ++pt->accel.visibilityRefits;
   }
   if(!matChanged)
     return MI_PT_OK;
@@ -1367,8 +1440,8 @@ int updateRenderNodesResident(MiPt* pt, const MiGltfRenderNode* renderNodes, int
   HIP_TRY(hipMemcpy(pt->nodes.ptr, pt->hostNodes.data(), sizeof(MiGltfRenderNode) * nn, hipMemcpyHostToDevice));
   if(int rc = patchTriangleData(pt, flags, matDirty))
     return rc;
-  ++pt->materialPatches;
-  pt->lastUpdate = MI_PT_ACCEL_LAST_REFIT;
+  ++pt->accel.materialPatches;
+  pt->accel.lastUpdate = MI_PT_ACCEL_LAST_REFIT;
   return followSummaries(pt, hadTransmissive, wasSimple);
 }
 
@@ -1551,7 +1624,7 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
     const MiPtRenderPrimitive& rp = sd->renderPrimitives[i];
     pt->primTriangles[size_t(i)]  = (rp.positions && rp.indices) ? rp.triangleCount : 0u;
   }
-  pt->bvhBuilder = options ? options->bvhBuilder : 0;
+  pt->accel.bvhBuilder = options ? options->bvhBuilder : 0;
 
   // ---- textures: one RGBA8 pool with all mip chains -----------------------------------------------------------------------
   {
@@ -1754,7 +1827,7 @@ int mi_pt_update_materials(MiPt* pt, const MiGltfShadeMaterial* materials, int n
   const std::vector<uint8_t> flags = instanceFlags(pt);
   // ---- what the resident structure cannot take in place is rebuilt: the BVH2 walk (no patch path), and a transmissive bit that changes
   // while the tree holds pre-split references (triangles of transmissive instances keep ONE reference: bvh_build.hip, k_split_refs)
-  if((anyAlpha || anyFlags) && pt->scene.numTris > 0 && (!pt->wide || (transmissiveChanged && pt->splitRefs)))
+  if((anyAlpha || anyFlags) && pt->scene.numTris > 0 && (!pt->accel.wide || (transmissiveChanged && pt->accel.splitRefs)))
   {
     if(int rc = buildAcceleration(pt))
       return rc;
@@ -1957,8 +2030,8 @@ int mi_pt_update_deformation(MiPt* pt, const float* jointMatrices, const float* 
   printBuildTiming("deform", t0);
   pt->vm.poseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
   for(int id : pt->deform.primIDs)  // (what the next acceleration update refits; sized by a build that kept refit data)
-    if(size_t(id) < pt->primDirty.size())
-      pt->primDirty[size_t(id)] = pt->primDeformed[size_t(id)] = 1;
+    if(size_t(id) < pt->accel.primDirty.size())
+      pt->accel.primDirty[size_t(id)] = pt->accel.primDeformed[size_t(id)] = 1;
   if(flags & MI_PT_DEFORM_DEFER_BUILD)
     return MI_PT_OK;
   return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
@@ -2179,8 +2252,8 @@ static int updateVertices(MiPt* pt, const MiPtVertexUpdate* updates, int numUpda
     return MI_PT_OK;
   pt->vm.poseDirty = true;  // (vertex motion: the next rendered pose is followed by a snapshot of the positions)
   for(int k = 0; k < numUpdates; ++k)  // (what the next acceleration update refits; sized by a build that kept refit data)
-    if(size_t(updates[k].renderPrimID) < pt->primDirty.size())
-      pt->primDirty[size_t(updates[k].renderPrimID)] = pt->primDeformed[size_t(updates[k].renderPrimID)] = 1;
+    if(size_t(updates[k].renderPrimID) < pt->accel.primDirty.size())
+      pt->accel.primDirty[size_t(updates[k].renderPrimID)] = pt->accel.primDeformed[size_t(updates[k].renderPrimID)] = 1;
   if(flags & MI_PT_DEFORM_DEFER_BUILD)
     return MI_PT_OK;
   return updateAcceleration(pt, true, std::vector<uint8_t>(pt->hostNodes.size(), 0));
@@ -2583,19 +2656,16 @@ int mi_pt_set_accel_update(MiPt* pt, int mode, float rebuildCostRatio)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_update: the rebuild cost ratio must be finite and at least 1");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still walk the structure
-  pt->accelMode  = mode;
-  pt->accelRatio = rebuildCostRatio;
+  pt->accel.accelMode  = mode;
+  pt->accel.accelRatio = rebuildCostRatio;
   if(mode == MI_PT_ACCEL_REBUILD)
   {
-    pt->refit = MiPt::RefitData{};
+    pt->accel.refit = MiPt::Accel::RefitData{};
     return MI_PT_OK;
   }
-  if(!pt->refit.levels.empty() || !pt->refitCapable)
+  if(!pt->accel.refit.levels.empty() || !pt->accel.refitCapable)
     return MI_PT_OK;  // (refit data held already, or the structure can never keep any -- BVH2 walk, host collapse, empty or one-reference scene: no build)
-  pt->switchBuild = true;
-  const int rc    = buildAcceleration(pt);
-  pt->switchBuild = false;
-  return rc;
+  return buildForSwitch(pt);
 }
 
 int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* out)
@@ -2603,15 +2673,15 @@ int mi_pt_get_accel_info(MiPt* pt, MiPtAccelInfo* out)
   if(!pt || !out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_accel_info: null argument");
   memset(out, 0, sizeof(*out));
-  out->mode             = pt->accelMode;
-  out->lastUpdate       = pt->lastUpdate;
-  out->rebuildCostRatio = pt->accelRatio;
-  out->builds           = uint64_t(std::max(pt->accelBuilds, 0));
-  out->refits           = pt->accelRefits;
-  out->sahCostAtBuild   = pt->refit.sahAtBuild;
-  out->sahCost          = pt->refit.sahNow;
-  out->trianglesMoved   = pt->trianglesMoved;
-  out->refitBytes       = pt->refit.bytes();
+  out->mode             = pt->accel.accelMode;
+  out->lastUpdate       = pt->accel.lastUpdate;
+  out->rebuildCostRatio = pt->accel.accelRatio;
+  out->builds           = uint64_t(std::max(pt->accel.accelBuilds, 0));
+  out->refits           = pt->accel.accelRefits;
+  out->sahCostAtBuild   = pt->accel.refit.sahAtBuild;
+  out->sahCost          = pt->accel.refit.sahNow;
+  out->trianglesMoved   = pt->accel.trianglesMoved;
+  out->refitBytes       = pt->accel.refit.bytes();
   return MI_PT_OK;
 }
 
@@ -2622,15 +2692,12 @@ int mi_pt_set_accel_resident(MiPt* pt, int enable)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_accel_resident: null instance");
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());  // frames in flight still walk the structure
-  pt->accelResident = enable != 0;
+  pt->accel.accelResident = enable != 0;
   // the tree the updates then refit: built once, here, when the request comes into force or leaves it (inert under REBUILD, the BVH2 walk
   // and the host collapse: their updates build anyway)
-  if(residentWanted(pt) == pt->residentTree || pt->accelMode == MI_PT_ACCEL_REBUILD || (pt->bvhBuilder & 1) != 0 || pt->sw.hostCollapse)
+  if(residentWanted(pt) == pt->accel.residentTree || pt->accel.accelMode == MI_PT_ACCEL_REBUILD || pt->accel.keepsNoRefitData(pt->sw))
     return MI_PT_OK;
-  pt->switchBuild = true;
-  const int rc    = buildAcceleration(pt);
-  pt->switchBuild = false;
-  return rc;
+  return buildForSwitch(pt);
 }
 
 int mi_pt_get_accel_resident_info(MiPt* pt, MiPtAccelResidentInfo* out)
@@ -2639,12 +2706,12 @@ int mi_pt_get_accel_resident_info(MiPt* pt, MiPtAccelResidentInfo* out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_accel_resident_info: null argument");
   memset(out, 0, sizeof(*out));
   const bool inForce     = residentInForce(pt);
-  out->enabled           = pt->accelResident ? 1 : 0;
+  out->enabled           = pt->accel.accelResident ? 1 : 0;
   out->inForce           = inForce ? 1 : 0;
   out->residentTriangles = inForce ? uint64_t(std::max(pt->scene.numTris, 0)) : 0;
-  out->hiddenTriangles   = inForce ? pt->hiddenTris : 0;
-  out->visibilityRefits  = pt->visibilityRefits;
-  out->materialPatches   = pt->materialPatches;
+  out->hiddenTriangles   = inForce ? pt->accel.hiddenTris : 0;
+  out->visibilityRefits  = pt->accel.visibilityRefits;
+  out->materialPatches   = pt->accel.materialPatches;
   return MI_PT_OK;
 }
 
@@ -2926,7 +2993,7 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     c.hasAlphaClosest = false;
   c.hasTransmissive  = pt->hasTransmissive;
   c.simpleMaterials  = pt->simpleMaterials;
-  c.wide             = pt->wide;
+  c.wide             = pt->accel.wide;
   c.collectCounters  = pt->collectCounters;
   c.shadowDeposit    = pt->sw.shadowDeposit;
   {
@@ -3258,7 +3325,7 @@ QueryCall queryCallOf(const char* who, const MiPtQueryOptions* o)
 }
 int failQuery(const QueryCall& c, int code, const std::string& what) { return fail(code, std::string(c.who) + ": " + what); }
 // An alpha-aware walk reads the alpha record of every triangle without INST_FORCE_OPAQUE / INST_ALPHA_PASSES.  Such a triangle sets hasAlphaTest,
-// hence hasAlpha, under which the build and the material patch keep the records (buildAccelerationOver, patchTriangleData): checked, not assumed.
+// hence hasAlpha, under which the build and the material patch keep the records (makeTriangleRecords, patchTriangleData): checked, not assumed.
 bool queryAlphaRecordsMissing(const MiPt* pt, const pt::QueryRules& rules)
 {
   return rules.alpha != MI_PT_QUERY_ALPHA_OPAQUE && pt->hasAlphaTest && pt->scene.numTris > 0 && !pt->scene.alphaTris;
@@ -3288,7 +3355,7 @@ int queryHostRays(MiPt* pt, const QueryCall& c, const MiPtRay* hostRays, int num
   if(int rc = queryStaging(pt, size_t(numRays), numHits))
     return rc;
   HIP_TRY(hipMemcpy(pt->queryRays.ptr, hostRays, size_t(numRays) * sizeof(MiPtRay), hipMemcpyHostToDevice));
-  pt::launchQueryRaysEx(pt->scene, pt->wide, c.any, c.rules, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
+  pt::launchQueryRaysEx(pt->scene, pt->accel.wide, c.any, c.rules, pt->queryRays.ptr, uint32_t(numRays), pt->queryHits.ptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
   return MI_PT_OK;
@@ -3305,7 +3372,7 @@ int queryDeviceRays(MiPt* pt, const QueryCall& c, const void* deviceRays, int nu
   if(numRays == 0)
     return MI_PT_OK;
   HIP_TRY(hipSetDevice(pt->device));
-  pt::launchQueryRaysEx(pt->scene, pt->wide, c.any, c.rules, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays), static_cast<MiPtRayHit*>(deviceHits),
+  pt::launchQueryRaysEx(pt->scene, pt->accel.wide, c.any, c.rules, static_cast<const MiPtRay*>(deviceRays), uint32_t(numRays), static_cast<MiPtRayHit*>(deviceHits),
                         reinterpret_cast<hipStream_t>(hipStream));
   HIP_TRY(hipGetLastError());
   return MI_PT_OK;
@@ -3342,7 +3409,7 @@ int queryPixels(MiPt* pt, const QueryCall& c, const float* pixelXY, int numPixel
   fc.frameInfo = pt->frameInfo;
   fc.width     = pt->width;
   fc.height    = pt->height;
-  pt::launchPickRaysEx(pt->scene, fc, pt->wide, c.rules, xy, scratch ? pt->queryRays.ptr : nullptr, uint32_t(numPixels), pt->queryHits.ptr, nullptr);
+  pt::launchPickRaysEx(pt->scene, fc, pt->accel.wide, c.rules, xy, scratch ? pt->queryRays.ptr : nullptr, uint32_t(numPixels), pt->queryHits.ptr, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(hostHits, pt->queryHits.ptr, numHits * sizeof(MiPtRayHit), hipMemcpyDeviceToHost));
   return MI_PT_OK;
@@ -3795,9 +3862,8 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
   // The feature groups sum themselves (MiPt::*::bytes()); every other buffer is named here.  Four small ones are in neither total, as they
   // never were: matDirty, skyPre, tmHistogram and tmAutoState.  Counting them is a change of what the totals report, not of this bookkeeping.
   const uint64_t scene = pt->materials.bytes() + pt->texInfos.bytes() + pt->nodes.bytes() + pt->prims.bytes() + pt->lights.bytes() + pt->textures.bytes() + pt->texels.bytes() + pt->texQuads.bytes()
-                         + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->alphaTris.bytes()
-                         + pt->shadeTris.bytes() + pt->texRefs.bytes() + pt->coreTex.bytes() + pt->bvh8Planes.bytes() + pt->deform.bytes() + pt->refit.bytes() + pt->vm.bytes()
-                         + pt->vu.bytes() + pt->tuTables.bytes() + pt->bvhNodes.bytes() + pt->bvh8Nodes.bytes() + pt->bvhTris.bytes();
+                         + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->texRefs.bytes()
+                         + pt->coreTex.bytes() + pt->deform.bytes() + pt->vm.bytes() + pt->vu.bytes() + pt->tuTables.bytes() + pt->accel.bytes();
   const uint64_t pathState = pt->pathArrays.bytes() + pt->optThroughput.bytes() + pt->optMisc.bytes() + pt->optMedium.bytes() + pt->optPixelSum.bytes() + pt->optGuides.bytes()
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
