@@ -6,46 +6,11 @@ import numpy as np
 import pytest
 
 import parity_util as pu
+from denoise_ref import _atrous_numpy, _svgf_numpy
 from vk_gltf_renderer_amd import _capi as capi
 from vk_gltf_renderer_amd import pathtracer as ptmod
 
 pytestmark = pytest.mark.gpu
-
-
-def _atrous_numpy(img, albedo, normal, iterations, sigma_color, sigma_normal, sigma_albedo):
-    """Dammertz et al. 2010 edge-avoiding a-trous, B3-spline taps, weights = colour x albedo x normal^sigma, geometry is
-    only filtered with geometry (albedo.w = first-hit fraction) — the definition csrc/device/denoise.hip implements."""
-    H, W, _ = img.shape
-    kern = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], np.float64)
-    cur = img.astype(np.float64)
-    a, n = albedo.astype(np.float64), normal.astype(np.float64)
-    solid = a[..., 3] > 0.5
-    inv_c, inv_a = 1.0 / max(sigma_color ** 2, 1e-8), 1.0 / max(sigma_albedo ** 2, 1e-8)
-    for it in range(iterations):
-        step = 1 << it
-        acc = np.zeros((H, W, 3))
-        wsum = np.zeros((H, W))
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                oy, ox = dy * step, dx * step
-                ys, xs = np.arange(H) + oy, np.arange(W) + ox
-                vy, vx = (ys >= 0) & (ys < H), (xs >= 0) & (xs < W)
-                valid = vy[:, None] & vx[None, :]
-                qy, qx = np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)
-                qc, qa, qn, qs = cur[qy][:, qx], a[qy][:, qx], n[qy][:, qx], solid[qy][:, qx]
-                valid &= qs == solid
-                w_c = np.exp(-((qc[..., :3] - cur[..., :3]) ** 2).sum(-1) * inv_c)
-                w_a = np.exp(-((qa[..., :3] - a[..., :3]) ** 2).sum(-1) * inv_a)
-                nd = np.maximum(0.0, (qn[..., :3] * n[..., :3]).sum(-1))
-                w_n = np.where(solid, nd ** sigma_normal, 1.0)
-                w = kern[dy + 2] * kern[dx + 2] * w_c * w_a * w_n * valid
-                acc += qc[..., :3] * w[..., None]
-                wsum += w
-        out = cur.copy()
-        ok = wsum > 0
-        out[ok, :3] = acc[ok] / wsum[ok, None]
-        cur = out
-    return cur
 
 
 def test_atrous_matches_numpy_and_reduces_noise(built, assets):
@@ -88,87 +53,6 @@ def test_atrous_matches_numpy_and_reduces_noise(built, assets):
     err_noisy = np.sqrt(((noisy[hit][:, :3] - ref[hit][:, :3]) ** 2).mean())
     err_den = np.sqrt(((den[hit][:, :3] - ref[hit][:, :3]) ** 2).mean())
     assert err_den < 0.85 * err_noisy, (err_den, err_noisy)
-
-
-def _svgf_numpy(color, albedo, normal, depth, frames, iterations, sigma_l, sigma_n, sigma_z):
-    """The definition csrc/device/denoise.hip implements (Schied et al. 2017 without reprojection), in float64."""
-    H, W, _ = color.shape
-    lumw = np.array([0.2126, 0.7152, 0.0722])
-    c, a, n = color.astype(np.float64), albedo.astype(np.float64), normal.astype(np.float64)
-    solid = a[..., 3] > 0.5
-    dem = np.where(solid[..., None], np.maximum(a[..., :3], 0.02), 1.0)
-    il = c[..., :3] / dem
-    if frames >= 4:
-        l = c[..., :3] @ lumw
-        var = np.maximum(0.0, n[..., 3] - l * l) / frames / (dem @ lumw) ** 2
-    else:
-        li = il @ lumw
-        s1, s2, sw = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W))
-        for dy in range(-3, 4):
-            for dx in range(-3, 4):
-                ys, xs = np.arange(H) + dy, np.arange(W) + dx
-                valid = ((ys >= 0) & (ys < H))[:, None] & ((xs >= 0) & (xs < W))[None, :]
-                qy, qx = np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)
-                valid &= solid[qy][:, qx] == solid
-                nd = np.maximum(0.0, (n[qy][:, qx][..., :3] * n[..., :3]).sum(-1))
-                w = np.where(solid, (nd > 0.9).astype(np.float64), 1.0) * valid
-                lq = li[qy][:, qx]
-                s1 += w * lq
-                s2 += w * lq * lq
-                sw += w
-        m = np.where(sw > 0, s1 / np.maximum(sw, 1e-30), 0.0)
-        var = np.where(sw > 0, np.maximum(0.0, s2 / np.maximum(sw, 1e-30) - m * m), 0.0)
-    cur = np.concatenate([il, var[..., None]], -1)
-    zk = 1.0 / np.maximum(1.0 - depth.astype(np.float64), 1e-7)
-    zx = np.empty_like(zk)
-    zx[:, :-1] = zk[:, 1:]
-    zx[:, -1] = zk[:, -2] if W > 1 else zk[:, -1]
-    zy = np.empty_like(zk)
-    zy[:-1] = zk[1:]
-    zy[-1] = zk[-2] if H > 1 else zk[-1]
-    gz = np.maximum(np.abs(zx - zk), np.abs(zy - zk))
-    kern = {0: 3 / 8, 1: 1 / 4, 2: 1 / 16}
-    gauss = {0: 0.5, 1: 0.25}
-    for it in range(iterations):
-        step = 1 << it
-        gv, gw = np.zeros((H, W)), np.zeros((H, W))
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                ys, xs = np.arange(H) + dy, np.arange(W) + dx
-                valid = ((ys >= 0) & (ys < H))[:, None] & ((xs >= 0) & (xs < W))[None, :]
-                qy, qx = np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)
-                w = gauss[abs(dx)] * gauss[abs(dy)] * valid
-                gv += w * cur[qy][:, qx][..., 3]
-                gw += w
-        sdev = np.sqrt(np.maximum(gv / gw, 0.0))
-        lc = cur[..., :3] @ lumw
-        h0 = kern[0] * kern[0]
-        acc = cur[..., :3] * h0
-        accv = cur[..., 3] * h0 * h0
-        sw = np.full((H, W), h0)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                if dx == 0 and dy == 0:
-                    continue
-                ys, xs = np.arange(H) + dy * step, np.arange(W) + dx * step
-                valid = ((ys >= 0) & (ys < H))[:, None] & ((xs >= 0) & (xs < W))[None, :]
-                qy, qx = np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)
-                valid &= solid[qy][:, qx] == solid
-                qc = cur[qy][:, qx]
-                w = np.exp(-np.abs(qc[..., :3] @ lumw - lc) / (sigma_l * sdev + 1e-6))
-                nd = np.maximum(0.0, (n[qy][:, qx][..., :3] * n[..., :3]).sum(-1))
-                dist = step * np.sqrt(dx * dx + dy * dy)
-                wg = nd ** sigma_n * np.exp(-np.abs(zk[qy][:, qx] - zk) / (sigma_z * gz * dist + 1e-6 * zk))
-                w = np.where(solid, w * wg, w) * valid
-                h = kern[abs(dx)] * kern[abs(dy)] * w
-                acc += qc[..., :3] * h[..., None]
-                accv += qc[..., 3] * h * h
-                sw += h
-        cur = np.concatenate([acc / sw[..., None], (accv / (sw * sw))[..., None]], -1)
-    out = np.empty((H, W, 4))
-    out[..., :3] = cur[..., :3] * dem
-    out[..., 3] = c[..., 3]
-    return out
 
 
 @pytest.mark.parametrize("frames", [2, 16])
