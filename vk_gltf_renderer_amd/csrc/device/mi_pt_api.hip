@@ -145,10 +145,25 @@ struct MiPt
   int numCUs = 256;
   RunSwitches sw;
   // mi_pt_set_frame_queue: consecutive mi_pt_render_frame calls held back and issued together (flushPending)
-  int               frameQueueDepth = 1;
-  int               pendingFrames   = 0;
-  MiPathtraceParams pendingFirst{};
-  void*             pendingStream   = nullptr;
+  struct FrameQueue
+  {
+    int               frameQueueDepth = 1;
+    int               pendingFrames   = 0;
+    MiPathtraceParams pendingFirst{};
+    void*             pendingStream   = nullptr;
+    // frame k of a batch is the first frame's parameters with frameCount + k and totalSamples + k * numSamples (mi_pt_render_frames): a call joins
+    // the pending batch when it is exactly that, on the same stream, and does not start a new accumulation
+    bool joins(const MiPathtraceParams& params, void* stream) const
+    {
+      MiPathtraceParams expect = pendingFirst;
+      expect.frameCount += pendingFrames;
+      expect.totalSamples += pendingFrames * expect.numSamples;
+      expect.flags &= ~MI_PT_FIRST_FRAME;
+      expect.mouseCoord[0] = params.mouseCoord[0];
+      expect.mouseCoord[1] = params.mouseCoord[1];
+      return pendingFrames > 0 && stream == pendingStream && memcmp(&expect, &params, sizeof(expect)) == 0;
+    }
+  } frameQueue;
   // scene
   DevBuf<MiGltfShadeMaterial> materials;
   DevBuf<MiGltfTextureInfo>   texInfos;
@@ -168,17 +183,28 @@ struct MiPt
   pt::DevScene                scene{};
   bool                        hasAlpha = false, hasAlphaTest = false, hasVolumeScatter = false, simpleMaterials = true, hasTransmissive = false;
   // device-resident descriptor copies (see k_shade): the scene struct, re-uploaded when the environment changes, and a ring
-  // of per-batch frame constants fed from pinned host memory
-  static constexpr int        FC_RING = 32;
+  // of per-batch frame constants fed from pinned host memory (FrameConstsRing, with the owners of HIP handles at the end)
   DevBuf<pt::DevScene>        sceneDev;
   bool                        sceneDevDirty = true;
-  DevBuf<pt::FrameConsts>     fcRing;
-  DevBuf<pt::SkyPrecomp>      skyPre;  // constants of the sky model for `skyPreFor` (k_sky_precomp)
-  MiSkyPhysicalParameters     skyPreFor{};
-  bool                        skyPreValid = false;
-  pt::FrameConsts*            fcHost = nullptr;  // pinned, FC_RING entries
-  hipEvent_t                  fcDone[FC_RING] = {};
-  unsigned                    fcCursor = 0;
+  struct SkyConstants
+  {
+    DevBuf<pt::SkyPrecomp>      skyPre;  // constants of the sky model for `skyPreFor` (k_sky_precomp)
+    MiSkyPhysicalParameters     skyPreFor{};
+    bool                        skyPreValid = false;
+    // The constants are those of `sky`: k_sky_precomp runs only when the parameters changed since it last ran
+    int upToDate(const MiSkyPhysicalParameters& sky, hipStream_t stream)
+    {
+      if(skyPreValid && memcmp(&skyPreFor, &sky, sizeof(sky)) == 0)
+        return MI_PT_OK;
+      // stream-ordered behind the batches that still read the previous values
+      if(!skyPre.ptr)
+        HIP_TRY(skyPre.alloc(1));
+      pt::launchSkyPrecomp(sky, skyPre.ptr, stream);
+      skyPreFor   = sky;
+      skyPreValid = true;
+      return MI_PT_OK;
+    }
+  } skyConsts;
   MiPtStats                   staticStats{};
   // host copies of what the acceleration structure is built from, kept so that mi_pt_update_render_nodes can rebuild it
   std::vector<MiGltfRenderNode> hostNodes;
@@ -358,40 +384,172 @@ struct MiPt
   const MiPtRay*          cameraRays = nullptr;
   int                     cameraRaySets = 0, cameraRaysWidth = 0, cameraRaysHeight = 0;  // the size they were bound at
   uint32_t                cameraRayFlags = 0;
+  // rays bound at another image size: the render calls refuse until the caller binds or unbinds again
+  bool                    cameraRaysStale() const { return cameraRays && (cameraRaysWidth != width || cameraRaysHeight != height); }
+  static constexpr const char* CAMERA_RAYS_STALE = "mi_pt_render_frame: the bound camera rays were bound at another image size -- bind or unbind them again";
   DevBuf<uint32_t>        allTiles;           // every tile of the image, for mi_pt_make_camera_rays under a tile partition (else ownedTiles is that)
   DevBuf<pt::StatCounters> stats;
   bool                    collectCounters = false;
-  bool                    timingEnabled   = false;
-  // deferred timing: events are recorded per launch and only resolved in mi_pt_get_frame_timing (no per-frame sync)
-  struct Span
-  {
-    int        kind;
-    hipEvent_t a, b;
-  };
-  std::vector<Span>       pendingSpans;
-  size_t                  evCursor = 0;
-  MiPtFrameTiming         accTiming{};
-  std::vector<hipEvent_t> eventPool;
   hipStream_t             lastStream = nullptr;
-  hipStream_t             sideStream = nullptr;                    // the shadow stage of small batches (RunSwitches::overlapUpTo)
-  hipEvent_t              evShaded = nullptr, evShadowed = nullptr;  // main -> side after a shade launch, side -> main after the shadow stage
-
-  ~MiPt()
+  // ---- the owners of the render path's HIP handles.  Each releases its own in its destructor and is never copied; they stand LAST so that
+  // mi_pt_destroy releases the handles before the device buffers above (members are destroyed in reverse order): timer, ring, second stream.
+  struct ShadowOverlap
   {
-    for(hipEvent_t e : eventPool)
-      (void)hipEventDestroy(e);
-    for(hipEvent_t e : fcDone)
-      if(e)
+    hipStream_t             sideStream = nullptr;                    // the shadow stage of small batches (RunSwitches::overlapUpTo)
+    hipEvent_t              evShaded = nullptr, evShadowed = nullptr;  // main -> side after a shade launch, side -> main after the shadow stage
+    // The stream and its two events exist, made by the first batch that wants them; false: HIP made none, and the batch keeps one stream
+    bool ready()
+    {
+      return sideStream
+             || (hipStreamCreateWithFlags(&sideStream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&evShaded, hipEventDisableTiming) == hipSuccess
+                 && hipEventCreateWithFlags(&evShadowed, hipEventDisableTiming) == hipSuccess);
+    }
+    // Any early return of a batch (a failed queue poll, a launch error) must not leave shadow-stage work queued on the side stream behind the caller's
+    // back: a caller that synchronises its own stream and then resizes or updates would race with kernels still adding into the radiance records.
+    // On every exit taken while a shadow stage is outstanding the side stream is drained (error paths only: the ordinary path joins it by event).
+    struct SideJoin
+    {
+      hipStream_t side        = nullptr;
+      bool        outstanding = false;
+      ~SideJoin()
+      {
+        if(outstanding && side)
+          (void)hipStreamSynchronize(side);
+      }
+    };
+    ShadowOverlap()                                = default;
+    ShadowOverlap(const ShadowOverlap&)            = delete;
+    ShadowOverlap& operator=(const ShadowOverlap&) = delete;
+    ~ShadowOverlap()
+    {
+      if(sideStream)
+        (void)hipStreamDestroy(sideStream);
+      if(evShaded)
+        (void)hipEventDestroy(evShaded);
+      if(evShadowed)
+        (void)hipEventDestroy(evShadowed);
+    }
+  } shadowOverlap;
+  struct FrameConstsRing
+  {
+    static constexpr int        FC_RING = 32;
+    DevBuf<pt::FrameConsts>     fcRing;
+    pt::FrameConsts*            fcHost = nullptr;  // pinned, FC_RING entries
+    hipEvent_t                  fcDone[FC_RING] = {};
+    unsigned                    fcCursor = 0;
+    // The next slot of the ring (made by the first call) holds `fc` for the batch about to be launched on `stream`: the call waits for the batch
+    // that used the slot FC_RING calls ago, then copies stream-ordered.  `dev`: the constants on the device; recordDone(slot, stream) ends the claim
+    int claim(const pt::FrameConsts& fc, hipStream_t stream, const pt::FrameConsts** dev, unsigned* slot)
+    {
+      if(!fcHost)
+      {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&fcHost), sizeof(pt::FrameConsts) * FC_RING, hipHostMallocDefault));
+        HIP_TRY(fcRing.alloc(FC_RING));
+        for(hipEvent_t& e : fcDone)
+          HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      }
+      const unsigned fcSlot = fcCursor++ % unsigned(FC_RING);
+      if(fcCursor > unsigned(FC_RING))
+        HIP_TRY(hipEventSynchronize(fcDone[fcSlot]));  // the batch that used this slot FC_RING calls ago must have drained
+      fcHost[fcSlot] = fc;
+      HIP_TRY(hipMemcpyAsync(fcRing.ptr + fcSlot, fcHost + fcSlot, sizeof(pt::FrameConsts), hipMemcpyHostToDevice, stream));
+      *dev  = fcRing.ptr + fcSlot;
+      *slot = fcSlot;
+      return MI_PT_OK;
+    }
+    // ... behind the batch's last launch
+    int recordDone(unsigned slot, hipStream_t stream)
+    {
+      HIP_TRY(hipEventRecord(fcDone[slot], stream));
+      return MI_PT_OK;
+    }
+    FrameConstsRing() = default;  // (never copied: DevBuf is move-only)
+    ~FrameConstsRing()
+    {
+      for(hipEvent_t e : fcDone)
+        if(e)
+          (void)hipEventDestroy(e);
+      if(fcHost)
+        (void)hipHostFree(fcHost);
+    }
+  } fcConsts;
+  struct LaunchTimer
+  {
+    bool                    timingEnabled   = false;
+    // deferred timing: events are recorded per launch and only resolved in mi_pt_get_frame_timing (no per-frame sync)
+    struct Span
+    {
+      int        kind;
+      hipEvent_t a, b;
+    };
+    std::vector<Span>       pendingSpans;
+    size_t                  evCursor = 0;
+    MiPtFrameTiming         accTiming{};
+    std::vector<hipEvent_t> eventPool;
+    // The next event of the pool, which grows when the spans recorded since the last reset() have used them all
+    hipEvent_t getEvent()
+    {
+      if(evCursor >= eventPool.size())
+      {
+        hipEvent_t e;
+        (void)hipEventCreate(&e);
+        eventPool.push_back(e);
+      }
+      return eventPool[evCursor++];
+    }
+    // `launch` on `stream`, between two events when the timer is on: a span of `kind` (TimedKernel)
+    template <typename Launch>
+    void timed(hipStream_t stream, int kind, Launch&& launch)
+    {
+      if(timingEnabled)
+      {
+        hipEvent_t a = getEvent(), b = getEvent();
+        (void)hipEventRecord(a, stream);
+        launch();
+        (void)hipEventRecord(b, stream);
+        pendingSpans.push_back({kind, a, b});
+      }
+      else
+        launch();
+    }
+    // No span is pending and every event of the pool is free again (accTiming stays)
+    void reset()
+    {
+      pendingSpans.clear();
+      evCursor = 0;
+    }
+    // The pending spans' times go into accTiming, after the device synchronisation of the caller
+    void resolve()
+    {
+      MiPtFrameTiming& t = accTiming;
+      for(const Span& sp : pendingSpans)
+      {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, sp.a, sp.b);
+        switch(sp.kind)
+        {
+          case TK_GENERATE: t.generateMs += ms; break;
+          case TK_TRACE: t.traceClosestMs += ms; break;
+          case TK_SORT: t.sortMs += ms; break;
+          case TK_SHADE: t.shadeMs += ms; break;
+          case TK_PRIMARY: t.traceClosestMs += ms; t.tracePrimaryMs += ms; break;
+          case TK_SHADE_FIRST: t.shadeMs += ms; t.shadeFirstMs += ms; break;
+          case TK_SHADOW: t.traceShadowMs += ms; break;
+          case TK_ACCUM: t.accumulateMs += ms; break;
+          default: t.totalMs += ms; break;
+        }
+      }
+      reset();
+    }
+    LaunchTimer()                              = default;
+    LaunchTimer(const LaunchTimer&)            = delete;
+    LaunchTimer& operator=(const LaunchTimer&) = delete;
+    ~LaunchTimer()
+    {
+      for(hipEvent_t e : eventPool)
         (void)hipEventDestroy(e);
-    if(fcHost)
-      (void)hipHostFree(fcHost);
-    if(sideStream)
-      (void)hipStreamDestroy(sideStream);
-    if(evShaded)
-      (void)hipEventDestroy(evShaded);
-    if(evShadowed)
-      (void)hipEventDestroy(evShadowed);
-  }
+    }
+  } timer;
 };
 
 namespace {
@@ -731,17 +889,6 @@ int allocFrameResources(MiPt* pt)
   pt->tmHistogram.release();
   pt->tmAutoState.release();
   return allocTemporal(pt);
-}
-
-hipEvent_t getEvent(MiPt* pt, size_t& cursor)
-{
-  if(cursor >= pt->eventPool.size())
-  {
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    pt->eventPool.push_back(e);
-  }
-  return pt->eventPool[cursor++];
 }
 
 
@@ -1455,16 +1602,13 @@ const char* mi_pt_last_error(void)
 }
 // Issues the frames mi_pt_render_frame has been holding back (mi_pt_set_frame_queue) as ONE mi_pt_render_frames batch.  Every entry point that
 // reads or changes what those frames depend on calls this first, so a caller never observes the deferral except through time.
-// rays bound at another image size: the render calls refuse until the caller binds or unbinds again
-static bool cameraRaysStale(const MiPt* pt) { return pt->cameraRays && (pt->cameraRaysWidth != pt->width || pt->cameraRaysHeight != pt->height); }
-static const char* const CAMERA_RAYS_STALE = "mi_pt_render_frame: the bound camera rays were bound at another image size -- bind or unbind them again";
 static int flushPending(MiPt* pt)
 {
-  if(!pt || pt->pendingFrames == 0)
+  if(!pt || pt->frameQueue.pendingFrames == 0)
     return MI_PT_OK;
-  const int n       = pt->pendingFrames;
-  pt->pendingFrames = 0;
-  return mi_pt_render_frames(pt, &pt->pendingFirst, n, pt->pendingStream);
+  const int n                  = pt->frameQueue.pendingFrames;
+  pt->frameQueue.pendingFrames = 0;
+  return mi_pt_render_frames(pt, &pt->frameQueue.pendingFirst, n, pt->frameQueue.pendingStream);
 }
 #define FLUSH_PENDING(pt)              \
   do                                   \
@@ -1473,76 +1617,55 @@ static int flushPending(MiPt* pt)
       return rcFlush_;                 \
   } while(0)
 
-int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt** out)
+// ---- mi_pt_create in phases: the description is validated as a whole, then uploaded table by table ----------------------------------------
+// Cross-table consistency (include/mi_pt.h: MI_PT_ERR_ARGUMENT for inconsistent tables).  The kernels index these tables
+// without further checks, so a caller other than the in-tree loader gets an error here instead of a device fault.
+// false: `why` is the message.  (The two limits on pool SIZES stand where the sizes are summed: uploadGeometry, uploadTextures.)
+static bool validateSceneDesc(const MiPtSceneDesc* sd, std::string& why)
 {
-  if(!sd || !out)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: null argument");
-  int deviceCount = 0;
-  if(hipGetDeviceCount(&deviceCount) != hipSuccess || deviceCount <= 0)
-    return fail(MI_PT_ERR_NO_DEVICE, "mi_pt_create: no HIP device visible (this library has no CPU path)");
-  const int device = options ? options->device : 0;
-  if(device < 0 || device >= deviceCount)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  auto refuse = [&](const std::string& message) {
+    why = message;
+    return false;
+  };
   if(sd->numMaterials <= 0 || sd->numTextureInfos <= 0)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: scene needs at least one material and the reserved texture-info slot 0");
-
-  // ---- cross-table consistency (include/mi_pt.h: MI_PT_ERR_ARGUMENT for inconsistent tables).  The kernels index these tables
-  // without further checks, so a caller other than the in-tree loader gets an error here instead of a device fault.
+    return refuse("mi_pt_create: scene needs at least one material and the reserved texture-info slot 0");
   if(sd->numRenderNodes < 0 || sd->numRenderPrimitives < 0 || sd->numLights < 0 || sd->numTextures < 0 || sd->numMaterials > 65535 * 4
      || (sd->numRenderNodes > 0 && !sd->renderNodes) || (sd->numRenderPrimitives > 0 && !sd->renderPrimitives) || (sd->numLights > 0 && !sd->lights)
      || (sd->numTextures > 0 && !sd->textures) || !sd->materials || !sd->textureInfos)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: negative table size or null table");
+    return refuse("mi_pt_create: negative table size or null table");
   for(int n = 0; n < sd->numRenderNodes; ++n)
   {
     const MiGltfRenderNode& rn = sd->renderNodes[n];
     if(rn.materialID >= sd->numMaterials)  // (negative ids mean "default material", reference: max(0, materialID))
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render node " + std::to_string(n) + " references material " + std::to_string(rn.materialID) + " of "
-                                          + std::to_string(sd->numMaterials));
+      return refuse("mi_pt_create: render node " + std::to_string(n) + " references material " + std::to_string(rn.materialID) + " of "
+                    + std::to_string(sd->numMaterials));
   }
-  {
-    std::string why;
-    if(!materialSlotsInRange(sd->materials, sd->numMaterials, sd->numTextureInfos, why))
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: " + why);
-  }
+  std::string slot;
+  if(!materialSlotsInRange(sd->materials, sd->numMaterials, sd->numTextureInfos, slot))
+    return refuse("mi_pt_create: " + slot);
   for(int i = 0; i < sd->numRenderPrimitives; ++i)
   {
     const MiPtRenderPrimitive& p = sd->renderPrimitives[i];
     if(p.vertexCount > 0 && !p.positions)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render primitive " + std::to_string(i) + " has vertices but no positions");
+      return refuse("mi_pt_create: render primitive " + std::to_string(i) + " has vertices but no positions");
     if(p.triangleCount > 0 && !p.indices)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render primitive " + std::to_string(i) + " has triangles but no indices");
+      return refuse("mi_pt_create: render primitive " + std::to_string(i) + " has triangles but no indices");
     for(size_t k = 0, n = size_t(p.triangleCount) * 3; k < n; ++k)
       if(p.indices[k] >= p.vertexCount)
-        return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: render primitive " + std::to_string(i) + " has a vertex index beyond its vertexCount");
+        return refuse("mi_pt_create: render primitive " + std::to_string(i) + " has a vertex index beyond its vertexCount");
   }
+  for(int i = 0; i < sd->numTextures; ++i)
+  {
+    const MiPtTexture& t = sd->textures[i];
+    if(t.numLevels < 1 || t.numLevels > 16 || t.width < 1 || t.height < 1 || t.width > 65535 || t.height > 65535)
+      return refuse("mi_pt_create: texture dimensions / level count out of range");
+  }
+  return true;
+}
 
-  // the phases of the scene build under the build-timing switch
-  auto tPhase = BuildClock::now();
-  auto phase  = [&](const char* what) {
-    if(!buildTiming())
-      return;
-    (void)hipDeviceSynchronize();
-    printBuildTiming(what, tPhase);
-    tPhase = BuildClock::now();
-  };
-
-  std::unique_ptr<MiPt> pt(new MiPt());
-  pt->sw.read();
-  if(pt->sw.collapseBad)
-    return fail(MI_PT_ERR_ARGUMENT, std::string("MI_PT_COLLAPSE=") + getenv("MI_PT_COLLAPSE") + " is neither \"sah\" nor \"greedy\"");
-  pt->device          = device;
-  pt->numCUs          = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  pt->collectCounters = options && options->collectCounters;
-
-  HIP_TRY(pt->materials.upload(sd->materials, size_t(sd->numMaterials)));
-  HIP_TRY(pt->texInfos.upload(sd->textureInfos, size_t(sd->numTextureInfos)));
-  HIP_TRY(pt->nodes.upload(sd->renderNodes, size_t(sd->numRenderNodes)));
-  HIP_TRY(pt->lights.upload(sd->lights, size_t(sd->numLights)));
-
-  // ---- geometry pool ------------------------------------------------------------------------------------------------
+// The geometry pool: every index / attribute stream and the interleaved vertex copy, and the primitives' records that address them
+static int uploadGeometry(MiPt* pt, const MiPtSceneDesc* sd)
+{
   size_t geomBytes = 0;
   for(int i = 0; i < sd->numRenderPrimitives; ++i)
   {
@@ -1603,9 +1726,12 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
   pt->hostPrims = devPrims;
   for(int i = 0; i < sd->numRenderPrimitives; ++i)
     pt->primVertices.push_back(sd->renderPrimitives[i].vertexCount);
-  phase("tables + geometry upload");
+  return MI_PT_OK;
+}
 
-  // ---- what the acceleration structure is built from (see buildAcceleration) ------------------------------------------------
+// The host copies of what the acceleration structure is built from (see buildAcceleration) and of what the material updates diff against
+static void keepHostTables(MiPt* pt, const MiPtSceneDesc* sd)
+{
   pt->hostNodes.assign(sd->renderNodes, sd->renderNodes + sd->numRenderNodes);
   if(sd->renderNodeVisible)
     pt->hostVisible.assign(sd->renderNodeVisible, sd->renderNodeVisible + sd->numRenderNodes);
@@ -1624,69 +1750,67 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
     const MiPtRenderPrimitive& rp = sd->renderPrimitives[i];
     pt->primTriangles[size_t(i)]  = (rp.positions && rp.indices) ? rp.triangleCount : 0u;
   }
-  pt->accel.bvhBuilder = options ? options->bvhBuilder : 0;
+}
 
-  // ---- textures: one RGBA8 pool with all mip chains -----------------------------------------------------------------------
+// Textures: one RGBA8 pool with all mip chains, the bilinear footprints, the per-slot records of the materials, and the sRGB table
+static int uploadTextures(MiPt* pt, const MiPtSceneDesc* sd)
+{
+  std::vector<pt::DevTexture> dt(size_t(sd->numTextures));
+  size_t                      totalTexels = 0;
+  for(int i = 0; i < sd->numTextures; ++i)
+    for(int l = 0; l < sd->textures[i].numLevels; ++l)  // (sizes and level counts are in range: validateSceneDesc)
+      totalTexels += levelExtent(sd->textures[i], l).texels;
+  if(totalTexels > 0xffffffffull)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: texture pool exceeds 2^32 texels");
+  std::vector<uchar4> pool(std::max<size_t>(totalTexels, 1));
+  size_t              off = 0;
+  for(int i = 0; i < sd->numTextures; ++i)
   {
-    std::vector<pt::DevTexture> dt(size_t(sd->numTextures));
-    size_t                      totalTexels = 0;
-    for(int i = 0; i < sd->numTextures; ++i)
+    const MiPtTexture& t = sd->textures[i];
+    pt::DevTexture&    d = dt[size_t(i)];
+    memset(&d, 0, sizeof(d));
+    d.width = uint16_t(t.width); d.height = uint16_t(t.height); d.numLevels = uint8_t(t.numLevels); d.srgb = uint8_t(t.srgb ? 1 : 0);
+    d.magFilter = uint8_t(t.magFilter); d.minFilter = uint8_t(t.minFilter); d.mipmapMode = uint8_t(t.mipmapMode);
+    d.wrapS = uint8_t(t.wrapS); d.wrapT = uint8_t(t.wrapT);
+    for(int l = 0; l < t.numLevels; ++l)
     {
-      const MiPtTexture& t = sd->textures[i];
-      if(t.numLevels < 1 || t.numLevels > 16 || t.width < 1 || t.height < 1 || t.width > 65535 || t.height > 65535)
-        return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: texture dimensions / level count out of range");
-      for(int l = 0; l < t.numLevels; ++l)
-        totalTexels += levelExtent(t, l).texels;
+      const size_t n   = levelExtent(t, l).texels;
+      d.levelOffset[l] = uint32_t(off);
+      memcpy(&pool[off], t.levels[l], n * 4);
+      off += n;
     }
-    if(totalTexels > 0xffffffffull)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: texture pool exceeds 2^32 texels");
-    std::vector<uchar4> pool(std::max<size_t>(totalTexels, 1));
-    size_t              off = 0;
-    for(int i = 0; i < sd->numTextures; ++i)
-    {
-      const MiPtTexture& t = sd->textures[i];
-      pt::DevTexture&    d = dt[size_t(i)];
-      memset(&d, 0, sizeof(d));
-      d.width = uint16_t(t.width); d.height = uint16_t(t.height); d.numLevels = uint8_t(t.numLevels); d.srgb = uint8_t(t.srgb ? 1 : 0);
-      d.magFilter = uint8_t(t.magFilter); d.minFilter = uint8_t(t.minFilter); d.mipmapMode = uint8_t(t.mipmapMode);
-      d.wrapS = uint8_t(t.wrapS); d.wrapT = uint8_t(t.wrapT);
-      for(int l = 0; l < t.numLevels; ++l)
-      {
-        const size_t n   = levelExtent(t, l).texels;
-        d.levelOffset[l] = uint32_t(off);
-        memcpy(&pool[off], t.levels[l], n * 4);
-        off += n;
-      }
-    }
-    HIP_TRY(pt->textures.upload(dt.data(), dt.size()));
-    HIP_TRY(pt->texels.upload(pool.data(), pool.size()));
-    // bilinear footprints (pt_scene.h: texQuads), built on the device from the pool just uploaded; MI_PT_DIAG_NO_QUADS=1: A/B switch
-    if(totalTexels > 0 && !pt->sw.noQuads)
-    {
-      HIP_TRY(pt->texQuads.alloc(pool.size()));
-      for(const pt::DevTexture& d : dt)
-        for(int l = 0; l < d.numLevels; ++l)
-          pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], levelExtent(d, l).w, levelExtent(d, l).h, d.wrapS, d.wrapT, nullptr);
-      HIP_TRY(hipGetLastError());
-    }
-    pt->hostTextures = dt;
-    std::vector<pt::DevTexRef>  refs;
-    std::vector<pt::DevCoreTex> core;
-    deriveTextureRecords(pt.get(), sd->materials, sd->numMaterials, sd->textureInfos, sd->numTextureInfos, refs, core);
-    HIP_TRY(pt->texRefs.upload(refs.data(), refs.size()));
-    HIP_TRY(pt->coreTex.upload(core.data(), core.size()));
   }
+  HIP_TRY(pt->textures.upload(dt.data(), dt.size()));
+  HIP_TRY(pt->texels.upload(pool.data(), pool.size()));
+  // bilinear footprints (pt_scene.h: texQuads), built on the device from the pool just uploaded; MI_PT_DIAG_NO_QUADS=1: A/B switch
+  if(totalTexels > 0 && !pt->sw.noQuads)
   {
-    float lut[256];
-    for(int i = 0; i < 256; ++i)
-    {
-      float c = float(i) / 255.0f;
-      lut[i]  = c <= 0.04045f ? c / 12.92f : std::pow((c + 0.055f) / 1.055f, 2.4f);
-    }
-    HIP_TRY(pt->srgbLut.upload(lut, 256));
+    HIP_TRY(pt->texQuads.alloc(pool.size()));
+    for(const pt::DevTexture& d : dt)
+      for(int l = 0; l < d.numLevels; ++l)
+        pt::launchTextureQuads(pt->texels.ptr, pt->texQuads.ptr, d.levelOffset[l], levelExtent(d, l).w, levelExtent(d, l).h, d.wrapS, d.wrapT, nullptr);
+    HIP_TRY(hipGetLastError());
   }
-  phase("textures upload");
+  pt->hostTextures = dt;
+  std::vector<pt::DevTexRef>  refs;
+  std::vector<pt::DevCoreTex> core;
+  deriveTextureRecords(pt, sd->materials, sd->numMaterials, sd->textureInfos, sd->numTextureInfos, refs, core);
+  HIP_TRY(pt->texRefs.upload(refs.data(), refs.size()));
+  HIP_TRY(pt->coreTex.upload(core.data(), core.size()));
+  // sRGB decode table of the texel fetch
+  float lut[256];
+  for(int i = 0; i < 256; ++i)
+  {
+    float c = float(i) / 255.0f;
+    lut[i]  = c <= 0.04045f ? c / 12.92f : std::pow((c + 0.055f) / 1.055f, 2.4f);
+  }
+  HIP_TRY(pt->srgbLut.upload(lut, 256));
+  return MI_PT_OK;
+}
 
+// The scene as the kernels see it; the acceleration structure's arrays follow with the build
+static void describeScene(MiPt* pt, const MiPtSceneDesc* sd)
+{
   pt::DevScene& S = pt->scene;
   S.materials = pt->materials.ptr; S.texInfos = pt->texInfos.ptr; S.nodes = pt->nodes.ptr; S.prims = pt->prims.ptr; S.lights = pt->lights.ptr;
   S.textures = pt->textures.ptr; S.texels = pt->texels.ptr; S.texQuads = pt->texQuads.ptr; S.envPixels = nullptr; S.envAccel = nullptr; S.bvhNodes = nullptr; S.bvh8Nodes = nullptr; S.bvh8Planes = nullptr; S.tris = nullptr;
@@ -1696,18 +1820,76 @@ int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt
   S.envWidth = 0; S.envHeight = 0;
   S.packetInterval = pt->sw.packetInterval;  // A/B switch (LABNOTES.md section 2): 0 = the per-ray node test in every packet
   S.shadowOctFlip  = pt->sw.shadowFarFirst ? 7u : 0u;
-  if(int rc = buildAcceleration(pt.get()))
-    return rc;
-  phase("shade / alpha records");
-  HIP_TRY(pt->stats.alloc(1));
-  HIP_TRY(hipMemset(pt->stats.ptr, 0, sizeof(pt::StatCounters)));
-  // SkyPhysicalParameters{} defaults, so a caller that never calls mi_pt_set_sky still renders the default sky
+}
+
+// SkyPhysicalParameters{} defaults, so a caller that never calls mi_pt_set_sky still renders the default sky
+static MiSkyPhysicalParameters defaultSky()
+{
   MiSkyPhysicalParameters s{};
   s.rgbUnitConversion[0] = s.rgbUnitConversion[1] = s.rgbUnitConversion[2] = 1.0f / 80000.0f;
   s.multiplier = 0.1f; s.haze = 0.1f; s.redblueshift = 0.1f; s.saturation = 1.0f; s.groundColor[0] = s.groundColor[1] = s.groundColor[2] = 0.4f;
   s.horizonBlur = 0.3f; s.sunDiskIntensity = 1.0f; s.sunDirection[0] = s.sunDirection[1] = s.sunDirection[2] = 0.5773502691896258f;
   s.sunDiskScale = 1.0f; s.sunGlowIntensity = 1.0f; s.yIsUp = 1;
-  pt->sky = s;
+  return s;
+}
+
+int mi_pt_create(const MiPtSceneDesc* sd, const MiPtCreateOptions* options, MiPt** out)
+{
+  if(!sd || !out)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: null argument");
+  int deviceCount = 0;
+  if(hipGetDeviceCount(&deviceCount) != hipSuccess || deviceCount <= 0)
+    return fail(MI_PT_ERR_NO_DEVICE, "mi_pt_create: no HIP device visible (this library has no CPU path)");
+  const int device = options ? options->device : 0;
+  if(device < 0 || device >= deviceCount)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_create: bad device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  std::string why;
+  if(!validateSceneDesc(sd, why))
+    return fail(MI_PT_ERR_ARGUMENT, why);
+
+  // the phases of the scene build under the build-timing switch
+  auto tPhase = BuildClock::now();
+  auto phase  = [&](const char* what) {
+    if(!buildTiming())
+      return;
+    (void)hipDeviceSynchronize();
+    printBuildTiming(what, tPhase);
+    tPhase = BuildClock::now();
+  };
+
+  std::unique_ptr<MiPt> pt(new MiPt());
+  pt->sw.read();
+  if(pt->sw.collapseBad)
+    return fail(MI_PT_ERR_ARGUMENT, std::string("MI_PT_COLLAPSE=") + getenv("MI_PT_COLLAPSE") + " is neither \"sah\" nor \"greedy\"");
+  pt->device          = device;
+  pt->numCUs          = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  pt->collectCounters = options && options->collectCounters;
+
+  HIP_TRY(pt->materials.upload(sd->materials, size_t(sd->numMaterials)));
+  HIP_TRY(pt->texInfos.upload(sd->textureInfos, size_t(sd->numTextureInfos)));
+  HIP_TRY(pt->nodes.upload(sd->renderNodes, size_t(sd->numRenderNodes)));
+  HIP_TRY(pt->lights.upload(sd->lights, size_t(sd->numLights)));
+
+  if(int rc = uploadGeometry(pt.get(), sd))
+    return rc;
+  phase("tables + geometry upload");
+
+  keepHostTables(pt.get(), sd);
+  pt->accel.bvhBuilder = options ? options->bvhBuilder : 0;
+  if(int rc = uploadTextures(pt.get(), sd))
+    return rc;
+  phase("textures upload");
+
+  describeScene(pt.get(), sd);
+  if(int rc = buildAcceleration(pt.get()))
+    return rc;
+  phase("shade / alpha records");
+  HIP_TRY(pt->stats.alloc(1));
+  HIP_TRY(hipMemset(pt->stats.ptr, 0, sizeof(pt::StatCounters)));
+  pt->sky = defaultSky();
   *out    = pt.release();
   return MI_PT_OK;
 }
@@ -2735,10 +2917,9 @@ int mi_pt_read_vertices(MiPt* pt, int renderPrimID, float* positions, float* nor
 
 int mi_pt_destroy(MiPt* pt)
 {
-  if(pt)
-    pt->pendingFrames = 0;  // (frames still held back are dropped with the instance)
   if(!pt)
     return MI_PT_OK;
+  pt->frameQueue.pendingFrames = 0;  // (frames still held back are dropped with the instance)
   (void)hipSetDevice(pt->device);
   (void)hipDeviceSynchronize();
   pt::dumpTraceProfile();
@@ -2853,92 +3034,73 @@ int mi_pt_set_frame_queue(MiPt* pt, int depth)
   if(!pt || depth < 1 || depth > 1024)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_set_frame_queue: 1 <= depth <= 1024 required");
   FLUSH_PENDING(pt);
-  pt->frameQueueDepth = depth;
+  pt->frameQueue.frameQueueDepth = depth;
+  return MI_PT_OK;
+}
+
+// ---- the render calls.  Two refusals are shared by mi_pt_render_frame (a held-back frame is refused by the call that brings it, not by a
+// later flush) and mi_pt_render_frames: each is written once and returns the code
+static int refuseSamplesOrDepth(const MiPathtraceParams* params)
+{
+  // (maxDepth 0: the reference's loop `for(depth = 0; depth < maxDepth; ...)` never runs and the image is black; here no shade launch would run and
+  //  the queued camera hits would keep the radiance and guide records of an earlier batch -- refused instead of special-cased)
+  if(params->numSamples < 1 || params->maxDepth < 1 || params->maxDepth > 255)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: numSamples >= 1 and 1 <= maxDepth <= 255 required");
+  return MI_PT_OK;
+}
+static int refuseBeforeResize(const MiPt* pt)
+{
+  if(pt->width <= 0 || !pt->haveFrameInfo)
+    return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: call mi_pt_resize and mi_pt_set_frame_info first");
   return MI_PT_OK;
 }
 
 int mi_pt_render_frame(MiPt* pt, const MiPathtraceParams* params, void* hipStream)
 {
-  if(pt && params && pt->frameQueueDepth > 1)
+  if(pt && params && pt->frameQueue.frameQueueDepth > 1)
   {
-    // frame k of a batch is the first frame's parameters with frameCount + k and totalSamples + k * numSamples (mi_pt_render_frames): a call joins
-    // the pending batch when it is exactly that, on the same stream, and does not start a new accumulation
-    if(pt->pendingFrames > 0)
+    MiPt::FrameQueue& q = pt->frameQueue;
+    if(q.pendingFrames > 0)
     {
-      MiPathtraceParams expect = pt->pendingFirst;
-      expect.frameCount += pt->pendingFrames;
-      expect.totalSamples += pt->pendingFrames * expect.numSamples;
-      expect.flags &= ~MI_PT_FIRST_FRAME;
-      expect.mouseCoord[0] = params->mouseCoord[0];
-      expect.mouseCoord[1] = params->mouseCoord[1];
-      if(hipStream == pt->pendingStream && memcmp(&expect, params, sizeof(expect)) == 0)
+      if(q.joins(*params, hipStream))
       {
-        if(++pt->pendingFrames >= pt->frameQueueDepth)
+        if(++q.pendingFrames >= q.frameQueueDepth)
           return flushPending(pt);
         return MI_PT_OK;
       }
       FLUSH_PENDING(pt);
     }
     // argument errors are reported by THIS call, not by a later flush
-    if(params->numSamples < 1 || params->maxDepth < 1 || params->maxDepth > 255)
-      return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: numSamples >= 1 and 1 <= maxDepth <= 255 required");
-    if(pt->width <= 0 || !pt->haveFrameInfo)
-      return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: call mi_pt_resize and mi_pt_set_frame_info first");
-    if(cameraRaysStale(pt))
-      return fail(MI_PT_ERR_STATE, CAMERA_RAYS_STALE);
-    pt->pendingFirst  = *params;
-    pt->pendingStream = hipStream;
-    pt->pendingFrames = 1;
+    if(int rc = refuseSamplesOrDepth(params))
+      return rc;
+    if(int rc = refuseBeforeResize(pt))
+      return rc;
+    if(pt->cameraRaysStale())
+      return fail(MI_PT_ERR_STATE, MiPt::CAMERA_RAYS_STALE);
+    q.pendingFirst  = *params;
+    q.pendingStream = hipStream;
+    q.pendingFrames = 1;
     return MI_PT_OK;
   }
 
   return mi_pt_render_frames(pt, params, 1, hipStream);
 }
 
-int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames, void* hipStream)
-{
-  FLUSH_PENDING(pt);
-  if(!pt || !params)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: null argument");
-  if(numFrames < 1 || numFrames > 1024)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frames: 1 <= numFrames <= 1024 required");
-  if(pt->width <= 0 || !pt->haveFrameInfo)
-    return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: call mi_pt_resize and mi_pt_set_frame_info first");
-  // (maxDepth 0: the reference's loop `for(depth = 0; depth < maxDepth; ...)` never runs and the image is black; here no shade launch would run and
-  //  the queued camera hits would keep the radiance and guide records of an earlier batch -- refused instead of special-cased)
-  if(params->numSamples < 1 || params->maxDepth < 1 || params->maxDepth > 255)
-    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: numSamples >= 1 and 1 <= maxDepth <= 255 required");
-  if((pt->frameInfo.flags & MI_SCENE_USE_HDR_ENVIRONMENT) && !pt->scene.envPixels)
-    return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: HDR environment requested but none was set");
-  if(cameraRaysStale(pt))
-    return fail(MI_PT_ERR_STATE, CAMERA_RAYS_STALE);
-  HIP_TRY(hipSetDevice(pt->device));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hipStream);
-  pt->lastStream     = stream;
-  if(pt->numSlots == 0)
-    return MI_PT_OK;
-  if(numFrames > pt->framesCap)  // grow the path/queue arrays once; later batches of this size reuse them
-  {
-    HIP_TRY(hipDeviceSynchronize());
-    if(int rc = allocPathResources(pt, numFrames))
-      return rc;
-  }
+// ---- mi_pt_render_frames in phases.  The entry point keeps every refusal and everything that allocates or synchronises; the phases launch.
+// The path state lives by slot, not in the queue entry, on shadow-catcher frames (the plane's resolve pass may end a path) and under MI_PT_STATE_BY_SLOT
+static bool catcherFrame(const MiPt* pt) { return (pt->frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER) != 0; }
+static bool stateBySlot(const MiPt* pt) { return pt->sw.stateBySlot || catcherFrame(pt); }
 
+// What every launch of the batch is given, but for the two device-resident descriptor copies (sceneDev, fcDev), which the entry point adds.
+// Needs the sky constants up to date and the batch's optional path arrays allocated; moves accumFrames / momentFrames on by the batch.
+static pt::LaunchCtx launchContextOf(MiPt* pt, const MiPathtraceParams* params, int numFrames, hipStream_t stream)
+{
   pt::LaunchCtx c;
   c.scene = pt->scene;
   memset(&c.fc, 0, sizeof(c.fc));
   c.fc.frameInfo = pt->frameInfo;
   c.fc.sky       = pt->sky;
-  if(!pt->skyPreValid || memcmp(&pt->skyPreFor, &pt->sky, sizeof(pt->sky)) != 0)
-  {
-    // stream-ordered behind the batches that still read the previous values
-    if(!pt->skyPre.ptr)
-      HIP_TRY(pt->skyPre.alloc(1));
-    pt::launchSkyPrecomp(pt->sky, pt->skyPre.ptr, stream);
-    pt->skyPreFor   = pt->sky;
-    pt->skyPreValid = true;
-  }
-  c.fc.skyPre    = pt->skyPre.ptr;
+  c.fc.skyPre    = pt->skyConsts.skyPre.ptr;
   c.fc.pc        = *params;
   c.fc.width     = pt->width;
   c.fc.height    = pt->height;
@@ -2947,24 +3109,21 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   c.fc.numSlots  = pt->numSlots;
   c.fc.numFrames = numFrames;
   pt::divideMagic(uint32_t(std::max(numFrames, 2)), c.fc.framesMagic, c.fc.framesShift);
-  c.fc.slotLayout = numFrames % 64 == 0 ? 1 : 0;
-  c.fc.stateInQueue = (!pt->sw.stateBySlot && !(pt->frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER)) ? 1 : 0;
-  const bool guides = (params->flags & MI_PT_USE_OPTIX_DENOISER) != 0;
-  if(int rc = ensureOptionalPathArrays(pt, c.fc.stateInQueue == 0, params->numSamples > 1, guides, (pt->frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER) != 0))
-    return rc;
-  c.paths        = pt->paths;
-  {
-    // optional records stay allocated (MiPt::opt*) once a batch needed them; THIS batch sees only the ones it needs itself -- a later
-    // single-sample batch must not keep paying the by-slot writes of an earlier multi-sample or catcher batch
-    const bool stateBySlot = c.fc.stateInQueue == 0, multiSample = params->numSamples > 1;
-    if(!(stateBySlot || multiSample))
-      c.paths.misc = nullptr;
-    if(!stateBySlot)
-      c.paths.throughput = nullptr;
-    if(!multiSample)
-      c.paths.pixelSum = nullptr;
-  }
-  pt->accumFrames   = float(params->totalSamples) / float(params->numSamples) + float(numFrames);
+  c.fc.slotLayout   = numFrames % 64 == 0 ? 1 : 0;
+  c.fc.stateInQueue = stateBySlot(pt) ? 0 : 1;
+  c.sceneDev        = nullptr;
+  c.fcDev           = nullptr;
+  c.paths           = pt->paths;
+  // optional records stay allocated (MiPt::opt*) once a batch needed them; THIS batch sees only the ones it needs itself -- a later
+  // single-sample batch must not keep paying the by-slot writes of an earlier multi-sample or catcher batch
+  const bool multiSample = params->numSamples > 1, guides = (params->flags & MI_PT_USE_OPTIX_DENOISER) != 0;
+  if(!(stateBySlot(pt) || multiSample))
+    c.paths.misc = nullptr;
+  if(!stateBySlot(pt))
+    c.paths.throughput = nullptr;
+  if(!multiSample)
+    c.paths.pixelSum = nullptr;
+  pt->accumFrames = float(params->totalSamples) / float(params->numSamples) + float(numFrames);
   // the second moment covers the accumulation only if every batch since its start carried the guides
   if(guides && (params->totalSamples == 0 || pt->momentFrames == pt->accumFrames - float(numFrames)))
     pt->momentFrames = pt->accumFrames;
@@ -2976,7 +3135,7 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     c.paths.guideNormal = nullptr;
   }
   c.queues           = pt->queues;
-  if(!(pt->frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER))
+  if(!catcherFrame(pt))
     c.queues.shadow.aux2 = nullptr;
   c.ownedTiles       = pt->ownedTiles.ptr;
   c.stats            = pt->stats.ptr;
@@ -2996,13 +3155,231 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
   c.wide             = pt->accel.wide;
   c.collectCounters  = pt->collectCounters;
   c.shadowDeposit    = pt->sw.shadowDeposit;
+  // Per-bounce sort of the shade kernel (k_shade): grouping the hits by material pays where the materials take different ways
+  // through the BSDF (glass workload: generic shade kernel -11 %); where every material runs the same code (the SIMPLE
+  // kernel, which therefore has no sort at all) it only cost (helmet +4 %, atrium +12 %, street +4 % of the shade kernel).
+  // MI_PT_SORT = 0 | 1 | 2 is the A/B switch of the generic kernel.
+  c.sortMode = pt->sw.sortMode;
+  return c;
+}
+
+// Small batches: a bounce's shadow stage (any-hit walk + resolve) on a second stream, next to the NEXT bounce's closest-hit walk.  The two
+// are independent -- the walk reads the continuation rays the shade launch wrote, the shadow stage adds into radiance records that only
+// the next SHADE launch reads (which therefore waits for it) -- and with few frames in flight neither fills the 256 CUs: most
+// workgroups of a persistent grid find no work and leave, so the other kernel's find room.  Needs the state in the queue entry (on
+// catcher frames the resolve pass may end a path the walk is about to trace).
+// ... and launches long enough to be worth two cross-stream hand-overs per bounce: measured (round 4, frames in flight 1 / 4 / 8 / 16 / 32 / 64 / 128)
+// atrium-class (406 k triangles, depth 12) +15 / +8 / +6 / +3.5 / +1.7 / +1.0 / +0.3 %, street-class 4K +8 % at 1, +1.6 % at 8, +0.3 % from 32;
+// helmet-class (74 k, 60 % of the camera paths leave at bounce 0) -6.5 / -0.4 / -0.8 / -0.6 %: scenes below 2e5 triangles keep one stream.
+// Default up to 32 frames: the interactive range, where it pays; larger batches fill the device by themselves, and their per-launch times
+// (bench.py's kernel table) stay those of kernels that have the device to themselves.
+// Volume-scatter scenes run it at every batch size and triangle count: their random walks leave ~100 bounce iterations of a few thousand paths per
+// batch, three dependent launches each, and taking the shadow stage off that chain measured +31 % for a single frame, +8.7 % at 32 and +2.2 % at 256
+// frames in flight on the glass-class workload (the host's poll of the queue length every eighth iteration only waits for the main stream).
+static bool wantsOverlap(const MiPt* pt, const pt::LaunchCtx& c)
+{
+  return pt->sw.overlapUpTo > 0 && ((c.fc.numFrames <= pt->sw.overlapUpTo && pt->scene.numTris >= pt->sw.overlapMinTris) || pt->hasVolumeScatter)
+         && c.fc.stateInQueue != 0 && !pt->sw.traceSpans;
+}
+
+// The bound of a sample's bounce loop.  Every iteration either ends a path or consumes one unit of surfaceDepth, except volume scatter events
+// (pathtrace_functions.h.slang:925-931), which are free for VOLUME_FREE_BUDGET bounces and then Russian-rouletted.
+static int maxIterationsOf(const MiPt* pt, const MiPathtraceParams* params)
+{
+  int maxIters = params->maxDepth;
+  // a shadow-catcher bounce does not consume surfaceDepth (eEarlyContinue) but is always followed by a miss or a surface hit
+  if((pt->frameInfo.flags & MI_SCENE_USE_INFINITE_PLANE) && catcherFrame(pt))
+    maxIters = 2 * params->maxDepth + 2;
+  if(pt->hasVolumeScatter)
+    maxIters = params->maxDepth * 66 + 512;
+  if(pt->sw.maxItersDiag > 0)
+    maxIters = std::min(maxIters, pt->sw.maxItersDiag);
+  return maxIters;
+}
+
+// The poll of a volume-scatter scene's long loops: `drained` when the active queue `cur` is empty (synchronises the caller's stream)
+static int queuesDrained(const pt::LaunchCtx& c, int cur, bool& drained)
+{
+  uint32_t counts[2 * pt::NSUB];
+  HIP_TRY(hipMemcpyAsync(counts, &c.queues.counters[cur ? pt::QC_PAIR1 : pt::QC_PAIR0], sizeof(counts), hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  uint32_t remaining = 0;
+  for(int q = 0; q < pt::NSUB; ++q)
+    remaining += counts[2 * q];
+  drained = remaining == 0;
+  return MI_PT_OK;
+}
+
+// MI_PT_TRACE_SPANS=1: one bounce iteration with per-launch wall time and queue lengths on stderr (synchronising; diagnostics only)
+static void traceSpansIteration(const MiPt* pt, const pt::LaunchCtx& c, const MiPathtraceParams* params, int it, int cur)
+{
+  const hipStream_t stream = c.stream;
+  auto count = [&](int base) {  // base: first of 16 tails stored 2 words apart
+    uint32_t v[2 * pt::NSUB];
+    (void)hipMemcpy(v, &c.queues.counters[base], sizeof(uint32_t) * (2 * pt::NSUB - 1), hipMemcpyDeviceToHost);
+    uint32_t t = 0;
+    for(int q = 0; q < pt::NSUB; ++q) t += v[2 * q];
+    return t;
+  };
+  auto span = [&](auto&& launch) {
+    (void)hipStreamSynchronize(stream);
+    auto t0 = std::chrono::steady_clock::now();
+    launch();
+    (void)hipStreamSynchronize(stream);
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  auto segs = [&]() {
+    pt::StatCounters h{};
+    (void)hipMemcpy(&h, pt->stats.ptr, sizeof(h), hipMemcpyDeviceToHost);
+    return h;
+  };
+  uint32_t nIn = count(cur ? pt::QC_PAIR1 : pt::QC_PAIR0);
+  const pt::StatCounters s0 = segs();
+  double   tTrace = span([&] { pt::launchTraceClosest(c, cur); });
+  const pt::StatCounters s1 = segs();
+  double   tShade = span([&] { pt::launchShade(c, cur, it == 0); });
+  uint32_t nSh    = count((cur ? pt::QC_PAIR0 : pt::QC_PAIR1) + 1);
+  double   tShadow = span([&] { pt::launchTraceShadow(c, cur ^ 1); });
+  const pt::StatCounters s2 = segs();
+  fprintf(stderr, "[mi_pt span] frame %d it %2d rays %8u (traced %8llu, nodes %9llu tris %9llu) trace %8.3f ms shade %8.3f ms | shadow rays %8u (traced %8llu, nodes %9llu tris %9llu) %8.3f ms\n",
+          params->frameCount, it, nIn, (unsigned long long)(s1.segments - s0.segments), (unsigned long long)(s1.nodesClosest - s0.nodesClosest),
+          (unsigned long long)(s1.trisClosest - s0.trisClosest), tTrace, tShade, nSh, (unsigned long long)(s2.shadowRays - s1.shadowRays),
+          (unsigned long long)(s2.nodesShadow - s1.nodesShadow), (unsigned long long)(s2.trisShadow - s1.trisShadow), tShadow);
+}
+
+// One sample of a batch: the primary stage, the bounce loop, the join of the side stream, the survivor flush and the fold into the accumulator.
+// `iterations` counts the batch's bounce iterations: each is one closest-hit, one shade and one shadow launch
+static int renderSample(MiPt* pt, const pt::LaunchCtx& c, const pt::LaunchCtx& cSide, const MiPathtraceParams* params, int s, bool overlap,
+                        MiPt::ShadowOverlap::SideJoin& sideJoin, int& iterations)
+{
+  MiPt::LaunchTimer&         timer      = pt->timer;
+  const MiPt::ShadowOverlap& side       = pt->shadowOverlap;
+  const hipStream_t          stream     = c.stream;
+  const bool                 debugSpans = pt->sw.traceSpans, guides = (params->flags & MI_PT_USE_OPTIX_DENOISER) != 0;
+  pt::launchResetCounters(c.queues, stream);
+  // 8-wide BVH: ONE kernel generates the camera rays, walks them as packets, finishes the paths that leave the scene and queues
+  // the hits (k_trace_primary); BVH2 / MI_PT_NO_PACKET: k_generate writes the rays and the per-lane kernel walks them
+  // bound camera rays: k_generate_rays takes the paths' rays from memory, then the per-lane walk, on both trees
+  const bool boundRays    = pt->cameraRays != nullptr;
+  const bool fusedPrimary = c.wide && !pt->sw.noPacket && !debugSpans && !boundRays;
+  if(fusedPrimary)
   {
-    // Per-bounce sort of the shade kernel (k_shade): grouping the hits by material pays where the materials take different ways
-    // through the BSDF (glass workload: generic shade kernel -11 %); where every material runs the same code (the SIMPLE
-    // kernel, which therefore has no sort at all) it only cost (helmet +4 %, atrium +12 %, street +4 % of the shade kernel).
-    // MI_PT_SORT = 0 | 1 | 2 is the A/B switch of the generic kernel.
-    c.sortMode = pt->sw.sortMode;
+    timer.timed(stream, TK_PRIMARY, [&] { pt::launchTracePrimary(c, s); });
+    if(timer.timingEnabled)
+      ++timer.accTiming.tracePrimaryLaunches;
   }
+  else if(boundRays)
+    timer.timed(stream, TK_GENERATE, [&] { pt::launchGenerateRays(c, pt->cameraRays, uint32_t(pt->cameraRaySets), (pt->cameraRayFlags & MI_PT_CAMERA_RAYS_UNIT) != 0, s); });
+  else
+    timer.timed(stream, TK_GENERATE, [&] { pt::launchGenerate(c, s); });
+  int       cur      = 0;
+  const int maxIters = maxIterationsOf(pt, params);
+  for(int it = 0; it < maxIters; ++it)
+  {
+    if(pt->hasVolumeScatter && it >= params->maxDepth && (it % 8) == 0)
+    {
+      bool drained = false;
+      if(int rc = queuesDrained(c, cur, drained))
+        return rc;
+      if(drained)
+        break;
+    }
+    if(debugSpans)
+      traceSpansIteration(pt, c, params, it, cur);
+    else
+    {
+      if(!(it == 0 && fusedPrimary))
+        timer.timed(stream, TK_TRACE, [&] { pt::launchTraceClosest(c, cur); });
+      if(overlap && it > 0)
+        (void)hipStreamWaitEvent(stream, side.evShadowed, 0);  // the previous bounce's shadow terms are in before this shade launch reads them
+      timer.timed(stream, it == 0 ? TK_SHADE_FIRST : TK_SHADE, [&] { pt::launchShade(c, cur, it == 0); });
+      if(it == 0 && timer.timingEnabled)
+        ++timer.accTiming.shadeFirstLaunches;
+      if(overlap)
+      {
+        (void)hipEventRecord(side.evShaded, stream);
+        (void)hipStreamWaitEvent(side.sideStream, side.evShaded, 0);
+        timer.timed(side.sideStream, TK_SHADOW, [&] { pt::launchTraceShadow(cSide, cur ^ 1); });
+        (void)hipEventRecord(side.evShadowed, side.sideStream);
+        sideJoin.outstanding = true;
+      }
+      else
+        timer.timed(stream, TK_SHADOW, [&] { pt::launchTraceShadow(c, cur ^ 1); });
+    }
+    ++iterations;
+    cur ^= 1;
+  }
+  if(overlap && iterations > 0)
+  {
+    (void)hipStreamWaitEvent(stream, side.evShadowed, 0);  // the last bounce's shadow terms, before the sample is folded
+    sideJoin.outstanding = false;                          // (joined: the caller's stream now orders everything after the side stream's work)
+  }
+  // paths the loop left alive (its iteration bound cut them: volume random walks) hand their radiance and seed over by slot
+  if(c.fc.stateInQueue && (pt->hasVolumeScatter || pt->sw.maxItersDiag > 0))
+    pt::launchFlushSurvivors(c, cur);
+  timer.timed(stream, TK_ACCUM, [&] {
+    pt::launchFinishSample(c, s, pt->accum, pt->depthImg(), guides ? pt->albedoImg() : nullptr, guides ? pt->normalImg() : nullptr);
+  });
+  return MI_PT_OK;
+}
+
+// What follows a first-frame batch: the selection image, and with motion vectors on the pose's motion image and the snapshot of its positions
+static void afterFirstFrame(MiPt* pt, const pt::LaunchCtx& c, const MiPathtraceParams* params)
+{
+  const hipStream_t stream = c.stream;
+  if(pt->cameraRays)  // (the set of the batch's first frame)
+    pt::launchSelectionRays(c, pt->cameraRays, uint32_t(params->frameCount) % uint32_t(pt->cameraRaySets), pt->selection.ptr);
+  else
+    pt::launchSelection(c, pt->selection.ptr);
+  pt->haveFirstHit = true;
+  if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
+  {
+    pt::launchMotionVectors(pt->firstHit.ptr, pt->firstHitTri.ptr, pt->vm.prims.ptr, int(pt->vm.prims.count), pt->ownedTiles.ptr, uint32_t(pt->numSlots),
+                            c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr, pt->temporalData.prevObjectToWorld.ptr, int(pt->nodes.count),
+                            pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->temporalData.motion.ptr, stream);
+    pt->temporalData.haveMotion = true;
+    if(pt->firstHitTri.ptr)  // vertex motion: the rendered pose's positions become the next pose's previous ones, when an update changed them
+    {
+      pt->haveFirstHitTri = true;
+      if(pt->vm.poseDirty)
+        pt::launchSnapshotPositions(pt->vm.prims.ptr, pt->vm.deformIDs.ptr, uint32_t(pt->vm.deformIDs.count), pt->vm.maxVertices, stream);
+      pt->vm.poseDirty = false;
+    }
+  }
+}
+
+int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames, void* hipStream)
+{
+  FLUSH_PENDING(pt);
+  if(!pt || !params)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frame: null argument");
+  if(numFrames < 1 || numFrames > 1024)
+    return fail(MI_PT_ERR_ARGUMENT, "mi_pt_render_frames: 1 <= numFrames <= 1024 required");
+  if(int rc = refuseBeforeResize(pt))
+    return rc;
+  if(int rc = refuseSamplesOrDepth(params))
+    return rc;
+  if((pt->frameInfo.flags & MI_SCENE_USE_HDR_ENVIRONMENT) && !pt->scene.envPixels)
+    return fail(MI_PT_ERR_STATE, "mi_pt_render_frame: HDR environment requested but none was set");
+  if(pt->cameraRaysStale())
+    return fail(MI_PT_ERR_STATE, MiPt::CAMERA_RAYS_STALE);
+  HIP_TRY(hipSetDevice(pt->device));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hipStream);
+  pt->lastStream     = stream;
+  if(pt->numSlots == 0)
+    return MI_PT_OK;
+  if(numFrames > pt->framesCap)  // grow the path/queue arrays once; later batches of this size reuse them
+  {
+    HIP_TRY(hipDeviceSynchronize());
+    if(int rc = allocPathResources(pt, numFrames))
+      return rc;
+  }
+
+  if(int rc = pt->skyConsts.upToDate(pt->sky, stream))
+    return rc;
+  if(int rc = ensureOptionalPathArrays(pt, stateBySlot(pt), params->numSamples > 1, (params->flags & MI_PT_USE_OPTIX_DENOISER) != 0, catcherFrame(pt)))
+    return rc;
+  pt::LaunchCtx c = launchContextOf(pt, params, numFrames, stream);
   // descriptor copies for the kernels that read them through a pointer
   if(pt->sceneDevDirty)
   {
@@ -3010,221 +3387,41 @@ int mi_pt_render_frames(MiPt* pt, const MiPathtraceParams* params, int numFrames
     HIP_TRY(pt->sceneDev.upload(&pt->scene, 1));
     pt->sceneDevDirty = false;
   }
-  if(!pt->fcHost)
-  {
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pt->fcHost), sizeof(pt::FrameConsts) * MiPt::FC_RING, hipHostMallocDefault));
-    HIP_TRY(pt->fcRing.alloc(MiPt::FC_RING));
-    for(hipEvent_t& e : pt->fcDone)
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const unsigned fcSlot = pt->fcCursor++ % unsigned(MiPt::FC_RING);
-  if(pt->fcCursor > unsigned(MiPt::FC_RING))
-    HIP_TRY(hipEventSynchronize(pt->fcDone[fcSlot]));  // the batch that used this slot FC_RING calls ago must have drained
-  pt->fcHost[fcSlot] = c.fc;
-  HIP_TRY(hipMemcpyAsync(pt->fcRing.ptr + fcSlot, pt->fcHost + fcSlot, sizeof(pt::FrameConsts), hipMemcpyHostToDevice, stream));
-  c.sceneDev = pt->sceneDev.ptr;
-  c.fcDev    = pt->fcRing.ptr + fcSlot;
+  c.sceneDev      = pt->sceneDev.ptr;
+  unsigned fcSlot = 0;
+  if(int rc = pt->fcConsts.claim(c.fc, stream, &c.fcDev, &fcSlot))
+    return rc;
 
-  auto timedOn = [&](hipStream_t on, int kind, auto&& launch) {
-    if(pt->timingEnabled)
-    {
-      hipEvent_t a = getEvent(pt, pt->evCursor), b = getEvent(pt, pt->evCursor);
-      (void)hipEventRecord(a, on);
-      launch();
-      (void)hipEventRecord(b, on);
-      pt->pendingSpans.push_back({kind, a, b});
-    }
-    else
-      launch();
-  };
-  auto timed = [&](int kind, auto&& launch) { timedOn(stream, kind, launch); };
-  hipEvent_t frameA = nullptr, frameB = nullptr;
-  if(pt->timingEnabled)
+  MiPt::LaunchTimer& timer  = pt->timer;
+  hipEvent_t         frameA = nullptr, frameB = nullptr;
+  if(timer.timingEnabled)
   {
-    frameA = getEvent(pt, pt->evCursor);
-    frameB = getEvent(pt, pt->evCursor);
+    frameA = timer.getEvent();
+    frameB = timer.getEvent();
     (void)hipEventRecord(frameA, stream);
   }
-  int iterations = 0, traceLaunches = 0, shadeLaunches = 0, shadowLaunches = 0;
-  const bool usePacket = !pt->sw.noPacket;
-  const bool debugSpans = pt->sw.traceSpans;
-  // Small batches: a bounce's shadow stage (any-hit walk + resolve) on a second stream, next to the NEXT bounce's closest-hit walk.  The two
-  // are independent -- the walk reads the continuation rays the shade launch wrote, the shadow stage adds into radiance records that only
-  // the next SHADE launch reads (which therefore waits for it) -- and with few frames in flight neither fills the 256 CUs: most
-  // workgroups of a persistent grid find no work and leave, so the other kernel's find room.  Needs the state in the queue entry (on
-  // catcher frames the resolve pass may end a path the walk is about to trace).
-  // ... and launches long enough to be worth two cross-stream hand-overs per bounce: measured (round 4, frames in flight 1 / 4 / 8 / 16 / 32 / 64 / 128)
-  // atrium-class (406 k triangles, depth 12) +15 / +8 / +6 / +3.5 / +1.7 / +1.0 / +0.3 %, street-class 4K +8 % at 1, +1.6 % at 8, +0.3 % from 32;
-  // helmet-class (74 k, 60 % of the camera paths leave at bounce 0) -6.5 / -0.4 / -0.8 / -0.6 %: scenes below 2e5 triangles keep one stream.
-  // Default up to 32 frames: the interactive range, where it pays; larger batches fill the device by themselves, and their per-launch times
-  // (bench.py's kernel table) stay those of kernels that have the device to themselves.
-  // Volume-scatter scenes run it at every batch size and triangle count: their random walks leave ~100 bounce iterations of a few thousand paths per
-  // batch, three dependent launches each, and taking the shadow stage off that chain measured +31 % for a single frame, +8.7 % at 32 and +2.2 % at 256
-  // frames in flight on the glass-class workload (the host's poll of the queue length every eighth iteration only waits for the main stream).
-  bool overlap = pt->sw.overlapUpTo > 0 && ((numFrames <= pt->sw.overlapUpTo && pt->scene.numTris >= pt->sw.overlapMinTris) || pt->hasVolumeScatter)
-                 && c.fc.stateInQueue != 0 && !debugSpans;
-  if(overlap && !pt->sideStream)
-    overlap = hipStreamCreateWithFlags(&pt->sideStream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&pt->evShaded, hipEventDisableTiming) == hipSuccess
-              && hipEventCreateWithFlags(&pt->evShadowed, hipEventDisableTiming) == hipSuccess;
-  pt::LaunchCtx cSide = c;
-  cSide.stream        = pt->sideStream;
-  // Any early return below (a failed queue poll, a launch error) must not leave shadow-stage work queued on the side stream behind the caller's
-  // back: a caller that synchronises its own stream and then resizes or updates would race with kernels still adding into the radiance records.
-  // On every exit taken while a shadow stage is outstanding the side stream is drained (error paths only: the ordinary path joins it by event).
-  struct SideJoin
-  {
-    hipStream_t side        = nullptr;
-    bool        outstanding = false;
-    ~SideJoin()
-    {
-      if(outstanding && side)
-        (void)hipStreamSynchronize(side);
-    }
-  } sideJoin;
-  sideJoin.side = overlap ? pt->sideStream : nullptr;
+  const bool    overlap = wantsOverlap(pt, c) && pt->shadowOverlap.ready();
+  pt::LaunchCtx cSide   = c;
+  cSide.stream          = pt->shadowOverlap.sideStream;
+  MiPt::ShadowOverlap::SideJoin sideJoin;
+  sideJoin.side  = overlap ? pt->shadowOverlap.sideStream : nullptr;
+  int iterations = 0;
   for(int s = 0; s < params->numSamples; ++s)
-  {
-    pt::launchResetCounters(c.queues, stream);
-    // 8-wide BVH: ONE kernel generates the camera rays, walks them as packets, finishes the paths that leave the scene and queues
-    // the hits (k_trace_primary); BVH2 / MI_PT_NO_PACKET: k_generate writes the rays and the per-lane kernel walks them
-    // bound camera rays: k_generate_rays takes the paths' rays from memory, then the per-lane walk, on both trees
-    const bool boundRays    = pt->cameraRays != nullptr;
-    const bool fusedPrimary = c.wide && usePacket && !debugSpans && !boundRays;
-    if(fusedPrimary)
-    {
-      timed(TK_PRIMARY, [&] { pt::launchTracePrimary(c, s); });
-      if(pt->timingEnabled)
-        ++pt->accTiming.tracePrimaryLaunches;
-    }
-    else if(boundRays)
-      timed(TK_GENERATE, [&] { pt::launchGenerateRays(c, pt->cameraRays, uint32_t(pt->cameraRaySets), (pt->cameraRayFlags & MI_PT_CAMERA_RAYS_UNIT) != 0, s); });
-    else
-      timed(TK_GENERATE, [&] { pt::launchGenerate(c, s); });
-    int cur = 0;
-    // Every iteration either ends a path or consumes one unit of surfaceDepth, except volume scatter events
-    // (pathtrace_functions.h.slang:925-931), which are free for VOLUME_FREE_BUDGET bounces and then Russian-rouletted.
-    int maxIters = params->maxDepth;
-    // a shadow-catcher bounce does not consume surfaceDepth (eEarlyContinue) but is always followed by a miss or a surface hit
-    if((pt->frameInfo.flags & MI_SCENE_USE_INFINITE_PLANE) && (pt->frameInfo.flags & MI_SCENE_INFINITE_PLANE_SHADOW_CATCHER))
-      maxIters = 2 * params->maxDepth + 2;
-    if(pt->hasVolumeScatter)
-      maxIters = params->maxDepth * 66 + 512;
-    if(pt->sw.maxItersDiag > 0)
-      maxIters = std::min(maxIters, pt->sw.maxItersDiag);
-    for(int it = 0; it < maxIters; ++it)
-    {
-      if(pt->hasVolumeScatter && it >= params->maxDepth && (it % 8) == 0)
-      {
-        uint32_t counts[2 * pt::NSUB];
-        HIP_TRY(hipMemcpyAsync(counts, &c.queues.counters[cur ? pt::QC_PAIR1 : pt::QC_PAIR0], sizeof(counts), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        uint32_t remaining = 0;
-        for(int q = 0; q < pt::NSUB; ++q)
-          remaining += counts[2 * q];
-        if(remaining == 0)
-          break;
-      }
-      if(debugSpans)  // MI_PT_TRACE_SPANS=1: per-launch wall time and queue lengths (synchronising; diagnostics only)
-      {
-        auto count = [&](int base) {  // base: first of 16 tails stored 2 words apart
-          uint32_t v[2 * pt::NSUB];
-          (void)hipMemcpy(v, &c.queues.counters[base], sizeof(uint32_t) * (2 * pt::NSUB - 1), hipMemcpyDeviceToHost);
-          uint32_t t = 0;
-          for(int q = 0; q < pt::NSUB; ++q) t += v[2 * q];
-          return t;
-        };
-        auto span = [&](auto&& launch) {
-          (void)hipStreamSynchronize(stream);
-          auto t0 = std::chrono::steady_clock::now();
-          launch();
-          (void)hipStreamSynchronize(stream);
-          return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        };
-        auto segs = [&]() {
-          pt::StatCounters h{};
-          (void)hipMemcpy(&h, pt->stats.ptr, sizeof(h), hipMemcpyDeviceToHost);
-          return h;
-        };
-        uint32_t nIn = count(cur ? pt::QC_PAIR1 : pt::QC_PAIR0);
-        const pt::StatCounters s0 = segs();
-        double   tTrace = span([&] { pt::launchTraceClosest(c, cur); });
-        const pt::StatCounters s1 = segs();
-        double   tShade = span([&] { pt::launchShade(c, cur, it == 0); });
-        uint32_t nSh    = count((cur ? pt::QC_PAIR0 : pt::QC_PAIR1) + 1);
-        double   tShadow = span([&] { pt::launchTraceShadow(c, cur ^ 1); });
-        const pt::StatCounters s2 = segs();
-        fprintf(stderr, "[mi_pt span] frame %d it %2d rays %8u (traced %8llu, nodes %9llu tris %9llu) trace %8.3f ms shade %8.3f ms | shadow rays %8u (traced %8llu, nodes %9llu tris %9llu) %8.3f ms\n",
-                params->frameCount, it, nIn, (unsigned long long)(s1.segments - s0.segments), (unsigned long long)(s1.nodesClosest - s0.nodesClosest),
-                (unsigned long long)(s1.trisClosest - s0.trisClosest), tTrace, tShade, nSh, (unsigned long long)(s2.shadowRays - s1.shadowRays),
-                (unsigned long long)(s2.nodesShadow - s1.nodesShadow), (unsigned long long)(s2.trisShadow - s1.trisShadow), tShadow);
-      }
-      else
-      {
-        if(!(it == 0 && fusedPrimary))
-          timed(TK_TRACE, [&] { pt::launchTraceClosest(c, cur); });
-        if(overlap && it > 0)
-          (void)hipStreamWaitEvent(stream, pt->evShadowed, 0);  // the previous bounce's shadow terms are in before this shade launch reads them
-        timed(it == 0 ? TK_SHADE_FIRST : TK_SHADE, [&] { pt::launchShade(c, cur, it == 0); });
-        if(it == 0 && pt->timingEnabled)
-          ++pt->accTiming.shadeFirstLaunches;
-        if(overlap)
-        {
-          (void)hipEventRecord(pt->evShaded, stream);
-          (void)hipStreamWaitEvent(pt->sideStream, pt->evShaded, 0);
-          timedOn(pt->sideStream, TK_SHADOW, [&] { pt::launchTraceShadow(cSide, cur ^ 1); });
-          (void)hipEventRecord(pt->evShadowed, pt->sideStream);
-          sideJoin.outstanding = true;
-        }
-        else
-          timed(TK_SHADOW, [&] { pt::launchTraceShadow(c, cur ^ 1); });
-      }
-      ++iterations; ++traceLaunches; ++shadeLaunches; ++shadowLaunches;
-      cur ^= 1;
-    }
-    if(overlap && iterations > 0)
-    {
-      (void)hipStreamWaitEvent(stream, pt->evShadowed, 0);  // the last bounce's shadow terms, before the sample is folded
-      sideJoin.outstanding = false;                         // (joined: the caller's stream now orders everything after the side stream's work)
-    }
-    // paths the loop left alive (its iteration bound cut them: volume random walks) hand their radiance and seed over by slot
-    if(c.fc.stateInQueue && (pt->hasVolumeScatter || pt->sw.maxItersDiag > 0))
-      pt::launchFlushSurvivors(c, cur);
-    timed(TK_ACCUM, [&] {
-      pt::launchFinishSample(c, s, pt->accum, pt->depthImg(), guides ? pt->albedoImg() : nullptr, guides ? pt->normalImg() : nullptr);
-    });
-  }
+    if(int rc = renderSample(pt, c, cSide, params, s, overlap, sideJoin, iterations))
+      return rc;
   if(params->flags & MI_PT_FIRST_FRAME)
-  {
-    if(pt->cameraRays)  // (the set of the batch's first frame)
-      pt::launchSelectionRays(c, pt->cameraRays, uint32_t(params->frameCount) % uint32_t(pt->cameraRaySets), pt->selection.ptr);
-    else
-      pt::launchSelection(c, pt->selection.ptr);
-    pt->haveFirstHit = true;
-    if(pt->temporal)  // the pose's motion image, then its matrices become the next pose's previous ones
-    {
-      pt::launchMotionVectors(pt->firstHit.ptr, pt->firstHitTri.ptr, pt->vm.prims.ptr, int(pt->vm.prims.count), pt->ownedTiles.ptr, uint32_t(pt->numSlots),
-                              c.fc.tileShift, pt->width, pt->height, pt->nodes.ptr, pt->temporalData.prevObjectToWorld.ptr, int(pt->nodes.count),
-                              pt->frameInfo.viewProjMatrix, pt->frameInfo.prevMVP, pt->temporalData.motion.ptr, stream);
-      pt->temporalData.haveMotion = true;
-      if(pt->firstHitTri.ptr)  // vertex motion: the rendered pose's positions become the next pose's previous ones, when an update changed them
-      {
-        pt->haveFirstHitTri = true;
-        if(pt->vm.poseDirty)
-          pt::launchSnapshotPositions(pt->vm.prims.ptr, pt->vm.deformIDs.ptr, uint32_t(pt->vm.deformIDs.count), pt->vm.maxVertices, stream);
-        pt->vm.poseDirty = false;
-      }
-    }
-  }
+    afterFirstFrame(pt, c, params);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(pt->fcDone[fcSlot], stream));
-  if(pt->timingEnabled)
+  if(int rc = pt->fcConsts.recordDone(fcSlot, stream))
+    return rc;
+  if(timer.timingEnabled)
   {
     (void)hipEventRecord(frameB, stream);
-    pt->pendingSpans.push_back({TK_COUNT, frameA, frameB});
-    pt->accTiming.traceClosestLaunches += traceLaunches;
-    pt->accTiming.shadeLaunches += shadeLaunches;
-    pt->accTiming.traceShadowLaunches += shadowLaunches;
-    pt->accTiming.bounceIterations += iterations;
+    timer.pendingSpans.push_back({TK_COUNT, frameA, frameB});
+    timer.accTiming.traceClosestLaunches += iterations;
+    timer.accTiming.shadeLaunches += iterations;
+    timer.accTiming.traceShadowLaunches += iterations;
+    timer.accTiming.bounceIterations += iterations;
   }
   return MI_PT_OK;
 }
@@ -3860,7 +4057,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_get_memory: null argument");
   HIP_TRY(hipSetDevice(pt->device));
   // The feature groups sum themselves (MiPt::*::bytes()); every other buffer is named here.  Four small ones are in neither total, as they
-  // never were: matDirty, skyPre, tmHistogram and tmAutoState.  Counting them is a change of what the totals report, not of this bookkeeping.
+  // never were: matDirty, skyConsts.skyPre, tmHistogram and tmAutoState.  Counting them is a change of what the totals report, not of this bookkeeping.
   const uint64_t scene = pt->materials.bytes() + pt->texInfos.bytes() + pt->nodes.bytes() + pt->prims.bytes() + pt->lights.bytes() + pt->textures.bytes() + pt->texels.bytes() + pt->texQuads.bytes()
                          + pt->geometry.bytes() + pt->instFlags.bytes() + pt->srgbLut.bytes() + pt->envPixels.bytes() + pt->envAccel.bytes() + pt->texRefs.bytes()
                          + pt->coreTex.bytes() + pt->deform.bytes() + pt->vm.bytes() + pt->vu.bytes() + pt->tuTables.bytes() + pt->accel.bytes();
@@ -3868,7 +4065,7 @@ int mi_pt_get_memory(MiPt* pt, MiPtMemory* out)
                              + pt->optShadowAux2.bytes() + pt->queueMem.bytes() + pt->queuePayload.bytes() + pt->candPool.bytes() + pt->candLists.bytes();
   const uint64_t renderer = pathState + pt->firstHit.bytes() + pt->accumOwn.bytes()
                             + pt->albedo.bytes() + pt->normal.bytes() + pt->denoiseA.bytes() + pt->denoiseB.bytes() + pt->tonemapped.bytes() + pt->depth.bytes()
-                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->euScratch.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcRing.bytes() + pt->stats.bytes()
+                            + pt->selection.bytes() + pt->cameraRaysOwn.bytes() + pt->allTiles.bytes() + pt->queryRays.bytes() + pt->queryHits.bytes() + pt->vuStaging.bytes() + pt->tuStaging.bytes() + pt->euScratch.bytes() + pt->ownedTiles.bytes() + pt->sceneDev.bytes() + pt->fcConsts.fcRing.bytes() + pt->stats.bytes()
                             + pt->temporalData.bytes() + pt->firstHitTri.bytes();
   size_t freeB = 0, totalB = 0;
   HIP_TRY(hipMemGetInfo(&freeB, &totalB));
@@ -3919,12 +4116,11 @@ int mi_pt_enable_timing(MiPt* pt, int enable)
   FLUSH_PENDING(pt);
   if(!pt)
     return fail(MI_PT_ERR_ARGUMENT, "mi_pt_enable_timing: null instance");
-  pt->timingEnabled = enable != 0;
+  pt->timer.timingEnabled = enable != 0;
   if(enable)
   {
-    pt->pendingSpans.clear();
-    pt->evCursor  = 0;
-    pt->accTiming = MiPtFrameTiming{};
+    pt->timer.reset();
+    pt->timer.accTiming = MiPtFrameTiming{};
   }
   return MI_PT_OK;
 }
@@ -3936,27 +4132,8 @@ int mi_pt_get_frame_timing(MiPt* pt, MiPtFrameTiming* out)
   // Totals since mi_pt_enable_timing(1): resolves the recorded events (one device synchronisation, here, not per frame).
   HIP_TRY(hipSetDevice(pt->device));
   HIP_TRY(hipDeviceSynchronize());
-  MiPtFrameTiming& t = pt->accTiming;
-  for(const MiPt::Span& sp : pt->pendingSpans)
-  {
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, sp.a, sp.b);
-    switch(sp.kind)
-    {
-      case TK_GENERATE: t.generateMs += ms; break;
-      case TK_TRACE: t.traceClosestMs += ms; break;
-      case TK_SORT: t.sortMs += ms; break;
-      case TK_SHADE: t.shadeMs += ms; break;
-      case TK_PRIMARY: t.traceClosestMs += ms; t.tracePrimaryMs += ms; break;
-      case TK_SHADE_FIRST: t.shadeMs += ms; t.shadeFirstMs += ms; break;
-      case TK_SHADOW: t.traceShadowMs += ms; break;
-      case TK_ACCUM: t.accumulateMs += ms; break;
-      default: t.totalMs += ms; break;
-    }
-  }
-  pt->pendingSpans.clear();
-  pt->evCursor = 0;
-  *out         = t;
+  pt->timer.resolve();
+  *out = pt->timer.accTiming;
   return MI_PT_OK;
 }
 }
