@@ -24,7 +24,8 @@
 // orders them by octant, quantises their boxes and writes the 80-byte record; a prefix sum over the level hands every node the indices of its inner children (= the next level's
 // work list, breadth-first order) and the positions of its leaf triangles.  Two kernels and one scan per level, ~10 levels.  The
 // single-threaded host collapse it replaces (0.6 s of a 0.86 s scene build at 2.6 M triangles in round 1) is kept behind
-// MI_PT_HOST_COLLAPSE=1 as the A/B reference: both emit the same node array.
+// MI_PT_HOST_COLLAPSE=1 as the A/B reference and serves the one-triangle scene; it lives in `bvh8_collapse_host.h` and is tested on the CPU
+// (tests/test_bvh8_collapse_on_host.py).  Both emit the same node array from the greedy opening, quantised by one text (bvh_refit.h).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -34,9 +35,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <vector>
 
+#include "bvh8_collapse_host.h"
 #include "bvh_refit.h"
 #include "pt_build.h"
 #include "pt_ticket.h"
@@ -46,26 +47,15 @@ namespace pt {
 
 namespace {
 
-// (Node8, the 80-byte record: bvh_refit.h, shared with the refit)
+// (Node8, the 80-byte record: bvh_refit.h, shared with the refit; Cand8, childRef2, triCount2, childBox2, boxArea8: bvh8_collapse_host.h, one
+//  text for this collapse and the host's)
 
-// Largest leaf child: 2 triangles.  Two bits of the node's 16-bit valid mask belong to
+// Largest leaf child: 2 triangles (BVH8_MAX_LEAF, bvh8_collapse_host.h: the host collapse opens by the same size).  Two bits of the node's 16-bit valid mask belong to
 // a slot, so a leaf child holds one or two triangles -- which is also what measured best when the mask had room for three and four
 // (round 2: 2 beats 1, 3 and 4 on the helmet, atrium and street workloads, +0.4 .. +2.5 % over 3).
 // SAH-optimal collapse by default: against the greedy one (MI_PT_COLLAPSE=greedy) 40 % fewer, fuller nodes (atrium 68.8 k -> 44 k),
 // node visits per secondary ray 19.74 -> 19.27 (atrium), 28.66 -> 27.55 (street), 8.01 -> 7.91 (helmet), and
 // atrium 482 -> 490, street 512 -> 518, helmet 3799 -> 3878, glass 537 -> 551 Msamples/s (round 3)
-
-struct Cand
-{
-  int   ref;  // >= 0 BVH2 inner node, < 0 leaf (~sorted triangle index)
-  float lo[3], hi[3];
-};
-
-float areaOf(const Cand& c)
-{
-  float ex = c.hi[0] - c.lo[0], ey = c.hi[1] - c.lo[1], ez = c.hi[2] - c.lo[2];
-  return ex * ey + ey * ez + ez * ex;
-}
 
 __global__ void k_reorder_tris(uint32_t n, const uint32_t* perm, const DevTri* in, DevTri* out)
 {
@@ -74,32 +64,7 @@ __global__ void k_reorder_tris(uint32_t n, const uint32_t* perm, const DevTri* i
     out[i] = in[perm[i]];
 }
 
-
-// ---- device collapse -----------------------------------------------------------------------------------------------------------
-struct DCand
-{
-  int   ref;  // >= 0 BVH2 inner node, < 0 leaf (~triangle index in BVH2 order)
-  float lo[3], hi[3];
-};
-__device__ __forceinline__ int d_childRef(const float4* nodes2, int node, int which)
-{
-  const float4 n3 = nodes2[size_t(node) * 4 + 3];
-  return __float_as_int(which == 0 ? n3.x : n3.y);
-}
-__device__ __forceinline__ uint32_t d_triCount(const float4* nodes2, int ref) { return ref >= 0 ? uint32_t(__float_as_int(nodes2[size_t(ref) * 4 + 3].z)) : 1u; }
-__device__ __forceinline__ void d_childBox(const float4* nodes2, int node, int which, float lo[3], float hi[3])
-{
-  const float4 n0 = nodes2[size_t(node) * 4 + 0], n1 = nodes2[size_t(node) * 4 + 1], n2 = nodes2[size_t(node) * 4 + 2];
-  if(which == 0) { lo[0] = n0.x; hi[0] = n0.y; lo[1] = n0.z; hi[1] = n0.w; lo[2] = n2.x; hi[2] = n2.y; }
-  else           { lo[0] = n1.x; hi[0] = n1.y; lo[1] = n1.z; hi[1] = n1.w; lo[2] = n2.z; hi[2] = n2.w; }
-}
-__device__ __forceinline__ float d_area(const DCand& c)
-{
-  const float ex = c.hi[0] - c.lo[0], ey = c.hi[1] - c.lo[1], ez = c.hi[2] - c.lo[2];
-  return __fadd_rn(__fadd_rn(__fmul_rn(ex, ey), __fmul_rn(ey, ez)), __fmul_rn(ez, ex));  // (fixed association; NB __fmul_rn / __fadd_rn are a plain * and + in this
-                                                                                         //  ROCm and hipcc may still fuse them -- bvh_reinsert.h: r2Area, where the bits matter, uses the pragma)
-}
-// ---- SAH-optimal collapse (Ylitie, Karras, Laine 2017, section 3.2) ------------------------------------------------------------
+// ---- device collapse: SAH-optimal collapse (Ylitie, Karras, Laine 2017, section 3.2) ------------------------------------------------------------
 // cost[n][i], i = 1..7: the cheapest way to represent the BVH2 subtree n as AT MOST i children of some 8-wide node -- each such child
 // either a leaf (the subtree has <= maxLeaf triangles; cost = area x C_TRI x triangles) or an inner 8-wide node (cost = area x 1 +
 // the cheapest forest of <= 8 children below it).  C_TRI = 56 / 235: a triangle test against a node visit in vector instructions.
@@ -113,11 +78,6 @@ struct DpTables
   float*  cost;   // numInner x 8 ([0] unused)
   int8_t* split;  // numInner x 8
 };
-__device__ __forceinline__ float d_boxArea(const float lo[3], const float hi[3])
-{
-  const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-  return __fadd_rn(__fadd_rn(__fmul_rn(ex, ey), __fmul_rn(ey, ez)), __fmul_rn(ez, ex));
-}
 __global__ void k_dp_parents(int numInner, const float4* nodes2, int* parent, int* leafParent, int root)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,7 +85,7 @@ __global__ void k_dp_parents(int numInner, const float4* nodes2, int* parent, in
     return;
   for(int k = 0; k < 2; ++k)
   {
-    const int c = d_childRef(nodes2, i, k);
+    const int c = childRef2(nodes2, i, k);
     if(c >= 0)
       parent[c] = i;
     else
@@ -141,17 +101,17 @@ __device__ void d_dpSolve(const float4* nodes2, DpTables dp, int nd, uint32_t ma
   float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
   for(int k = 0; k < 2; ++k)
   {
-    ref[k] = d_childRef(nodes2, nd, k);
+    ref[k] = childRef2(nodes2, nd, k);
     float l[3], h[3];
-    d_childBox(nodes2, nd, k, l, h);
-    leafCost[k] = d_boxArea(l, h) * DP_C_TRI;
+    childBox2(nodes2, nd, k, l, h);
+    leafCost[k] = boxArea8(l, h) * DP_C_TRI;
     for(int a = 0; a < 3; ++a)
     {
       lo[a] = fminf(lo[a], l[a]);
       hi[a] = fmaxf(hi[a], h[a]);
     }
   }
-  const float area = d_boxArea(lo, hi);
+  const float area = boxArea8(lo, hi);
   // The cost tables are what one thread of this kernel writes and another (the solver of the parent, possibly on another XCD) reads: they go through
   // agent-scope relaxed atomic loads and stores (coherent past the per-XCD L2s), ordered against the ticket in k_dp_solve by the stores'
   // acknowledgement -- not through plain stores between two device-scope fences, which cost an L2 write-back + invalidate per thread and level
@@ -191,7 +151,7 @@ __device__ void d_dpSolve(const float4* nodes2, DpTables dp, int nd, uint32_t ma
     }
   }
   inner += area;
-  const uint32_t cnt  = d_triCount(nodes2, nd);
+  const uint32_t cnt  = triCount2(nodes2, nd);
   const float    leaf = cnt <= maxLeaf ? area * DP_C_TRI * float(cnt) : FLT_MAX;
   c[0] = 0.0f;
   c[1] = leaf <= inner ? leaf : inner;
@@ -228,10 +188,10 @@ __device__ __forceinline__ bool d_isInner(const float4* nodes2, const DpTables& 
     return false;
   if(dp.split)
     return dp.split[size_t(ref) * 8 + 1] != 0;
-  return d_triCount(nodes2, ref) > maxLeaf;
+  return triCount2(nodes2, ref) > maxLeaf;
 }
 // The children of the 8-wide node rooted at BVH2 node `ref` as the DP tables chose them.
-__device__ int d_expandDp(const float4* nodes2, const DpTables& dp, int ref, DCand cands[8])
+__device__ int d_expandDp(const float4* nodes2, const DpTables& dp, int ref, Cand8 cands[8])
 {
   struct Item
   {
@@ -240,8 +200,8 @@ __device__ int d_expandDp(const float4* nodes2, const DpTables& dp, int ref, DCa
   Item stack[16];
   int  sp = 0, count = 0;
   const int k0 = dp.split[size_t(ref) * 8 + 0];
-  stack[sp++] = Item{d_childRef(nodes2, ref, 1), ref, 1, 8 - k0};  // (right first: popped last, so the children come out left to right)
-  stack[sp++] = Item{d_childRef(nodes2, ref, 0), ref, 0, k0};
+  stack[sp++] = Item{childRef2(nodes2, ref, 1), ref, 1, 8 - k0};  // (right first: popped last, so the children come out left to right)
+  stack[sp++] = Item{childRef2(nodes2, ref, 0), ref, 0, k0};
   while(sp > 0)
   {
     const Item it = stack[--sp];
@@ -252,22 +212,22 @@ __device__ int d_expandDp(const float4* nodes2, const DpTables& dp, int ref, DCa
       if(count < 8)
       {
         cands[count].ref = it.ref;
-        d_childBox(nodes2, it.parentNode, it.which, cands[count].lo, cands[count].hi);
+        childBox2(nodes2, it.parentNode, it.which, cands[count].lo, cands[count].hi);
         ++count;
       }
       continue;
     }
     if(sp + 2 <= 16)
     {
-      stack[sp++] = Item{d_childRef(nodes2, it.ref, 1), it.ref, 1, sh - sv};
-      stack[sp++] = Item{d_childRef(nodes2, it.ref, 0), it.ref, 0, sv};
+      stack[sp++] = Item{childRef2(nodes2, it.ref, 1), it.ref, 1, sh - sv};
+      stack[sp++] = Item{childRef2(nodes2, it.ref, 0), it.ref, 0, sv};
     }
   }
   return count;
 }
 // The children of the 8-wide node that starts at BVH2 node `ref`: greedy, always open the inner child of largest surface area that
 // holds more than maxLeaf triangles, until there are eight (or nothing left to open).  Returns how many, and the leaf size used.
-__device__ int d_expand(const float4* nodes2, const DpTables& dp, int ref, uint32_t maxLeafIn, DCand cands[8], uint32_t& maxLeafOut)
+__device__ int d_expand(const float4* nodes2, const DpTables& dp, int ref, uint32_t maxLeafIn, Cand8 cands[8], uint32_t& maxLeafOut)
 {
   if(dp.split)
   {
@@ -281,17 +241,17 @@ __device__ int d_expand(const float4* nodes2, const DpTables& dp, int ref, uint3
     count = 2;
     for(int k = 0; k < 2; ++k)
     {
-      cands[k].ref = d_childRef(nodes2, ref, k);
-      d_childBox(nodes2, ref, k, cands[k].lo, cands[k].hi);
+      cands[k].ref = childRef2(nodes2, ref, k);
+      childBox2(nodes2, ref, k, cands[k].lo, cands[k].hi);
     }
     while(count < 8)
     {
       int   best  = -1;
       float bestA = -1.0f;
       for(int k = 0; k < count; ++k)
-        if(cands[k].ref >= 0 && d_triCount(nodes2, cands[k].ref) > maxLeaf)
+        if(cands[k].ref >= 0 && triCount2(nodes2, cands[k].ref) > maxLeaf)
         {
-          const float a = d_area(cands[k]);
+          const float a = boxArea8(cands[k].lo, cands[k].hi);
           if(a > bestA)
           {
             bestA = a;
@@ -301,16 +261,16 @@ __device__ int d_expand(const float4* nodes2, const DpTables& dp, int ref, uint3
       if(best < 0)
         break;
       const int r = cands[best].ref;
-      cands[best].ref = d_childRef(nodes2, r, 0);
-      d_childBox(nodes2, r, 0, cands[best].lo, cands[best].hi);
-      cands[count].ref = d_childRef(nodes2, r, 1);
-      d_childBox(nodes2, r, 1, cands[count].lo, cands[count].hi);
+      cands[best].ref = childRef2(nodes2, r, 0);
+      childBox2(nodes2, r, 0, cands[best].lo, cands[best].hi);
+      cands[count].ref = childRef2(nodes2, r, 1);
+      childBox2(nodes2, r, 1, cands[count].lo, cands[count].hi);
       ++count;
     }
     uint32_t leafTris = 0;
     for(int k = 0; k < count; ++k)
     {
-      const uint32_t tc = d_triCount(nodes2, cands[k].ref);
+      const uint32_t tc = triCount2(nodes2, cands[k].ref);
       leafTris += cands[k].ref < 0 ? 1u : (tc <= maxLeaf ? tc : 0u);
     }
     if(leafTris <= 31u || maxLeaf <= 3u)
@@ -326,13 +286,13 @@ __global__ void k_collapse_count(int numItems, const int* items, const float4* n
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= numItems)
     return;
-  DCand    cands[8];
+  Cand8    cands[8];
   uint32_t ml;
   const int count = d_expand(nodes2, dp, items[i], maxLeaf, cands, ml);
   uint32_t  inner = 0, tris = 0;
   for(int k = 0; k < count; ++k)
   {
-    const uint32_t tc = d_triCount(nodes2, cands[k].ref);
+    const uint32_t tc = triCount2(nodes2, cands[k].ref);
     if(d_isInner(nodes2, dp, cands[k].ref, ml))
       ++inner;
     else
@@ -350,7 +310,7 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
     return;
   if(i == numItems - 1)
     *totals = offsets[i] + counts[i];
-  DCand    cands[8];
+  Cand8    cands[8];
   uint32_t ml;
   const int count = d_expand(nodes2, dp, items[i], maxLeaf, cands, ml);
   // node frame
@@ -361,7 +321,7 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
       lo[a] = fminf(lo[a], cands[k].lo[a]);
       hi[a] = fmaxf(hi[a], cands[k].hi[a]);
     }
-  // octant-ordered slot assignment (greedy on dot(centroid - centre, slot diagonal)), ties by (candidate, slot) order
+  // octant-ordered slot assignment (greedy on dot(centroid - centre, slot diagonal)), ties by (candidate, slot) order; host twin: assignSlots8
   int  candOfSlot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   bool slotUsed[8] = {false, false, false, false, false, false, false, false}, done[8] = {false, false, false, false, false, false, false, false};
   for(int round = 0; round < count; ++round)
@@ -414,8 +374,8 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
   {
     if(candOfSlot[sl] < 0)
       continue;
-    const DCand&   c  = cands[candOfSlot[sl]];
-    const uint32_t tc = d_triCount(nodes2, c.ref);
+    const Cand8&   c  = cands[candOfSlot[sl]];
+    const uint32_t tc = triCount2(nodes2, c.ref);
     if(d_isInner(nodes2, dp, c.ref, ml))
     {
       N.imask |= uint8_t(1u << sl);
@@ -440,15 +400,15 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
             if(f < 0)
               for(int a = 0; a < 3; ++a) { b.lo[a] = c.lo[a]; b.hi[a] = c.hi[a]; }
             else
-              d_childBox(nodes2, f >> 1, f & 1, b.lo, b.hi);
+              childBox2(nodes2, f >> 1, f & 1, b.lo, b.hi);
             slotBox[triAt] = b;
           }
           perm[triAt++] = uint32_t(~r);
         }
         else
         {
-          stack[sp] = d_childRef(nodes2, r, 1); from[sp++] = 2 * r + 1;
-          stack[sp] = d_childRef(nodes2, r, 0); from[sp++] = 2 * r;
+          stack[sp] = childRef2(nodes2, r, 1); from[sp++] = 2 * r + 1;
+          stack[sp] = childRef2(nodes2, r, 0); from[sp++] = 2 * r;
         }
       }
     }
@@ -456,406 +416,158 @@ __global__ void k_collapse_emit(int numItems, const int* items, const float4* no
   nodes8[levelStart + uint32_t(i)] = N;
 }
 
-}  // namespace
-
-bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, std::string& err, const Bvh8Options& opt)
+// A failed call leaves what it was for and the HIP error's text in `err`; the DevBuf locals of the collapse that returns on it free what was allocated.
+bool hipOk(hipError_t e, const char* what, std::string& err)
 {
-  out                = Bvh8Output();
-  const uint32_t n   = b2.numTris;
-  if(n == 0)
-    return true;
-  auto check = [&](hipError_t e, const char* what) {
-    if(e != hipSuccess)
+  if(e != hipSuccess)
+    err = std::string(what) + ": " + hipGetErrorString(e);
+  return e == hipSuccess;
+}
+
+// ---- device collapse, one level at a time (see the header comment): fills `r` from a BVH2 with at least one inner node -------
+bool collapseOnDevice(const BvhBuildOutput& b2, const Bvh8Options& opt, hipStream_t stream, std::string& err, Bvh8Output& r)
+{
+  auto check = [&](hipError_t e, const char* what) { return hipOk(e, what, err); };
+  const uint32_t n = b2.numTris, numInner = b2.numNodes;
+  DevBuf<Node8>              dNodes;
+  DevBuf<int>                itemsA, itemsB;
+  DevBuf<uint32_t>           dPerm;
+  DevBuf<unsigned long long> counts, offsets, totals;
+  DevBuf<uint8_t>            scanTemp;
+  size_t                     scanBytes = 0;
+  uint32_t                   trisPlaced = 0;
+  DpTables                   dp{nullptr, nullptr};
+  DevBuf<float>              dpCost;
+  DevBuf<int8_t>             dpSplit;
+  DevBuf<int>                dpParent, dpLeafParent;
+  DevBuf<unsigned>           dpArrive;
+  // every 8-wide node is rooted at a distinct BVH2 inner node: numInner bounds their number and the length of any level
+  if(!check(dNodes.alloc(numInner), "alloc BVH8 nodes (worst case)")) return false;
+  if(!check(itemsA.alloc(numInner), "alloc level items")) return false;
+  if(!check(itemsB.alloc(numInner), "alloc level items")) return false;
+  if(!check(dPerm.alloc(n), "alloc perm")) return false;
+  if(opt.keepRefit)  // the refit data (bvh_refit.hip): the box each triangle slot was filed under
+    if(!check(r.slotBox.alloc(n), "alloc refit slot boxes")) return false;
+  if(!check(counts.alloc(numInner), "alloc counts")) return false;
+  if(!check(offsets.alloc(numInner), "alloc offsets")) return false;
+  if(!check(totals.alloc(1), "alloc totals")) return false;
+  if(!check(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, counts.ptr, offsets.ptr, int(numInner), stream), "scan size")) return false;
+  if(!check(scanTemp.alloc(scanBytes), "alloc scan")) return false;
+  const int root = b2.root;
+  if(!check(hipMemcpyAsync(itemsA.ptr, &root, sizeof(int), hipMemcpyHostToDevice, stream), "seed level 0")) return false;
+  uint32_t levelStart = 0, levelCount = 1;
+  uint32_t   maxLeaf = BVH8_MAX_LEAF;
+  // which BVH2 subtrees become the children of an 8-wide node (Bvh8Options; the images do not depend on it)
+  const bool sahDp   = opt.sahCollapse;
+  if(sahDp)
+  {
+    maxLeaf = std::min(maxLeaf, 3u);
+    if(!check(dpCost.alloc(8 * size_t(numInner)), "alloc DP cost")) return false;
+    if(!check(dpSplit.alloc(8 * size_t(numInner)), "alloc DP split")) return false;
+    if(!check(dpParent.alloc(numInner), "alloc DP parents")) return false;
+    if(!check(dpLeafParent.alloc(n), "alloc DP leaf parents")) return false;
+    if(!check(dpArrive.alloc(numInner), "alloc DP tickets")) return false;
+    if(!check(hipMemsetAsync(dpArrive.ptr, 0, sizeof(unsigned) * size_t(numInner), stream), "clear DP tickets")) return false;
+    dp = DpTables{dpCost.ptr, dpSplit.ptr};
+    hipLaunchKernelGGL(k_dp_parents, dim3((numInner + 255u) / 256u), dim3(256), 0, stream, int(numInner), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, root);
+    hipLaunchKernelGGL(k_dp_solve, dim3((n + 255u) / 256u), dim3(256), 0, stream, int(n), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, dpArrive.ptr, dp, maxLeaf);
+    if(!check(hipGetLastError(), "DP kernels")) return false;
+  }
+  while(levelCount > 0)
+  {
+    const unsigned g = (levelCount + 127u) / 128u;
+    hipLaunchKernelGGL(k_collapse_count, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr);
+    if(!check(hipcub::DeviceScan::ExclusiveSum(scanTemp.ptr, scanBytes, counts.ptr, offsets.ptr, int(levelCount), stream), "scan")) return false;
+    hipLaunchKernelGGL(k_collapse_emit, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr, offsets.ptr, levelStart,
+                       levelStart + levelCount, trisPlaced, dNodes.ptr, itemsB.ptr, dPerm.ptr, totals.ptr, r.slotBox.ptr);
+    r.levels.push_back(levelStart);
+    unsigned long long t = 0;
+    if(!check(hipGetLastError(), "collapse kernels")) return false;
+    if(!check(hipMemcpyAsync(&t, totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream), "read level totals")) return false;
+    if(!check(hipStreamSynchronize(stream), "sync level")) return false;
+    levelStart += levelCount;
+    levelCount = uint32_t(t);
+    trisPlaced += uint32_t(t >> 32);
+    if(levelStart + levelCount > numInner || trisPlaced > n)
     {
-      err = std::string(what) + ": " + hipGetErrorString(e);
+      err = "BVH8 collapse overran its bounds";
       return false;
     }
-    return true;
-  };
-  Bvh8Output     r;  // becomes `out` once the collapse has succeeded: a failure leaves `out` empty
-  const uint32_t numInner = b2.numNodes;
-  const bool hostCollapse = opt.hostCollapse;
-  const int  leafTrisOpt  = 2;  // (see the note above Cand)
-  if(numInner > 0 && !hostCollapse)
-  {
-    // ---- device collapse, one level at a time (see the header comment) -------------------------------------------------------
-    DevBuf<Node8>              dNodes;
-    DevBuf<int>                itemsA, itemsB;
-    DevBuf<uint32_t>           dPerm;
-    DevBuf<unsigned long long> counts, offsets, totals;
-    DevBuf<uint8_t>            scanTemp;
-    size_t                     scanBytes = 0;
-    uint32_t                   trisPlaced = 0;
-    DpTables                   dp{nullptr, nullptr};
-    DevBuf<float>              dpCost;
-    DevBuf<int8_t>             dpSplit;
-    DevBuf<int>                dpParent, dpLeafParent;
-    DevBuf<unsigned>           dpArrive;
-    // every 8-wide node is rooted at a distinct BVH2 inner node: numInner bounds their number and the length of any level
-    if(!check(dNodes.alloc(numInner), "alloc BVH8 nodes (worst case)")) return false;
-    if(!check(itemsA.alloc(numInner), "alloc level items")) return false;
-    if(!check(itemsB.alloc(numInner), "alloc level items")) return false;
-    if(!check(dPerm.alloc(n), "alloc perm")) return false;
-    if(opt.keepRefit)  // the refit data (bvh_refit.hip): the box each triangle slot was filed under
-      if(!check(r.slotBox.alloc(n), "alloc refit slot boxes")) return false;
-    if(!check(counts.alloc(numInner), "alloc counts")) return false;
-    if(!check(offsets.alloc(numInner), "alloc offsets")) return false;
-    if(!check(totals.alloc(1), "alloc totals")) return false;
-    if(!check(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, counts.ptr, offsets.ptr, int(numInner), stream), "scan size")) return false;
-    if(!check(scanTemp.alloc(scanBytes), "alloc scan")) return false;
-    const int root = b2.root;
-    if(!check(hipMemcpyAsync(itemsA.ptr, &root, sizeof(int), hipMemcpyHostToDevice, stream), "seed level 0")) return false;
-    uint32_t levelStart = 0, levelCount = 1;
-    uint32_t   maxLeaf = uint32_t(leafTrisOpt);
-    // which BVH2 subtrees become the children of an 8-wide node (Bvh8Options; the images do not depend on it)
-    const bool sahDp   = opt.sahCollapse;
-    if(sahDp)
-    {
-      maxLeaf = std::min(maxLeaf, 3u);
-      if(!check(dpCost.alloc(8 * size_t(numInner)), "alloc DP cost")) return false;
-      if(!check(dpSplit.alloc(8 * size_t(numInner)), "alloc DP split")) return false;
-      if(!check(dpParent.alloc(numInner), "alloc DP parents")) return false;
-      if(!check(dpLeafParent.alloc(n), "alloc DP leaf parents")) return false;
-      if(!check(dpArrive.alloc(numInner), "alloc DP tickets")) return false;
-      if(!check(hipMemsetAsync(dpArrive.ptr, 0, sizeof(unsigned) * size_t(numInner), stream), "clear DP tickets")) return false;
-      dp = DpTables{dpCost.ptr, dpSplit.ptr};
-      hipLaunchKernelGGL(k_dp_parents, dim3((numInner + 255u) / 256u), dim3(256), 0, stream, int(numInner), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, root);
-      hipLaunchKernelGGL(k_dp_solve, dim3((n + 255u) / 256u), dim3(256), 0, stream, int(n), b2.nodes.ptr, dpParent.ptr, dpLeafParent.ptr, dpArrive.ptr, dp, maxLeaf);
-      if(!check(hipGetLastError(), "DP kernels")) return false;
-    }
-    while(levelCount > 0)
-    {
-      const unsigned g = (levelCount + 127u) / 128u;
-      hipLaunchKernelGGL(k_collapse_count, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr);
-      if(!check(hipcub::DeviceScan::ExclusiveSum(scanTemp.ptr, scanBytes, counts.ptr, offsets.ptr, int(levelCount), stream), "scan")) return false;
-      hipLaunchKernelGGL(k_collapse_emit, dim3(g), dim3(128), 0, stream, int(levelCount), itemsA.ptr, b2.nodes.ptr, dp, maxLeaf, counts.ptr, offsets.ptr, levelStart,
-                         levelStart + levelCount, trisPlaced, dNodes.ptr, itemsB.ptr, dPerm.ptr, totals.ptr, r.slotBox.ptr);
-      r.levels.push_back(levelStart);
-      unsigned long long t = 0;
-      if(!check(hipGetLastError(), "collapse kernels")) return false;
-      if(!check(hipMemcpyAsync(&t, totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream), "read level totals")) return false;
-      if(!check(hipStreamSynchronize(stream), "sync level")) return false;
-      levelStart += levelCount;
-      levelCount = uint32_t(t);
-      trisPlaced += uint32_t(t >> 32);
-      if(levelStart + levelCount > numInner || trisPlaced > n)
-      {
-        err = "BVH8 collapse overran its bounds";
-        return false;
-      }
-      std::swap(itemsA, itemsB);
-    }
-    const uint32_t numNodes8 = levelStart;
-    if(trisPlaced != n)
-    {
-      err = "BVH8 collapse lost triangles";
-      return false;
-    }
-    if(!check(r.nodes.alloc(5 * size_t(numNodes8)), "alloc BVH8 nodes")) return false;
-    if(!check(hipMemcpyAsync(r.nodes.ptr, dNodes.ptr, sizeof(Node8) * size_t(numNodes8), hipMemcpyDeviceToDevice, stream), "copy BVH8 nodes")) return false;
-    r.levels.push_back(numNodes8);
-    if(opt.keepRefit)  // (filled by the first pass of k_refit_level, which the caller runs over the new tree)
-      if(!check(r.nodeBox.alloc(numNodes8), "alloc refit node boxes")) return false;
-    if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
-    hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
-    if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
-    r.numNodes  = numNodes8;
-    r.numTris   = n;
-    r.numLevels = uint32_t(r.levels.size()) - 1u;
-    out         = std::move(r);
-    return true;
+    std::swap(itemsA, itemsB);
   }
-  // ---- host collapse (A/B reference, and the one-triangle scene): download the BVH2 -------------------------------------------
-
-  std::vector<float4> nodes2(size_t(numInner) * 4);
-  if(numInner && !check(hipMemcpy(nodes2.data(), b2.nodes.ptr, nodes2.size() * sizeof(float4), hipMemcpyDeviceToHost), "download BVH2"))
-    return false;
-  std::vector<DevTri> tris2;
-  if(numInner == 0)  // single triangle: need its bounds
-  {
-    tris2.resize(n);
-    if(!check(hipMemcpy(tris2.data(), b2.tris.ptr, sizeof(DevTri) * n, hipMemcpyDeviceToHost), "download triangles"))
-      return false;
-  }
-  auto childRef = [&](int node, int which) {
-    float f = which == 0 ? nodes2[size_t(node) * 4 + 3].x : nodes2[size_t(node) * 4 + 3].y;
-    int   r;
-    memcpy(&r, &f, 4);
-    return r;
-  };
-  auto childBox = [&](int node, int which, float lo[3], float hi[3]) {
-    const float4 &n0 = nodes2[size_t(node) * 4 + 0], &n1 = nodes2[size_t(node) * 4 + 1], &n2 = nodes2[size_t(node) * 4 + 2];
-    if(which == 0)
-    {
-      lo[0] = n0.x; hi[0] = n0.y; lo[1] = n0.z; hi[1] = n0.w; lo[2] = n2.x; hi[2] = n2.y;
-    }
-    else
-    {
-      lo[0] = n1.x; hi[0] = n1.y; lo[1] = n1.z; hi[1] = n1.w; lo[2] = n2.z; hi[2] = n2.w;
-    }
-  };
-  // ---- subtree triangle counts ---------------------------------------------------------------------------------------------
-  std::vector<uint32_t> cnt(numInner, 0);
-  if(numInner)
-  {
-    std::vector<int> order;  // pre-order; children have larger positions than parents
-    order.reserve(numInner);
-    std::vector<int> stack{b2.root};
-    while(!stack.empty())
-    {
-      int v = stack.back();
-      stack.pop_back();
-      order.push_back(v);
-      for(int w = 0; w < 2; ++w)
-      {
-        int c = childRef(v, w);
-        if(c >= 0)
-          stack.push_back(c);
-      }
-    }
-    for(size_t k = order.size(); k-- > 0;)
-    {
-      int      v = order[k];
-      uint32_t c = 0;
-      for(int w = 0; w < 2; ++w)
-      {
-        int r = childRef(v, w);
-        c += r >= 0 ? cnt[size_t(r)] : 1u;
-      }
-      cnt[size_t(v)] = c;
-    }
-  }
-  auto triCount = [&](int ref) { return ref >= 0 ? cnt[size_t(ref)] : 1u; };
-  // triangles below a (small) subtree, left to right
-  std::function<void(int, std::vector<uint32_t>&)> collectTris = [&](int ref, std::vector<uint32_t>& dst) {
-    if(ref < 0)
-    {
-      dst.push_back(uint32_t(~ref));
-      return;
-    }
-    collectTris(childRef(ref, 0), dst);
-    collectTris(childRef(ref, 1), dst);
-  };
-
-  // ---- breadth-first collapse ----------------------------------------------------------------------------------------
-  std::vector<Node8>    nodes8;
-  std::vector<uint32_t> perm;  // new triangle index -> sorted (BVH2) triangle index
-  perm.reserve(n);
-  struct Work
-  {
-    uint32_t          node8;
-    uint32_t          level = 0;  // nodes above it
-    std::vector<Cand> cands;  // the (<= 2 at start) children to expand
-  };
-  std::vector<Work> queue;
-  {
-    Work w;
-    w.node8 = 0;
-    if(numInner == 0)
-    {
-      Cand c;
-      c.ref = ~0;
-      const DevTri& T = tris2[0];
-      float v[3][3] = {{T.a.x, T.a.y, T.a.z}, {T.a.x + T.b.x, T.a.y + T.b.y, T.a.z + T.b.z}, {T.a.x + T.c.x, T.a.y + T.c.y, T.a.z + T.c.z}};
-      for(int a = 0; a < 3; ++a)
-      {
-        c.lo[a] = std::min(v[0][a], std::min(v[1][a], v[2][a]));
-        c.hi[a] = std::max(v[0][a], std::max(v[1][a], v[2][a]));
-        // one ulp of slack each way: the BVH2 path bounds the true vertices too (k_tri_setup)
-        c.lo[a] = std::nextafter(c.lo[a], -FLT_MAX);
-        c.hi[a] = std::nextafter(c.hi[a], FLT_MAX);
-      }
-      w.cands.push_back(c);
-    }
-    else
-      for(int k = 0; k < 2; ++k)
-      {
-        Cand c;
-        c.ref = childRef(b2.root, k);
-        childBox(b2.root, k, c.lo, c.hi);
-        w.cands.push_back(c);
-      }
-    queue.push_back(std::move(w));
-    nodes8.emplace_back();
-  }
-  for(size_t qi = 0; qi < queue.size(); ++qi)
-  {
-    const std::vector<Cand> cands0 = std::move(queue[qi].cands);
-    std::vector<Cand>       cands;
-    const uint32_t          self = queue[qi].node8, level = queue[qi].level;
-    r.numLevels = std::max(r.numLevels, level + 1u);
-    uint32_t                MAX_LEAF_TRIS = uint32_t(leafTrisOpt);
-    for(;;)
-    {
-      cands = cands0;
-      // greedy: open the largest inner child that is too big to be a leaf until 8 children are reached
-      while(cands.size() < 8)
-      {
-        int   best = -1;
-        float bestA = -1.0f;
-        for(size_t k = 0; k < cands.size(); ++k)
-          if(cands[k].ref >= 0 && triCount(cands[k].ref) > MAX_LEAF_TRIS && areaOf(cands[k]) > bestA)
-          {
-            bestA = areaOf(cands[k]);
-            best  = int(k);
-          }
-        if(best < 0)
-          break;
-        int  ref = cands[size_t(best)].ref;
-        Cand a, b;
-        a.ref = childRef(ref, 0);
-        b.ref = childRef(ref, 1);
-        childBox(ref, 0, a.lo, a.hi);
-        childBox(ref, 1, b.lo, b.hi);
-        cands[size_t(best)] = a;
-        cands.push_back(b);
-      }
-      uint32_t leafTris = 0;
-      for(const Cand& c : cands)
-        leafTris += c.ref < 0 ? 1u : (triCount(c.ref) <= MAX_LEAF_TRIS ? triCount(c.ref) : 0u);
-      if(leafTris <= 31u || MAX_LEAF_TRIS <= 3u)
-        break;
-      MAX_LEAF_TRIS = 3u;  // would not fit the node's triangle mask
-    }
-    // node frame
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for(const Cand& c : cands)
-      for(int a = 0; a < 3; ++a)
-      {
-        lo[a] = std::min(lo[a], c.lo[a]);
-        hi[a] = std::max(hi[a], c.hi[a]);
-      }
-    // octant-ordered slot assignment (greedy on dot(centroid - centre, slot diagonal))
-    int  slotOf[8];
-    bool slotUsed[8] = {false, false, false, false, false, false, false, false}, done[8] = {false, false, false, false, false, false, false, false};
-    for(size_t round = 0; round < cands.size(); ++round)
-    {
-      float bestCost = -FLT_MAX;
-      int   bc = -1, bs = -1;
-      for(size_t c = 0; c < cands.size(); ++c)
-      {
-        if(done[c])
-          continue;
-        float d[3];
-        for(int a = 0; a < 3; ++a)
-          d[a] = 0.5f * (cands[c].lo[a] + cands[c].hi[a]) - 0.5f * (lo[a] + hi[a]);
-        for(int s = 0; s < 8; ++s)
-        {
-          if(slotUsed[s])
-            continue;
-          float cost = ((s & 1) ? d[0] : -d[0]) + ((s & 2) ? d[1] : -d[1]) + ((s & 4) ? d[2] : -d[2]);
-          if(cost > bestCost)
-          {
-            bestCost = cost;
-            bc       = int(c);
-            bs       = s;
-          }
-        }
-      }
-      slotOf[bc]   = bs;
-      slotUsed[bs] = true;
-      done[bc]     = true;
-    }
-    int candOfSlot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    for(size_t c = 0; c < cands.size(); ++c)
-      candOfSlot[slotOf[c]] = int(c);
-
-    Node8 N;
-    memset(&N, 0, sizeof(N));
-    // quantisation frame; grow an exponent until every child fits conservatively
-    int ex[3];
-    for(int a = 0; a < 3; ++a)
-    {
-      N.p[a]      = lo[a];
-      float ext   = hi[a] - lo[a];
-      ex[a]       = ext > 0.0f ? int(std::ceil(std::log2(double(ext) / 255.0))) : -126;
-      ex[a]       = std::max(-126, std::min(ex[a], 126));
-    }
-    for(int s = 0; s < 8; ++s)
-      for(int a = 0; a < 3; ++a)
-      {
-        N.qlo[a][s] = 255;  // empty slot: inverted box (and no valid bit)
-        N.qhi[a][s] = 0;
-      }
-    for(int a = 0; a < 3; ++a)
-    {
-      for(;;)
-      {
-        const float scale = std::ldexp(1.0f, ex[a]);
-        bool        fits  = true;
-        for(int s = 0; s < 8 && fits; ++s)
-        {
-          if(candOfSlot[s] < 0)
-            continue;
-          const Cand& c  = cands[size_t(candOfSlot[s])];
-          double      ql = std::floor((double(c.lo[a]) - double(N.p[a])) / double(scale));
-          double      qh = std::ceil((double(c.hi[a]) - double(N.p[a])) / double(scale));
-          int         il = int(std::max(0.0, std::min(255.0, ql))), ih = int(std::max(0.0, std::min(255.0, qh)));
-          while(il > 0 && std::fmaf(float(il), scale, N.p[a]) > c.lo[a])
-            --il;
-          while(ih < 255 && std::fmaf(float(ih), scale, N.p[a]) < c.hi[a])
-            ++ih;
-          if(std::fmaf(float(il), scale, N.p[a]) > c.lo[a] || std::fmaf(float(ih), scale, N.p[a]) < c.hi[a])
-            fits = false;
-          N.qlo[a][s] = uint8_t(il);
-          N.qhi[a][s] = uint8_t(ih);
-        }
-        if(fits || ex[a] >= 126)
-          break;
-        ++ex[a];
-      }
-      N.e[a] = uint8_t(ex[a] + 127);
-    }
-    // children: inner ones get consecutive node indices in slot order, leaf ones consecutive triangles
-    N.childBase = uint32_t(nodes8.size());
-    N.triBase   = uint32_t(perm.size());
-    for(int s = 0; s < 8; ++s)
-    {
-      if(candOfSlot[s] < 0)
-        continue;
-      const Cand& c = cands[size_t(candOfSlot[s])];
-      if(c.ref >= 0 && triCount(c.ref) > MAX_LEAF_TRIS)
-      {
-        N.imask |= uint8_t(1u << s);
-        Work w;
-        w.node8 = uint32_t(nodes8.size());
-        w.level = level + 1u;
-        for(int k = 0; k < 2; ++k)
-        {
-          Cand cc;
-          cc.ref = childRef(c.ref, k);
-          childBox(c.ref, k, cc.lo, cc.hi);
-          w.cands.push_back(cc);
-        }
-        nodes8.emplace_back();
-        queue.push_back(std::move(w));
-      }
-      else
-      {
-        const uint32_t count = triCount(c.ref);  // <= MAX_LEAF_TRIS <= 2
-        N.valid |= uint16_t((count >= 2u ? 3u : 1u) << (2 * s));
-        collectTris(c.ref, perm);
-      }
-    }
-    nodes8[self] = N;
-  }
-  if(perm.size() != n)
+  const uint32_t numNodes8 = levelStart;
+  if(trisPlaced != n)
   {
     err = "BVH8 collapse lost triangles";
     return false;
   }
-  // ---- upload ----------------------------------------------------------------------------------------------------------
-  DevBuf<uint32_t> dPerm;
-  if(!check(r.nodes.alloc(5 * nodes8.size()), "alloc BVH8 nodes")) return false;
-  if(!check(hipMemcpy(r.nodes.ptr, nodes8.data(), nodes8.size() * sizeof(Node8), hipMemcpyHostToDevice), "upload BVH8 nodes")) return false;
+  if(!check(r.nodes.alloc(5 * size_t(numNodes8)), "alloc BVH8 nodes")) return false;
+  if(!check(hipMemcpyAsync(r.nodes.ptr, dNodes.ptr, sizeof(Node8) * size_t(numNodes8), hipMemcpyDeviceToDevice, stream), "copy BVH8 nodes")) return false;
+  r.levels.push_back(numNodes8);
+  if(opt.keepRefit)  // (filled by the first pass of k_refit_level, which the caller runs over the new tree)
+    if(!check(r.nodeBox.alloc(numNodes8), "alloc refit node boxes")) return false;
   if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
-  if(!check(dPerm.alloc(n), "alloc perm")) return false;
-  if(!check(hipMemcpy(dPerm.ptr, perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice), "upload perm")) return false;
   hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
   if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
-  r.numNodes = uint32_t(nodes8.size());
-  r.numTris  = n;
-  out        = std::move(r);
+  r.numNodes  = numNodes8;
+  r.numTris   = n;
+  r.numLevels = uint32_t(r.levels.size()) - 1u;
+  return true;
+}
+
+// ---- host collapse (A/B reference, and the one-triangle scene): download the BVH2, collapse it (bvh8_collapse_host.h), upload ----
+bool collapseOnHost(const BvhBuildOutput& b2, hipStream_t stream, std::string& err, Bvh8Output& r)
+{
+  auto check = [&](hipError_t e, const char* what) { return hipOk(e, what, err); };
+  const uint32_t      n = b2.numTris, numInner = b2.numNodes;
+  std::vector<float4> nodes2(size_t(numInner) * 4);
+  if(numInner && !check(hipMemcpy(nodes2.data(), b2.nodes.ptr, nodes2.size() * sizeof(float4), hipMemcpyDeviceToHost), "download BVH2"))
+    return false;
+  float loneLo[3] = {0.0f, 0.0f, 0.0f}, loneHi[3] = {0.0f, 0.0f, 0.0f};
+  if(numInner == 0)  // single triangle: need its bounds
+  {
+    DevTri T;
+    if(!check(hipMemcpy(&T, b2.tris.ptr, sizeof(DevTri), hipMemcpyDeviceToHost), "download triangles")) return false;
+    const float v[3][3] = {{T.a.x, T.a.y, T.a.z}, {T.a.x + T.b.x, T.a.y + T.b.y, T.a.z + T.b.z}, {T.a.x + T.c.x, T.a.y + T.c.y, T.a.z + T.c.z}};
+    for(int a = 0; a < 3; ++a)
+    {
+      // one ulp of slack each way: the BVH2 path bounds the true vertices too (k_tri_setup)
+      loneLo[a] = std::nextafter(std::min(v[0][a], std::min(v[1][a], v[2][a])), -FLT_MAX);
+      loneHi[a] = std::nextafter(std::max(v[0][a], std::max(v[1][a], v[2][a])), FLT_MAX);
+    }
+  }
+  const Bvh8OnHost h = collapseBvh8OnHost(nodes2.data(), b2.root, numInner, n, loneLo, loneHi);
+  if(h.perm.size() != n)
+  {
+    err = "BVH8 collapse lost triangles";
+    return false;
+  }
+  DevBuf<uint32_t> dPerm;
+  if(!check(r.nodes.alloc(5 * h.nodes.size()), "alloc BVH8 nodes")) return false;
+  if(!check(hipMemcpy(r.nodes.ptr, h.nodes.data(), h.nodes.size() * sizeof(Node8), hipMemcpyHostToDevice), "upload BVH8 nodes")) return false;
+  if(!check(r.tris.alloc(n), "alloc BVH8 triangles")) return false;
+  if(!check(dPerm.alloc(n), "alloc perm")) return false;
+  if(!check(hipMemcpy(dPerm.ptr, h.perm.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice), "upload perm")) return false;
+  hipLaunchKernelGGL(k_reorder_tris, dim3((n + 255) / 256), dim3(256), 0, stream, n, dPerm.ptr, b2.tris.ptr, r.tris.ptr);
+  if(!check(hipGetLastError(), "k_reorder_tris") || !check(hipStreamSynchronize(stream), "sync")) return false;
+  r.numNodes  = uint32_t(h.nodes.size());
+  r.numTris   = n;
+  r.numLevels = h.numLevels;
+  return true;
+}
+
+}  // namespace
+
+bool buildBvh8(const BvhBuildOutput& b2, Bvh8Output& out, hipStream_t stream, std::string& err, const Bvh8Options& opt)
+{
+  out = Bvh8Output();
+  if(b2.numTris == 0)
+    return true;
+  Bvh8Output r;  // becomes `out` once the collapse has succeeded: a failure leaves `out` empty
+  const bool onDevice = b2.numNodes > 0 && !opt.hostCollapse;  // (a one-triangle tree has no BVH2 node to seed the first level with)
+  if(!(onDevice ? collapseOnDevice(b2, opt, stream, err, r) : collapseOnHost(b2, stream, err, r)))
+    return false;
+  out = std::move(r);
   return true;
 }
 

@@ -500,6 +500,50 @@ __global__ void k_tree_height(Bvh2Tree T, unsigned int* height)
     }                                                                                                                   \
   }
 
+constexpr int B = 256;  // threads per block of the builder's launches
+
+// MI_PT_BUILD_TIMING: the builder reports its reinsertion passes and the height of its tree on stderr
+bool buildTiming()
+{
+  static const bool timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  return timing;
+}
+
+// ---- the phases of buildBvh, each with the temporaries it owns (declared in buildBvh: see there why) ---------------------------------------------
+struct TriangleScratch  // the triangles -- references, once pre-split -- every later phase reads
+{
+  DevBuf<DevTri>   tris;
+  DevBuf<float4>   boxLo, boxHi;
+  DevBuf<uint32_t> bounds;  // of the box centres, as ordered integers (floatToOrdered)
+};
+struct SplitScratch
+{
+  DevBuf<float>    area, sum;
+  DevBuf<uint32_t> counts, offsets;
+  DevBuf<uint8_t>  temp;
+};
+struct SortScratch
+{
+  DevBuf<uint64_t> keysA, keysB;  // B: sorted
+  DevBuf<uint32_t> valsA, valsB;
+  DevBuf<uint8_t>  temp;
+};
+struct PlocScratch
+{
+  DevBuf<int>                cidA, cidB, nn;
+  DevBuf<float4>             cloA, chiA, cloB, chiB;
+  DevBuf<unsigned long long> flags, pos, totals;
+  DevBuf<uint8_t>            scanTemp;
+};
+struct KarrasScratch
+{
+  DevBuf<int2>     children;
+  DevBuf<int>      parentInternal, parentLeaf, nodeCnt;
+  DevBuf<float4>   nodeLo, nodeHi;
+  DevBuf<unsigned> arrive;
+};
+const uint32_t INIT_BOUNDS[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+
 }  // namespace
 
 // `passes` searches, each followed by up to `rounds` lock / move rounds and one refit; stops early once a pass moves fewer than one node
@@ -510,11 +554,11 @@ static bool reinsertBvh2(float4* nodes, int numInner, int root, int passes, int 
     *movesOut = 0;
   if(passes <= 0 || numInner < 3)
     return true;
-  static const bool          timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
+  const bool                 timing = buildTiming();
   const auto                 t0     = std::chrono::steady_clock::now();
   int                        passesRun = 0;
   uint32_t                   movesAll  = 0;
-  const int                  ids = 2 * numInner + 1, B = 256;
+  const int                  ids = 2 * numInner + 1;
   DevBuf<int>                parent, leafParent;
   DevBuf<ReinsertMove>       moves;
   DevBuf<unsigned long long> locks;
@@ -563,7 +607,6 @@ static bool bvh2Height(float4* nodes, int numInner, int root, hipStream_t stream
 {
   DevBuf<int>          parent, leafParent;
   DevBuf<unsigned int> h;
-  const int            B = 256;
   BUILD_CHECK(parent.alloc(numInner));
   BUILD_CHECK(leafParent.alloc(numInner + 1));
   BUILD_CHECK(h.alloc(1));
@@ -579,247 +622,194 @@ static bool bvh2Height(float4* nodes, int numInner, int root, hipStream_t stream
   return true;
 }
 
-bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, std::string& err)
+// k_tri_setup: world-space records, boxes and centroid bounds of the n triangles
+static bool setupTriangles(const BvhBuildInput& in, uint32_t n, TriangleScratch& tri, hipStream_t stream, std::string& err)
 {
-  out               = BvhBuildOutput();
-  uint32_t n        = in.numTris;  // becomes the number of REFERENCES once the large triangles are pre-split (below)
-  out.numTris       = n;
-  out.sceneTris     = n;
-  out.root          = BVH_EMPTY;
-  if(n == 0)
-    return true;
-  // every temporary lives to the end of the build (a free on the way would synchronise the device); `nodes` and `tris` become the
-  // output's only once the build has succeeded
-  DevBuf<float4>   nodes;
-  DevBuf<DevTri>   tris, trisTmp;
-  DevBuf<float4>   boxLo, boxHi, nodeLo, nodeHi;
-  DevBuf<uint32_t> bounds, valsA, valsB;
-  DevBuf<uint64_t> keysA, keysB;
-  DevBuf<int2>     children;
-  DevBuf<int>      parentInternal, parentLeaf, nodeCnt;
-  DevBuf<unsigned> arrive;
-  DevBuf<uint8_t>  sortTemp, scanTemp, splitTemp;
-  size_t           sortBytes = 0, scanBytes = 0;
-  DevBuf<int>      cidA, cidB, nn;
-  DevBuf<float4>   cloA, chiA, cloB, chiB;
-  DevBuf<unsigned long long> flags, pos, totals;
-  const int        B     = 256;
-  unsigned         gridT = (n + B - 1) / B;
-  DevBuf<float>    splitArea, splitSum;
-  DevBuf<uint32_t> splitCounts, splitOffsets;
   BuildTables T{in.nodes, in.prims, in.instFlags, in.nodeTriOffset, in.entryNode, in.numEntries};
-  const uint32_t initBounds[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-  uint32_t       hb[6]         = {0, 0, 0, 0, 0, 0};
-
-  BUILD_CHECK(trisTmp.alloc(n));
-  BUILD_CHECK(boxLo.alloc(n));
-  BUILD_CHECK(boxHi.alloc(n));
-  BUILD_CHECK(bounds.alloc(6));
-  BUILD_CHECK(hipMemcpyAsync(bounds.ptr, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_tri_setup, dim3(gridT), dim3(B), 0, stream, T, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, bounds.ptr);
+  BUILD_CHECK(tri.tris.alloc(n));
+  BUILD_CHECK(tri.boxLo.alloc(n));
+  BUILD_CHECK(tri.boxHi.alloc(n));
+  BUILD_CHECK(tri.bounds.alloc(6));
+  BUILD_CHECK(hipMemcpyAsync(tri.bounds.ptr, INIT_BOUNDS, sizeof(INIT_BOUNDS), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_tri_setup, dim3((n + B - 1) / B), dim3(B), 0, stream, T, n, tri.tris.ptr, tri.boxLo.ptr, tri.boxHi.ptr, tri.bounds.ptr);
   BUILD_CHECK(hipGetLastError());
+  return true;
+}
 
-  // ---- pre-splitting: references instead of triangles from here on (bvh_split.h) ----
-  if(in.splitFactor > 0.0f && n >= 2)
+// Pre-splitting: references instead of triangles from here on (bvh_split.h).  n: the number of triangles on entry, of references on return -- the
+// same where the scene is not split --, with `tri` holding them and their centroid bounds.
+static bool preSplitReferences(const BvhBuildInput& in, TriangleScratch& tri, SplitScratch& split, uint32_t& n, hipStream_t stream, std::string& err)
+{
+  const unsigned gridT = (n + B - 1) / B;
+  size_t         tb1 = 0, tb2 = 0;
+  BUILD_CHECK(split.area.alloc(n));
+  BUILD_CHECK(split.sum.alloc(1));
+  BUILD_CHECK(split.counts.alloc(n));
+  BUILD_CHECK(split.offsets.alloc(n));
+  BUILD_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb1, split.area.ptr, split.sum.ptr, int(n), stream));
+  BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, split.counts.ptr, split.offsets.ptr, int(n), stream));
+  BUILD_CHECK(split.temp.alloc(std::max(tb1, tb2)));
+  hipLaunchKernelGGL(k_split_area, dim3(gridT), dim3(B), 0, stream, n, tri.boxLo.ptr, tri.boxHi.ptr, split.area.ptr);
+  BUILD_CHECK(hipcub::DeviceReduce::Sum(split.temp.ptr, tb1, split.area.ptr, split.sum.ptr, int(n), stream));
+  // Splitting engages only where large triangles DOMINATE the scene's box area (the SAH is area weighted): the share of the summed box area held by
+  // triangles above 64 x the mean is 0 / 0.05 on the evenly tessellated atrium / street stand-ins -- whose trees splitting only perturbs (-1 %) --
+  // and 0.20 / 0.89 on their sliver versions (+6 % / +41 %).  The threshold is splitMinShare (default 0.1; 0 = always split).
+  bool engage = true;
+  if(in.splitMinShare > 0.0f)
   {
-    size_t tb1 = 0, tb2 = 0;
-    BUILD_CHECK(splitArea.alloc(n));
-    BUILD_CHECK(splitSum.alloc(1));
-    BUILD_CHECK(splitCounts.alloc(n));
-    BUILD_CHECK(splitOffsets.alloc(n));
-    BUILD_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb1, splitArea.ptr, splitSum.ptr, int(n), stream));
-    BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, splitCounts.ptr, splitOffsets.ptr, int(n), stream));
-    BUILD_CHECK(splitTemp.alloc(std::max(tb1, tb2)));
-    hipLaunchKernelGGL(k_split_area, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, splitArea.ptr);
-    BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp.ptr, tb1, splitArea.ptr, splitSum.ptr, int(n), stream));
-    // Splitting engages only where large triangles DOMINATE the scene's box area (the SAH is area weighted): the share of the summed box area held by
-    // triangles above 64 x the mean is 0 / 0.05 on the evenly tessellated atrium / street stand-ins -- whose trees splitting only perturbs (-1 %) --
-    // and 0.20 / 0.89 on their sliver versions (+6 % / +41 %).  The threshold is splitMinShare (default 0.1; 0 = always split).
-    bool engage = true;
-    if(in.splitMinShare > 0.0f)
-    {
-      float* large = reinterpret_cast<float*>(splitCounts.ptr);  // (not yet in use)
-      float  sums[2] = {0.0f, 0.0f};
-      hipLaunchKernelGGL(k_split_large_area, dim3(gridT), dim3(B), 0, stream, n, splitArea.ptr, splitSum.ptr, 64.0f, large);
-      BUILD_CHECK(hipMemcpyAsync(&sums[0], splitSum.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipcub::DeviceReduce::Sum(splitTemp.ptr, tb1, large, reinterpret_cast<float*>(splitOffsets.ptr), int(n), stream));
-      BUILD_CHECK(hipMemcpyAsync(&sums[1], splitOffsets.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipStreamSynchronize(stream));
-      engage = sums[0] > 0.0f && sums[1] >= in.splitMinShare * sums[0];
-    }
-    // the references are budgeted: more than half as many again as there are triangles means the rule does not fit this scene (a few
-    // giants among dust: the mean says little) -- the factor is doubled until it does, at most four times
-    float    factor = in.splitFactor;
-    uint32_t total  = n;
-    for(int attempt = 0; engage && attempt < 5; ++attempt, factor *= 2.0f)
-    {
-      hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, splitSum.ptr, factor, in.splitMaxDepth, nullptr, splitCounts.ptr, nullptr, nullptr, nullptr);
-      BUILD_CHECK(hipGetLastError());
-      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(splitTemp.ptr, tb2, splitCounts.ptr, splitOffsets.ptr, int(n), stream));
-      uint32_t lastOff = 0, lastCnt = 0;
-      BUILD_CHECK(hipMemcpyAsync(&lastOff, splitOffsets.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipMemcpyAsync(&lastCnt, splitCounts.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-      BUILD_CHECK(hipStreamSynchronize(stream));
-      total = lastOff + lastCnt;
-      if(uint64_t(total) <= uint64_t(n) + uint64_t(n) / 2u + 4096u && total < (1u << 26))
-        break;
-      total = n;
-    }
-    if(total > n)
-    {
-      // (the reference arrays replace the triangle arrays only once all three exist and are filled; a failure on the way frees what was allocated)
-      DevBuf<DevTri> refTris;
-      DevBuf<float4> refLo, refHi;
-      hipError_t     e = refTris.alloc(total);
-      if(e == hipSuccess) e = refLo.alloc(total);
-      if(e == hipSuccess) e = refHi.alloc(total);
-      if(e == hipSuccess)
-      {
-        hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, trisTmp.ptr, boxLo.ptr, boxHi.ptr, splitSum.ptr, factor, in.splitMaxDepth, splitOffsets.ptr, splitCounts.ptr, refTris.ptr, refLo.ptr, refHi.ptr);
-        e = hipGetLastError();
-      }
-      if(e == hipSuccess) e = hipStreamSynchronize(stream);
-      if(e != hipSuccess)
-      {
-        err = std::string("triangle pre-splitting: ") + hipGetErrorString(e);
-        return false;
-      }
-      trisTmp = std::move(refTris); boxLo = std::move(refLo); boxHi = std::move(refHi);
-      n           = total;
-      gridT       = (n + B - 1) / B;
-      out.numTris = n;
-      BUILD_CHECK(hipMemcpyAsync(bounds.ptr, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(k_centroid_bounds, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, bounds.ptr);
-      BUILD_CHECK(hipGetLastError());
-    }
-  }
-
-  BUILD_CHECK(tris.alloc(n));
-  if(n == 1)
-  {
-    BUILD_CHECK(hipMemcpyAsync(tris.ptr, trisTmp.ptr, sizeof(DevTri), hipMemcpyDeviceToDevice, stream));
+    float* large = reinterpret_cast<float*>(split.counts.ptr);  // (not yet in use)
+    float  sums[2] = {0.0f, 0.0f};
+    hipLaunchKernelGGL(k_split_large_area, dim3(gridT), dim3(B), 0, stream, n, split.area.ptr, split.sum.ptr, 64.0f, large);
+    BUILD_CHECK(hipMemcpyAsync(&sums[0], split.sum.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
+    BUILD_CHECK(hipcub::DeviceReduce::Sum(split.temp.ptr, tb1, large, reinterpret_cast<float*>(split.offsets.ptr), int(n), stream));
+    BUILD_CHECK(hipMemcpyAsync(&sums[1], split.offsets.ptr, sizeof(float), hipMemcpyDeviceToHost, stream));
     BUILD_CHECK(hipStreamSynchronize(stream));
-    out.root     = ~0;  // leaf 0
-    out.numNodes = 0;
+    engage = sums[0] > 0.0f && sums[1] >= in.splitMinShare * sums[0];
   }
-  else
+  // the references are budgeted: more than half as many again as there are triangles means the rule does not fit this scene (a few
+  // giants among dust: the mean says little) -- the factor is doubled until it does, at most four times
+  float    factor = in.splitFactor;
+  uint32_t total  = n;
+  for(int attempt = 0; engage && attempt < 5; ++attempt, factor *= 2.0f)
   {
-    BUILD_CHECK(keysA.alloc(n));
-    BUILD_CHECK(keysB.alloc(n));
-    BUILD_CHECK(valsA.alloc(n));
-    BUILD_CHECK(valsB.alloc(n));
-    hipLaunchKernelGGL(k_morton, dim3(gridT), dim3(B), 0, stream, n, boxLo.ptr, boxHi.ptr, bounds.ptr, keysA.ptr, valsA.ptr);
+    hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, tri.tris.ptr, tri.boxLo.ptr, tri.boxHi.ptr, split.sum.ptr, factor, in.splitMaxDepth, nullptr, split.counts.ptr, nullptr, nullptr, nullptr);
     BUILD_CHECK(hipGetLastError());
-    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, keysA.ptr, keysB.ptr, valsA.ptr, valsB.ptr, int(n), 0, 63, stream));
-    BUILD_CHECK(sortTemp.alloc(sortBytes));
-    BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(sortTemp.ptr, sortBytes, keysA.ptr, keysB.ptr, valsA.ptr, valsB.ptr, int(n), 0, 63, stream));
-
-    BUILD_CHECK(nodes.alloc(4 * size_t(n - 1)));
-    // the BVH2 over the sorted references, by either topology (both can run again: they read the keys, the boxes and the order only)
-    auto topology = [&](bool karras) -> bool {
-    if(!karras)
-    {
-      BUILD_CHECK(cidA.alloc(n)); BUILD_CHECK(cidB.alloc(n)); BUILD_CHECK(nn.alloc(n));
-      BUILD_CHECK(cloA.alloc(n)); BUILD_CHECK(chiA.alloc(n));
-      BUILD_CHECK(cloB.alloc(n)); BUILD_CHECK(chiB.alloc(n));
-      BUILD_CHECK(flags.alloc(n)); BUILD_CHECK(pos.alloc(n));
-      BUILD_CHECK(totals.alloc(1));
-      BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, flags.ptr, pos.ptr, int(n), stream));
-      BUILD_CHECK(scanTemp.alloc(scanBytes));
-      hipLaunchKernelGGL(k_ploc_init, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, cidA.ptr, cloA.ptr, chiA.ptr);
-      BUILD_CHECK(hipGetLastError());
-      int m = int(n), nodeBase = 0, rootRef = BVH_EMPTY;
-      while(m > 1)
-      {
-        const unsigned g = unsigned(m + B - 1) / B;
-        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, stream, m, cloA.ptr, chiA.ptr, nn.ptr);
-        hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, m, nn.ptr, flags.ptr);
-        BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(scanTemp.ptr, scanBytes, flags.ptr, pos.ptr, m, stream));
-        hipLaunchKernelGGL(k_ploc_emit, dim3(g), dim3(B), 0, stream, m, nn.ptr, flags.ptr, pos.ptr, cidA.ptr, cloA.ptr, chiA.ptr, cidB.ptr, cloB.ptr, chiB.ptr, nodeBase, nodes.ptr, totals.ptr);
-        BUILD_CHECK(hipGetLastError());
-        unsigned long long t = 0;
-        BUILD_CHECK(hipMemcpyAsync(&t, totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream));
-        BUILD_CHECK(hipStreamSynchronize(stream));
-        const int survivors = int(uint32_t(t)), merges = int(t >> 32);
-        if(merges < 1 || survivors != m - merges)
-        {
-          err = "PLOC round made no progress";
-          return false;
-        }
-        nodeBase += merges;
-        m = survivors;
-        std::swap(cidA, cidB); std::swap(cloA, cloB); std::swap(chiA, chiB);
-      }
-      BUILD_CHECK(hipMemcpy(&rootRef, cidA.ptr, sizeof(int), hipMemcpyDeviceToHost));
-      if(nodeBase != int(n) - 1 || rootRef != int(n) - 2)
-      {
-        err = "PLOC produced an inconsistent tree";
-        return false;
-      }
-      hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, trisTmp.ptr, tris.ptr);
-      BUILD_CHECK(hipGetLastError());
-      BUILD_CHECK(hipStreamSynchronize(stream));
-      out.root     = rootRef;
-      out.numNodes = n - 1;
-    }
-    else
-    {
-    BUILD_CHECK(children.alloc(n - 1));
-    BUILD_CHECK(parentInternal.alloc(n - 1));
-    BUILD_CHECK(parentLeaf.alloc(n));
-    BUILD_CHECK(nodeLo.alloc(n - 1));
-    BUILD_CHECK(nodeHi.alloc(n - 1));
-    BUILD_CHECK(arrive.alloc(n - 1));
-    BUILD_CHECK(nodeCnt.alloc(n - 1));
-    BUILD_CHECK(hipMemsetAsync(arrive.ptr, 0, sizeof(unsigned) * (n - 1), stream));
-    hipLaunchKernelGGL(k_hierarchy, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), keysB.ptr, children.ptr, parentInternal.ptr, parentLeaf.ptr);
-    BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_fit, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, children.ptr, parentInternal.ptr, parentLeaf.ptr, nodeLo.ptr, nodeHi.ptr, arrive.ptr, nodeCnt.ptr);
-    BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_emit_nodes, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), valsB.ptr, boxLo.ptr, boxHi.ptr, children.ptr, nodeLo.ptr, nodeHi.ptr, nodeCnt.ptr, nodes.ptr);
-    BUILD_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), valsB.ptr, trisTmp.ptr, tris.ptr);
-    BUILD_CHECK(hipGetLastError());
+    BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(split.temp.ptr, tb2, split.counts.ptr, split.offsets.ptr, int(n), stream));
+    uint32_t lastOff = 0, lastCnt = 0;
+    BUILD_CHECK(hipMemcpyAsync(&lastOff, split.offsets.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BUILD_CHECK(hipMemcpyAsync(&lastCnt, split.counts.ptr + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     BUILD_CHECK(hipStreamSynchronize(stream));
-    out.root     = 0;
-    out.numNodes = n - 1;
-    }
+    total = lastOff + lastCnt;
+    if(uint64_t(total) <= uint64_t(n) + uint64_t(n) / 2u + 4096u && total < (1u << 26))
+      break;
+    total = n;
+  }
+  if(total <= n)
     return true;
-    };
-    // A walk holds one stack entry per level it descends with another child pending, and drops what its stack cannot hold (pt_bvh.h: LaneStack).
-    // PLOC bounds no height: boxes nested in one another, each the union of itself with any smaller one, merge one pair per round into a tree as
-    // deep as its leaves are many.  With a limit (maxHeight: the caller's stack) a tree taller than that is built again with the Morton-prefix
-    // topology, whose height the key and index bits bound (63 + 32) -- and once more without reinsertion if the passes made it a chain again,
-    // which for nested boxes is what costs the least area.
-    static const bool timing = getenv("MI_PT_BUILD_TIMING") != nullptr;
-    bool              karras = in.karrasTopology;
-    int               passes = in.reinsertPasses;
-    for(;;)
-    {
-      out.reinsertMoves = 0;
-      if(!topology(karras))
-        return false;
-      if(out.numNodes >= 3 && passes > 0 && !reinsertBvh2(nodes.ptr, int(out.numNodes), out.root, passes, in.reinsertRounds, stream, err, &out.reinsertMoves))
-        return false;
-      if(in.maxHeight <= 0)
-        break;
-      if(!bvh2Height(nodes.ptr, int(out.numNodes), out.root, stream, err, out.height))
-        return false;
-      if(timing)
-        fprintf(stderr, "[mi_pt build] BVH2 height %u (limit %d): %s topology, %d reinsertion passes\n", out.height, in.maxHeight, karras ? "Morton-prefix" : "PLOC", passes);
-      if(out.height <= uint32_t(in.maxHeight))
-        break;
-      if(!karras)
-        karras = true;
-      else if(passes > 0)
-        passes = 0;
-      else
-      {
-        err = "the BVH2 is " + std::to_string(out.height) + " levels high, the walk's stack holds " + std::to_string(in.maxHeight);
-        return false;
-      }
-    }
+  // (the reference arrays replace the triangle arrays only once all three exist and are filled; a failure on the way frees what was allocated)
+  DevBuf<DevTri> refTris;
+  DevBuf<float4> refLo, refHi;
+  hipError_t     e = refTris.alloc(total);
+  if(e == hipSuccess) e = refLo.alloc(total);
+  if(e == hipSuccess) e = refHi.alloc(total);
+  if(e == hipSuccess)
+  {
+    hipLaunchKernelGGL(k_split_refs, dim3(gridT), dim3(B), 0, stream, n, tri.tris.ptr, tri.boxLo.ptr, tri.boxHi.ptr, split.sum.ptr, factor, in.splitMaxDepth, split.offsets.ptr, split.counts.ptr, refTris.ptr, refLo.ptr, refHi.ptr);
+    e = hipGetLastError();
   }
+  if(e == hipSuccess) e = hipStreamSynchronize(stream);
+  if(e != hipSuccess)
+  {
+    err = std::string("triangle pre-splitting: ") + hipGetErrorString(e);
+    return false;
+  }
+  tri.tris = std::move(refTris); tri.boxLo = std::move(refLo); tri.boxHi = std::move(refHi);
+  n        = total;
+  BUILD_CHECK(hipMemcpyAsync(tri.bounds.ptr, INIT_BOUNDS, sizeof(INIT_BOUNDS), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_centroid_bounds, dim3((n + B - 1) / B), dim3(B), 0, stream, n, tri.boxLo.ptr, tri.boxHi.ptr, tri.bounds.ptr);
+  BUILD_CHECK(hipGetLastError());
+  return true;
+}
+
+// k_morton and the radix sort: the references in Morton order (sort.keysB, sort.valsB)
+static bool sortByMorton(const TriangleScratch& tri, SortScratch& sort, uint32_t n, hipStream_t stream, std::string& err)
+{
+  size_t sortBytes = 0;
+  BUILD_CHECK(sort.keysA.alloc(n));
+  BUILD_CHECK(sort.keysB.alloc(n));
+  BUILD_CHECK(sort.valsA.alloc(n));
+  BUILD_CHECK(sort.valsB.alloc(n));
+  hipLaunchKernelGGL(k_morton, dim3((n + B - 1) / B), dim3(B), 0, stream, n, tri.boxLo.ptr, tri.boxHi.ptr, tri.bounds.ptr, sort.keysA.ptr, sort.valsA.ptr);
+  BUILD_CHECK(hipGetLastError());
+  BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, sort.keysA.ptr, sort.keysB.ptr, sort.valsA.ptr, sort.valsB.ptr, int(n), 0, 63, stream));
+  BUILD_CHECK(sort.temp.alloc(sortBytes));
+  BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(sort.temp.ptr, sortBytes, sort.keysA.ptr, sort.keysB.ptr, sort.valsA.ptr, sort.valsB.ptr, int(n), 0, 63, stream));
+  return true;
+}
+
+// The BVH2 over the sorted references by PLOC clustering: the records into `nodes`, the references in tree order into `tris`, the root into `out`.
+// (Either topology can run again: both read the keys, the boxes and the order only.)
+static bool plocTopology(const TriangleScratch& tri, const SortScratch& sort, PlocScratch& ploc, uint32_t n, DevBuf<float4>& nodes, DevBuf<DevTri>& tris,
+                         BvhBuildOutput& out, hipStream_t stream, std::string& err)
+{
+  const unsigned gridT = (n + B - 1) / B;
+  size_t         scanBytes = 0;
+  BUILD_CHECK(ploc.cidA.alloc(n)); BUILD_CHECK(ploc.cidB.alloc(n)); BUILD_CHECK(ploc.nn.alloc(n));
+  BUILD_CHECK(ploc.cloA.alloc(n)); BUILD_CHECK(ploc.chiA.alloc(n));
+  BUILD_CHECK(ploc.cloB.alloc(n)); BUILD_CHECK(ploc.chiB.alloc(n));
+  BUILD_CHECK(ploc.flags.alloc(n)); BUILD_CHECK(ploc.pos.alloc(n));
+  BUILD_CHECK(ploc.totals.alloc(1));
+  BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, ploc.flags.ptr, ploc.pos.ptr, int(n), stream));
+  BUILD_CHECK(ploc.scanTemp.alloc(scanBytes));
+  hipLaunchKernelGGL(k_ploc_init, dim3(gridT), dim3(B), 0, stream, int(n), sort.valsB.ptr, tri.boxLo.ptr, tri.boxHi.ptr, ploc.cidA.ptr, ploc.cloA.ptr, ploc.chiA.ptr);
+  BUILD_CHECK(hipGetLastError());
+  int m = int(n), nodeBase = 0, rootRef = BVH_EMPTY;
+  while(m > 1)
+  {
+    const unsigned g = unsigned(m + B - 1) / B;
+    hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, stream, m, ploc.cloA.ptr, ploc.chiA.ptr, ploc.nn.ptr);
+    hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, m, ploc.nn.ptr, ploc.flags.ptr);
+    BUILD_CHECK(hipcub::DeviceScan::ExclusiveSum(ploc.scanTemp.ptr, scanBytes, ploc.flags.ptr, ploc.pos.ptr, m, stream));
+    hipLaunchKernelGGL(k_ploc_emit, dim3(g), dim3(B), 0, stream, m, ploc.nn.ptr, ploc.flags.ptr, ploc.pos.ptr, ploc.cidA.ptr, ploc.cloA.ptr, ploc.chiA.ptr, ploc.cidB.ptr, ploc.cloB.ptr, ploc.chiB.ptr, nodeBase, nodes.ptr, ploc.totals.ptr);
+    BUILD_CHECK(hipGetLastError());
+    unsigned long long t = 0;
+    BUILD_CHECK(hipMemcpyAsync(&t, ploc.totals.ptr, sizeof(t), hipMemcpyDeviceToHost, stream));
+    BUILD_CHECK(hipStreamSynchronize(stream));
+    const int survivors = int(uint32_t(t)), merges = int(t >> 32);
+    if(merges < 1 || survivors != m - merges)
+    {
+      err = "PLOC round made no progress";
+      return false;
+    }
+    nodeBase += merges;
+    m = survivors;
+    std::swap(ploc.cidA, ploc.cidB); std::swap(ploc.cloA, ploc.cloB); std::swap(ploc.chiA, ploc.chiB);
+  }
+  BUILD_CHECK(hipMemcpy(&rootRef, ploc.cidA.ptr, sizeof(int), hipMemcpyDeviceToHost));
+  if(nodeBase != int(n) - 1 || rootRef != int(n) - 2)
+  {
+    err = "PLOC produced an inconsistent tree";
+    return false;
+  }
+  hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), sort.valsB.ptr, tri.tris.ptr, tris.ptr);
+  BUILD_CHECK(hipGetLastError());
+  BUILD_CHECK(hipStreamSynchronize(stream));
+  out.root     = rootRef;
+  out.numNodes = n - 1;
+  return true;
+}
+
+// ... by the Morton-prefix hierarchy of Karras 2012, whose height the key and index bits bound
+static bool karrasTopology(const TriangleScratch& tri, const SortScratch& sort, KarrasScratch& karras, uint32_t n, DevBuf<float4>& nodes, DevBuf<DevTri>& tris,
+                           BvhBuildOutput& out, hipStream_t stream, std::string& err)
+{
+  const unsigned gridT = (n + B - 1) / B;
+  BUILD_CHECK(karras.children.alloc(n - 1));
+  BUILD_CHECK(karras.parentInternal.alloc(n - 1));
+  BUILD_CHECK(karras.parentLeaf.alloc(n));
+  BUILD_CHECK(karras.nodeLo.alloc(n - 1));
+  BUILD_CHECK(karras.nodeHi.alloc(n - 1));
+  BUILD_CHECK(karras.arrive.alloc(n - 1));
+  BUILD_CHECK(karras.nodeCnt.alloc(n - 1));
+  BUILD_CHECK(hipMemsetAsync(karras.arrive.ptr, 0, sizeof(unsigned) * (n - 1), stream));
+  hipLaunchKernelGGL(k_hierarchy, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), sort.keysB.ptr, karras.children.ptr, karras.parentInternal.ptr, karras.parentLeaf.ptr);
+  BUILD_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_fit, dim3(gridT), dim3(B), 0, stream, int(n), sort.valsB.ptr, tri.boxLo.ptr, tri.boxHi.ptr, karras.children.ptr, karras.parentInternal.ptr, karras.parentLeaf.ptr, karras.nodeLo.ptr, karras.nodeHi.ptr, karras.arrive.ptr, karras.nodeCnt.ptr);
+  BUILD_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_emit_nodes, dim3((n - 1 + B - 1) / B), dim3(B), 0, stream, int(n), sort.valsB.ptr, tri.boxLo.ptr, tri.boxHi.ptr, karras.children.ptr, karras.nodeLo.ptr, karras.nodeHi.ptr, karras.nodeCnt.ptr, nodes.ptr);
+  BUILD_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_emit_tris, dim3(gridT), dim3(B), 0, stream, int(n), sort.valsB.ptr, tri.tris.ptr, tris.ptr);
+  BUILD_CHECK(hipGetLastError());
+  BUILD_CHECK(hipStreamSynchronize(stream));
+  out.root     = 0;
+  out.numNodes = n - 1;
+  return true;
+}
+
+// the centroid bounds the setup (or the pre-split) left on the device, as floats
+static bool centroidBoundsOf(const DevBuf<uint32_t>& bounds, BvhBuildOutput& out, std::string& err)
+{
+  uint32_t hb[6] = {0, 0, 0, 0, 0, 0};
   BUILD_CHECK(hipMemcpy(hb, bounds.ptr, sizeof(hb), hipMemcpyDeviceToHost));
   for(int c = 0; c < 3; ++c)
   {
@@ -832,6 +822,81 @@ bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, 
     out.centroidLo[c] = toF(hb[c]);
     out.centroidHi[c] = toF(hb[3 + c]);
   }
+  return true;
+}
+
+bool buildBvh(const BvhBuildInput& in, BvhBuildOutput& out, hipStream_t stream, std::string& err)
+{
+  out               = BvhBuildOutput();
+  uint32_t n        = in.numTris;  // becomes the number of REFERENCES once the large triangles are pre-split (below)
+  out.numTris       = n;
+  out.sceneTris     = n;
+  out.root          = BVH_EMPTY;
+  if(n == 0)
+    return true;
+  // every temporary of the phases lives to the end of the build (a free on the way would synchronise the device): all are declared here and
+  // handed down by reference.  What frees on the way is what did before: the locals of reinsertBvh2 and bvh2Height and the three arrays the
+  // pre-split's commit replaces.  `nodes` and `tris` become the output's only once the build has succeeded
+  DevBuf<float4>  nodes;
+  DevBuf<DevTri>  tris;
+  TriangleScratch tri;
+  SplitScratch    split;
+  SortScratch     sort;
+  PlocScratch     ploc;
+  KarrasScratch   karras;
+  if(!setupTriangles(in, n, tri, stream, err))
+    return false;
+  if(in.splitFactor > 0.0f && n >= 2 && !preSplitReferences(in, tri, split, n, stream, err))
+    return false;
+  out.numTris = n;
+  BUILD_CHECK(tris.alloc(n));
+  if(n == 1)
+  {
+    BUILD_CHECK(hipMemcpyAsync(tris.ptr, tri.tris.ptr, sizeof(DevTri), hipMemcpyDeviceToDevice, stream));
+    BUILD_CHECK(hipStreamSynchronize(stream));
+    out.root     = ~0;  // leaf 0
+    out.numNodes = 0;
+  }
+  else
+  {
+    if(!sortByMorton(tri, sort, n, stream, err))
+      return false;
+    BUILD_CHECK(nodes.alloc(4 * size_t(n - 1)));
+    // A walk holds one stack entry per level it descends with another child pending, and drops what its stack cannot hold (pt_bvh.h: LaneStack).
+    // PLOC bounds no height: boxes nested in one another, each the union of itself with any smaller one, merge one pair per round into a tree as
+    // deep as its leaves are many.  With a limit (maxHeight: the caller's stack) a tree taller than that is built again with the Morton-prefix
+    // topology, whose height the key and index bits bound (63 + 32) -- and once more without reinsertion if the passes made it a chain again,
+    // which for nested boxes is what costs the least area.
+    bool useKarras = in.karrasTopology;
+    int  passes = in.reinsertPasses;
+    for(;;)
+    {
+      out.reinsertMoves = 0;
+      if(!(useKarras ? karrasTopology(tri, sort, karras, n, nodes, tris, out, stream, err) : plocTopology(tri, sort, ploc, n, nodes, tris, out, stream, err)))
+        return false;
+      if(out.numNodes >= 3 && passes > 0 && !reinsertBvh2(nodes.ptr, int(out.numNodes), out.root, passes, in.reinsertRounds, stream, err, &out.reinsertMoves))
+        return false;
+      if(in.maxHeight <= 0)
+        break;
+      if(!bvh2Height(nodes.ptr, int(out.numNodes), out.root, stream, err, out.height))
+        return false;
+      if(buildTiming())
+        fprintf(stderr, "[mi_pt build] BVH2 height %u (limit %d): %s topology, %d reinsertion passes\n", out.height, in.maxHeight, useKarras ? "Morton-prefix" : "PLOC", passes);
+      if(out.height <= uint32_t(in.maxHeight))
+        break;
+      if(!useKarras)
+        useKarras = true;
+      else if(passes > 0)
+        passes = 0;
+      else
+      {
+        err = "the BVH2 is " + std::to_string(out.height) + " levels high, the walk's stack holds " + std::to_string(in.maxHeight);
+        return false;
+      }
+    }
+  }
+  if(!centroidBoundsOf(tri.bounds, out, err))
+    return false;
   out.nodes = std::move(nodes);
   out.tris  = std::move(tris);
   return true;

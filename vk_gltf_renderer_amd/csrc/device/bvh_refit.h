@@ -4,6 +4,7 @@
 // (tests/host_shim/refit_on_host.cpp).
 #pragma once
 #include <cfloat>
+#include <cmath>
 
 #include "pt_scene.h"
 
@@ -82,9 +83,20 @@ PT_DEV void worldTriangle(const MiGltfRenderNode& rn, const DevPrim& rp, int rno
   lo[2] = fminf(lo[2], fminf(p1.z, p2.z)); hi[2] = fmaxf(hi[2], fmaxf(p1.z, p2.z));
 }
 
+// What the host collapse (bvh8_collapse_host.h) runs as well is callable from the host pass of hipcc, where __fmaf_rn has no definition.
+#define PT_HOST_DEV __host__ PT_DEV
+PT_HOST_DEV float fmaOnce(float a, float b, float c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __fmaf_rn(a, b, c);
+#else
+  return std::fmaf(a, b, c);
+#endif
+}
+
 // Quantisation of one axis of an 8-wide node: frame from p = lo, children = the boxes [clo, chi] of the slots set in `used`.  An exponent
 // grows until every child's decoded box fmaf(q, 2^e, p) contains its true box; empty slots hold an inverted box.  Returns e + 127.
-PT_DEV uint8_t quantiseAxis8(float p, float lo, float hi, const float (&clo)[8], const float (&chi)[8], uint32_t used, uint8_t (&qlo)[8], uint8_t (&qhi)[8])
+PT_HOST_DEV uint8_t quantiseAxis8(float p, float lo, float hi, const float (&clo)[8], const float (&chi)[8], uint32_t used, uint8_t (&qlo)[8], uint8_t (&qhi)[8])
 {
   const float ext = hi - lo;
   int         ex  = ext > 0.0f ? int(ceil(log2(double(ext) / 255.0))) : -126;
@@ -105,11 +117,11 @@ PT_DEV uint8_t quantiseAxis8(float p, float lo, float hi, const float (&clo)[8],
       const double ql = floor((double(clo[sl]) - double(p)) / double(scale));
       const double qh = ceil((double(chi[sl]) - double(p)) / double(scale));
       int          il = int(fmax(0.0, fmin(255.0, ql))), ih = int(fmax(0.0, fmin(255.0, qh)));
-      while(il > 0 && __fmaf_rn(float(il), scale, p) > clo[sl])
+      while(il > 0 && fmaOnce(float(il), scale, p) > clo[sl])
         --il;
-      while(ih < 255 && __fmaf_rn(float(ih), scale, p) < chi[sl])
+      while(ih < 255 && fmaOnce(float(ih), scale, p) < chi[sl])
         ++ih;
-      if(__fmaf_rn(float(il), scale, p) > clo[sl] || __fmaf_rn(float(ih), scale, p) < chi[sl])
+      if(fmaOnce(float(il), scale, p) > clo[sl] || fmaOnce(float(ih), scale, p) < chi[sl])
         fits = false;
       qlo[sl] = uint8_t(il);
       qhi[sl] = uint8_t(ih);
@@ -121,8 +133,8 @@ PT_DEV uint8_t quantiseAxis8(float p, float lo, float hi, const float (&clo)[8],
   return uint8_t(ex + 127);
 }
 // ... of the whole node: frame [lo, hi] (the union of its children), clo / chi per axis and slot.  Sets p, e, qlo and qhi.
-// k_collapse_emit and k_refit_level both call this, so equal boxes give equal bytes.
-PT_DEV void quantiseNode8(Node8& N, const float lo[3], const float hi[3], const float (&clo)[3][8], const float (&chi)[3][8], uint32_t used)
+// k_collapse_emit, the host collapse and k_refit_level all call this, so equal boxes give equal bytes.
+PT_HOST_DEV void quantiseNode8(Node8& N, const float lo[3], const float hi[3], const float (&clo)[3][8], const float (&chi)[3][8], uint32_t used)
 {
   for(int a = 0; a < 3; ++a)
   {
